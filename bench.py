@@ -7,8 +7,16 @@ value and old-log-prob passes, reward scaling, GAE and the PPO epochs (5 x minib
 S = 500, K = 20 DDPM steps (K' = 10), bf16 denoiser. value = whole-job env-steps/s over the full
 iteration (rollout + update), summed over ranks (weak scaling: 64 envs per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line. --full adds what
+takes runs of its own after the timed region: one instrumented iteration (per-minibatch and host
+times), the sampler burst with its roofline / latency-floor figures, the live per-kernel timings
+with the committed profile as a cross-check, and the CPU baseline (--no-cpu-baseline drops that
+leg). --dump-outputs DIR writes what the last timed step left its caller as DIR/<name>.npy.
+Every step trains from the same seeded parameters and optimizer state, put back outside the timer
+(restore_trained_state says why), so that two runs with the same arguments compute the same.
 """
 import argparse
 import json
@@ -274,6 +282,146 @@ def sampler_burst_ms(agent, n=30):
     return ev0.elapsed_time(ev1) / n, n
 
 
+def full_figures(args, cfg, agent, barrier, emu):
+    """--full: the figures that take untimed runs of their own after the timed region (one
+    instrumented iteration, the sampler burst, one iteration under the library's kernel timer)."""
+    d = agent.model.dims
+    agent.sampler_events, agent.update_events = [], []   # instrumented, untimed
+    agent.host_profile = {}
+    agent.iteration(force_train=True)
+    barrier()
+    hp = agent.host_profile
+    host_us = {k: 1e6 * v / max(1, hp.get("minibatches", 0)) for k, v in hp.items() if k != "minibatches"}
+    loop_samp_ms = sum(a.elapsed_time(b) for a, b in agent.sampler_events) / max(1, len(agent.sampler_events))
+    samp_ms, n_burst = sampler_burst_ms(agent)
+    upd_ms = sum(a.elapsed_time(b) for a, b in agent.update_events) / max(1, len(agent.update_events))
+    flops = sampler_flops_per_env(d) * agent.n_envs
+    prec = agent.model.precision
+    members = sampler_layout(d, prec, agent.n_envs)
+    from diffusionpolicyoptimization_amd import ops as _ops
+    plan = _ops.sampler_plan(d, prec, agent.n_envs)
+    kname = {0: "sample_kernel", 2: "sample_split4_kernel"}[plan["kernel"]]
+    achieved = flops / (samp_ms * 1e-3) / 1e12
+    traffic = None
+    if os.path.exists(args.traffic_json):
+        with open(args.traffic_json) as f:
+            tj = json.load(f)
+        if kname + "<" in tj.get("kernel", "") and tj.get("precision") == prec and tj.get("envs") == agent.n_envs:
+            traffic = tj.get("hbm_bytes_per_launch")
+    if members:
+        P = plan["members"] or SPLIT_DEFAULT_P
+        step_us = samp_ms * 1e3 / d.denoising_steps
+        floor_us = SPLIT_XCHG_US[P] + (SPLIT_MFMA_US_F32 if prec == "fp32" else SPLIT_MFMA_US)[P]
+        bound = {"kind": "latency", "kernel": kname, "workgroups_per_16_envs": members, "members_per_set": P,
+                 "sampler_plan": plan,
+                 "us_per_denoising_step": step_us, "floor_us_per_step": floor_us, "frac": floor_us / step_us,
+                 "note": (f"each 16-env group runs on {P} CUs with 1/{P} of an actor resident in registers and "
+                          "LDS (the base and fine-tuned actors' steps on two such member sets when "
+                          "workgroups_per_16_envs is twice members_per_set); a denoising step is a dependent "
+                          "chain of small GEMMs (M = 16 envs; l2 folded into the out-Dense) and one cross-CU "
+                          "partial-sum exchange, so its floor "
+                          "is that exchange (tools/xchg_probe2.hip) plus the step's MFMA issue, not bytes or "
+                          "FLOPs; see DESIGN.md")}
+    else:
+        stream_b = sampler_stream_bytes_per_tile(d, prec)
+        bound = {"kind": "load_path", "kernel": kname, "bytes_per_cu_per_launch": stream_b,
+                 "achieved_GBs_per_cu": stream_b / (samp_ms * 1e-3) / 1e9, "peak_GBs_per_cu": CU_LOAD_PEAK_GBS,
+                 "frac": stream_b / (samp_ms * 1e-3) / 1e9 / CU_LOAD_PEAK_GBS,
+                 "note": "each 16-row tile streams its actor's weights from L2 into one CU every denoising step"}
+    out = {
+        "sampler_bound": bound,
+        "roofline": {"bound": "mfma", "kernel": kname + " (K-step DDPM sampler, all layers fused)",
+                     "achieved": achieved, "peak": PEAK[prec], "unit": "TFLOP/s",
+                     "frac": achieved / PEAK[prec], "traffic": traffic,
+                     "avg_launch_ms": samp_ms, "flops_per_launch": flops, "burst_launches": n_burst,
+                     "in_loop_event_ms": loop_samp_ms if agent.sampler_events else None,
+                     "note": ("M = envs/GPU rows per GEMM: at 64 envs the sampler is a dependent chain of "
+                              "K x 3 small GEMMs (in-Dense, l1, the folded l2 + out-Dense), far below MFMA peak by "
+                              "construction; sampler_bound gives "
+                              "the figure that bounds it")},
+        "ppo_minibatch_avg_ms": upd_ms,
+        "host_us_per_minibatch": host_us,
+    }
+    if emu == 1:
+        mb_before = agent.timing["n_updates"]
+        live = kernel_times_live(agent)
+        n_mb_live = agent.timing["n_updates"] - mb_before
+        figs = kernel_figures(d, cfg.train.n_steps, agent.n_envs, cfg.train.batch_size, n_mb_live or 1, prec, live,
+                              "live: dppo_kernel_timing (HIP events around each launch) over one untimed iteration")
+        prof = kernel_stats_csv()
+        if prof:
+            n_mb_prof = prof.get("actor_rowtile_train", (0, n_mb_live))[1] or n_mb_live
+            cross = kernel_figures(d, cfg.train.n_steps, agent.n_envs, cfg.train.batch_size, n_mb_prof, prec, prof,
+                                   os.path.relpath(KERNEL_STATS_CSV, ROOT),
+                                   iters=max(1, round(n_mb_prof / max(1, n_mb_live))))
+            figs["profile_crosscheck"] = {k: v for k, v in cross.items() if k != "hbm_peak_GBs"}
+        out["kernels"] = figs
+    return out
+
+
+DUMP_MAX_ELEMS = 1 << 20   # per array (4 or 8 MB); the dump stays far below 64 MB in all
+
+
+def trained_state(agent):
+    """A copy of what an update changes: the trained parameters, the optimizer's moments and step
+    count (which also positions the LR schedule) and, for a learn_eta model, the eta logit's."""
+    m, opt = agent.model, agent.actor_optimizer
+    eta = (m.eta_state.clone(), m.eta_step_count) if m.learn_eta else None
+    return m.train_params.clone(), opt.m.clone(), opt.v.clone(), opt.iterations, eta
+
+
+def restore_trained_state(agent, state):
+    """Put trained_state() back and re-derive the packed weight images the kernels read.
+
+    The update sums its weight gradients with float atomics, in an order that varies from run to
+    run; AdamW turns that rounding into ~1e-4 relative differences in the parameters, and a rollout
+    of the updated policy through the envs amplifies them further with every iteration. So that a
+    step's inputs are the same in every run, each bench step trains from the same seeded parameters
+    and optimizer state. The envs, the noise counters and the reward scaler run on from step to
+    step: with the policy fixed they are the same in every run too. The work of a step is unchanged
+    (same kernels, same shapes)."""
+    import torch
+    m, opt = agent.model, agent.actor_optimizer
+    params, mom1, mom2, iterations, eta = state
+    m.train_params.copy_(params)
+    opt.m.copy_(mom1)
+    opt.v.copy_(mom2)
+    opt.iterations = iterations
+    m.repack()
+    if eta is not None:
+        m.eta_state.copy_(eta[0])
+        m.eta_step_count = eta[1]
+        m.refresh_eta()
+    torch.cuda.synchronize(agent.device)
+
+
+def dump_outputs(path, agent):
+    """What the last timed iteration left its caller, as path/<name>.npy: the trained parameters
+    (actor_ft then critic, flat fp32), the rollout it trained on (observations, denoising chains),
+    the passes over it (values, old log-probs), the scaled rewards (float64), advantages and
+    returns. An array of more than DUMP_MAX_ELEMS elements is written as a fixed sample of its
+    flattened elements (ascending indices drawn once from a generator seeded with 0, so two runs
+    sample the same places). The seeds of the weights, the sampler noise and the envs come from the
+    config and every step trains from the seeded start (restore_trained_state), so two runs with
+    the same arguments agree bit for bit in everything but the trained parameters, which carry the
+    rounding of one update's atomic gradient sums (~1e-4 of the largest parameter)."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize(agent.device)
+    os.makedirs(path, exist_ok=True)
+    m = agent.model
+    arrays = {"train_params": m.train_params, "obs_traj": agent.obs_traj, "chains_traj": agent.chains_traj,
+              "values": agent.values, "last_values": agent.last_values, "lp_old": agent.lp_old,
+              "reward_scaled": agent.reward_dev, "adv": agent.adv, "ret": agent.ret}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -285,7 +433,12 @@ def main():
     ap.add_argument("--n-steps", type=int, default=None, help="override S (chunks per rollout)")
     ap.add_argument("--precision", default=None)
     ap.add_argument("--batch-size", type=int, default=None, help="override train.batch_size (measurement)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the instrumented "
+                         "iteration, the sampler burst and its bounds, live per-kernel figures, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left its caller (see dump_outputs) as DIR/<name>.npy")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"))
     ap.add_argument("--emulate-ranks", type=int, default=1,
                     help="measurement mode: run ONE rank's share of an N-rank job on this GPU (the reference's "
@@ -331,10 +484,13 @@ def main():
     dev = agent.device
     d = agent.model.dims
 
+    # every step, warm-up ones included, trains from the seeded start (restored outside the timer)
+    start = trained_state(agent)
     for _ in range(args.warmup):
+        restore_trained_state(agent, start)
         agent.iteration(force_train=True)
     # the timed region carries no per-minibatch HIP timing events (their records sit on the
-    # minibatch chain); ppo_minibatch_avg_ms comes from one instrumented iteration after it
+    # minibatch chain); --full's ppo_minibatch_avg_ms comes from one instrumented iteration after it
     agent.sampler_events, agent.update_events = None, None
     agent.timing.update(rollout_s=0.0, update_s=0.0, n_updates=0, env_steps=0, iters=0)
 
@@ -343,61 +499,25 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    barrier()
-    t0 = time.perf_counter()
+    # an iteration starts and ends with the device idle, so the sum of the steps' times is the
+    # loop's time less the restores between them
+    elapsed = 0.0
     for _ in range(args.steps):
+        restore_trained_state(agent, start)
+        barrier()
+        t0 = time.perf_counter()
         agent.iteration(force_train=True)
+        torch.cuda.synchronize(dev)
+        elapsed += time.perf_counter() - t0
     barrier()
-    elapsed = time.perf_counter() - t0
     t = torch.tensor([elapsed, agent.timing["rollout_s"], agent.timing["update_s"]], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, t_roll, t_upd = t.tolist()
     n_updates = agent.timing["n_updates"]
 
-    agent.sampler_events, agent.update_events = [], []   # instrumented, untimed
-    agent.host_profile = {}
-    agent.iteration(force_train=True)
-    barrier()
-    hp = agent.host_profile
-    host_us = {k: 1e6 * v / max(1, hp.get("minibatches", 0)) for k, v in hp.items() if k != "minibatches"}
-    loop_samp_ms = sum(a.elapsed_time(b) for a, b in agent.sampler_events) / max(1, len(agent.sampler_events))
-    samp_ms, n_burst = sampler_burst_ms(agent)
-    upd_ms = sum(a.elapsed_time(b) for a, b in agent.update_events) / max(1, len(agent.update_events))
     env_steps = agent.n_envs_global * cfg.act_steps * cfg.train.n_steps * args.steps * emu
-    flops = sampler_flops_per_env(d) * agent.n_envs
     prec = agent.model.precision
-    members = sampler_layout(d, prec, agent.n_envs)
-    from diffusionpolicyoptimization_amd import ops as _ops
-    plan = _ops.sampler_plan(d, prec, agent.n_envs)
-    kname = {0: "sample_kernel", 2: "sample_split4_kernel"}[plan["kernel"]]
-    achieved = flops / (samp_ms * 1e-3) / 1e12
-    traffic = None
-    if os.path.exists(args.traffic_json):
-        with open(args.traffic_json) as f:
-            tj = json.load(f)
-        if kname + "<" in tj.get("kernel", "") and tj.get("precision") == prec and tj.get("envs") == agent.n_envs:
-            traffic = tj.get("hbm_bytes_per_launch")
-    if members:
-        P = plan["members"] or SPLIT_DEFAULT_P
-        step_us = samp_ms * 1e3 / d.denoising_steps
-        floor_us = SPLIT_XCHG_US[P] + (SPLIT_MFMA_US_F32 if prec == "fp32" else SPLIT_MFMA_US)[P]
-        bound = {"kind": "latency", "kernel": kname, "workgroups_per_16_envs": members, "members_per_set": P,
-                 "sampler_plan": plan,
-                 "us_per_denoising_step": step_us, "floor_us_per_step": floor_us, "frac": floor_us / step_us,
-                 "note": (f"each 16-env group runs on {P} CUs with 1/{P} of an actor resident in registers and "
-                          "LDS (the base and fine-tuned actors' steps on two such member sets when "
-                          "workgroups_per_16_envs is twice members_per_set); a denoising step is a dependent "
-                          "chain of small GEMMs (M = 16 envs; l2 folded into the out-Dense) and one cross-CU "
-                          "partial-sum exchange, so its floor "
-                          "is that exchange (tools/xchg_probe2.hip) plus the step's MFMA issue, not bytes or "
-                          "FLOPs; see DESIGN.md")}
-    else:
-        stream_b = sampler_stream_bytes_per_tile(d, prec)
-        bound = {"kind": "load_path", "kernel": kname, "bytes_per_cu_per_launch": stream_b,
-                 "achieved_GBs_per_cu": stream_b / (samp_ms * 1e-3) / 1e9, "peak_GBs_per_cu": CU_LOAD_PEAK_GBS,
-                 "frac": stream_b / (samp_ms * 1e-3) / 1e9 / CU_LOAD_PEAK_GBS,
-                 "note": "each 16-row tile streams its actor's weights from L2 into one CU every denoising step"}
     out = {
         "metric": METRIC, "value": env_steps / elapsed, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
@@ -421,34 +541,8 @@ def main():
         "ppo_updates_per_sec": n_updates / elapsed,
         "rollout_env_steps_per_sec": env_steps / t_roll if t_roll > 0 else None,
         "rollout_s_per_iter": t_roll / args.steps, "update_s_per_iter": t_upd / args.steps,
-        "sampler_bound": bound,
-        "roofline": {"bound": "mfma", "kernel": kname + " (K-step DDPM sampler, all layers fused)",
-                     "achieved": achieved, "peak": PEAK[prec], "unit": "TFLOP/s",
-                     "frac": achieved / PEAK[prec], "traffic": traffic,
-                     "avg_launch_ms": samp_ms, "flops_per_launch": flops, "burst_launches": n_burst,
-                     "in_loop_event_ms": loop_samp_ms if agent.sampler_events else None,
-                     "note": ("M = envs/GPU rows per GEMM: at 64 envs the sampler is a dependent chain of "
-                              "K x 3 small GEMMs (in-Dense, l1, the folded l2 + out-Dense), far below MFMA peak by "
-                              "construction; sampler_bound gives "
-                              "the figure that bounds it")},
-        "ppo_minibatch_avg_ms": upd_ms,
-        "host_us_per_minibatch": host_us,
     }
     n_mb_iter = n_updates / max(1, args.steps)
-    if emu == 1:
-        mb_before = agent.timing["n_updates"]
-        live = kernel_times_live(agent)
-        n_mb_live = agent.timing["n_updates"] - mb_before
-        figs = kernel_figures(d, cfg.train.n_steps, agent.n_envs, cfg.train.batch_size, n_mb_live or 1, prec, live,
-                              "live: dppo_kernel_timing (HIP events around each launch) over one untimed iteration")
-        prof = kernel_stats_csv()
-        if prof:
-            n_mb_prof = prof.get("actor_rowtile_train", (0, n_mb_live))[1] or n_mb_live
-            cross = kernel_figures(d, cfg.train.n_steps, agent.n_envs, cfg.train.batch_size, n_mb_prof, prec, prof,
-                                   os.path.relpath(KERNEL_STATS_CSV, ROOT),
-                                   iters=max(1, round(n_mb_prof / max(1, n_mb_live))))
-            figs["profile_crosscheck"] = {k: v for k, v in cross.items() if k != "hbm_peak_GBs"}
-        out["kernels"] = figs
     if emu > 1:
         out["emulated_ranks"] = emu
         out["scaling"] = "weak (emulated)"
@@ -458,8 +552,13 @@ def main():
                                             "per rank per iteration)")
         out["note"] = (f"value = {emu} x this rank's env steps / its wall time: the {emu}-GPU throughput this "
                        "rank's compute allows, all-reduce time excluded (an upper bound on the real run)")
-    if rank == 0 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(cfg, agent.n_envs, cfg.train.n_steps, cfg.train.batch_size)
+    # the dump comes before --full's untimed iterations, which write the same buffers again
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, agent)
+    if args.full:
+        out.update(full_figures(args, cfg, agent, barrier, emu))
+        if rank == 0 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(cfg, agent.n_envs, cfg.train.n_steps, cfg.train.batch_size)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
 for r in 1 2 3; do for v in main f32w16; do
   if [ $v = main ]; then L=""; else L=diffusionpolicyoptimization_amd/lib/variants/libdppo_hip_$v.so; fi
   log=gpurun_out/abf32_${v}_$r.log
-  DPPO_LIB=$L timeout -k 10 300 python -u bench.py --no-cpu-baseline --precision fp32 > $log 2>&1 || { echo "bench $v failed"; tail -20 $log; exit 1; }
+  DPPO_LIB=$L timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --precision fp32 > $log 2>&1 || { echo "bench $v failed"; tail -20 $log; exit 1; }
   python - $log $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

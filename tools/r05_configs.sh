@@ -12,6 +12,7 @@ F=cfg/gym/finetune
 run() {   # name, bench args...
   local name=$1; shift
   [ -n "$ONLY" ] && [[ ! $name =~ $ONLY ]] && return 0
+  set -- --full "$@"   # roofline and ppo_minibatch_avg_ms below are --full figures
   timeout -k 10 400 python -u bench.py --no-cpu-baseline "$@" > gpurun_out/bench_${tag}_$name.log 2>&1 \
     || { echo "bench $name failed"; tail -30 gpurun_out/bench_${tag}_$name.log; exit 1; }
   python - gpurun_out/bench_${tag}_$name.log $name <<'PY'

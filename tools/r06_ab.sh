@@ -12,7 +12,7 @@ if [ -n "$TESTS" ]; then
   tail -1 gpurun_out/${tag}_tests.log
 fi
 line() {   # label, env, bench args...
-  local lab=$1 envs=$2; shift 2
+  local lab=$1 envs=$2; shift 2; set -- --full "$@"   # ppo_minibatch_avg_ms below is a --full figure
   env $envs timeout -k 10 400 python -u bench.py --no-cpu-baseline "$@" > gpurun_out/${tag}_$lab.log 2>&1 || { tail -20 gpurun_out/${tag}_$lab.log; exit 1; }
   python - gpurun_out/${tag}_$lab.log $lab <<'PY'
 import json, sys

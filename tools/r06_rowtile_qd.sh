@@ -8,7 +8,7 @@ for r in 1 2; do
     if [ $v = main ]; then L=""; else L=diffusionpolicyoptimization_amd/lib/variants/libdppo_hip_$v.so; fi
     for emu in 1 8; do
       log=gpurun_out/qd_${v}_emu${emu}_$r.log
-      DPPO_LIB=$L timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps 2 --warmup 1 --emulate-ranks $emu > $log 2>&1 \
+      DPPO_LIB=$L timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps 2 --warmup 1 --emulate-ranks $emu > $log 2>&1 \
         || { echo "bench $v emu$emu failed"; tail -20 $log; exit 1; }
       python - $log $v $emu <<'PY'
 import json, sys

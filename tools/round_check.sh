@@ -10,7 +10,8 @@ export DPPO_PARITY_LOG=$GRAFT_REPO_ROOT/gpurun_out/parity_$tag.jsonl
 mkdir -p gpurun_out
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ${TESTS:+-k "$TESTS"} > gpurun_out/gpu_tests_$tag.log 2>&1 || { echo "tests failed"; tail -30 gpurun_out/gpu_tests_$tag.log; exit 1; }
 tail -3 gpurun_out/gpu_tests_$tag.log
-timeout -k 10 300 python -u bench.py > gpurun_out/bench_$tag.log 2>&1 || { echo "bench failed"; tail -30 gpurun_out/bench_$tag.log; exit 1; }
+out=$(dirname $DPPO_PARITY_LOG)
+timeout -k 10 300 python -u bench.py --full > $out/bench_$tag.log 2>&1 || { echo "bench failed"; tail -30 $out/bench_$tag.log; exit 1; }
 tail -1 gpurun_out/bench_$tag.log
 if [ -n "$LOWDIM" ]; then
   for spec in "1 0" "4 0" "1 20" "8 20"; do

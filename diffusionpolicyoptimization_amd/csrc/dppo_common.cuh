@@ -364,7 +364,7 @@ __device__ inline float mish_gradf(float x) {
 // t_emb(t) = Dense(2TD->TD)(mish(Dense(TD->2TD)(SinusoidalPosEmb(t)))) (mlp_diffusion.py:40-45,
 // modules.py:4-15), element by element. p: the actor's flat parameters (time_w1 [TD][2TD], time_b1,
 // time_w2 [2TD][TD], time_b2 at the given offsets). The dot products are explicit fmaf chains: the
-// pack's per-row blocks (pack.hip) and the fused optimizer step's last workgroup (update.hip) then
+// pack's per-row blocks (pack.hip) and the fused optimizer step's last workgroup (optimizer.hip) then
 // agree bit for bit whatever the compiler contracts in each kernel (left to it, the same source
 // compiled to different contractions in the two: last-ulp differences).
 // ------------------------------------------------------------------------------------------------

@@ -24,7 +24,7 @@ int dppo_pack_models(const Dims& D, int precision, const float* actor_params, vo
                      const float* critic_params, void* packed_critic, hipStream_t s, bool defer_sampler_tables = false,
                      void* const* zero_ptrs = nullptr, const size_t* zero_bytes = nullptr, int n_zero = 0);
 
-// The pack of one network as per-element stores (DPPO_STEP_FUSED_PACK, update.hip): each job maps
+// The pack of one network as per-element stores (DPPO_STEP_FUSED_PACK, optimizer.hip): each job maps
 // the elements [lo, hi) of the network's flat parameters to one image segment
 struct FuseJob {
     int kind;          // 0 = packed [IK][IN] image from a row-major [IK][IN] tensor, 1 = packed [IK][IN]

@@ -22,7 +22,7 @@ struct PpoWorkspace {
     float* pl2;
     // W_out's weight gradient through the folded forward (h3 = u2 W_l2 + a0 W_in + b_l2 + b_in):
     //   dW_out = W_l2^T pl2 + W_in^T pa0 + (b_l2 + b_in) db_out,  pa0 = a0^T dy [IN][XD] (dW GEMM),
-    // formed by the out_back groups after the dW (update.hip); zeroed with pl2 | pa0 | gseg
+    // formed by the out_back groups after the dW (backward_tail.hip); zeroed with pl2 | pa0 | gseg
     float* pa0;
     float* gseg;      // [64][H] per-t sums of dh1 (actor in-layer; 16 buckets in PPO, K in pretraining)
     float* cpl2;

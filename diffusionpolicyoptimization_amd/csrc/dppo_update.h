@@ -1,0 +1,43 @@
+// dppo_update.h — host-side declarations shared by the PPO update's translation units
+// (dw.hip, backward_tail.hip, optimizer.hip, update.hip).
+#pragma once
+#include "dppo_ppo.h"
+
+// ---- dw.hip: the grouped split-K weight-gradient GEMM -------------------------------------------
+enum { EXTRA_NONE = 0, EXTRA_ONES = 1, EXTRA_ONEHOT = 2 };
+// one problem of a grouped launch: G[Kx][N] += XT^T DT over the workspace rows, Gx its extra rows
+struct DWItem {
+    const void* XT; int Kx;
+    const void* DT; int N;
+    float* G;
+    int extra;
+    float* Gx;
+};
+// the output tile and LDS ring of a launch: the actor's 256-row tile on the full ring, or the critic's
+// 128-row tile on a 3-slot ring (it runs beside the actor's time-MLP backward, which needs LDS too)
+enum class DWTile { ACTOR, CRITIC };
+// Launches the items (at most 8) as one kernel over the workspace's ldm rows, in m-chunks of at least
+// min_chunk_rows rows, about one workgroup per CU. out_scale multiplies the outputs (1 / the backward
+// seed scale); rows_dev, when non-null, is a device-side row count that caps the rows summed.
+int launch_dw(DWTile tile, int precision, const DWItem* items, int n_items, const PpoWorkspace& ws, float out_scale,
+              const int* rows_dev, int min_chunk_rows, hipStream_t s);
+
+// ---- backward_tail.hip: what follows the dW launches -------------------------------------------
+// after the actor's dW: the time-MLP backward over nb buckets at t = q * TS (the bucket sums in
+// ws.gseg), W_out's gradient (out_back) and, with l2_back, l2's from ws.pl2, in one launch; without
+// l2_back the l2 gradient stays factored in its own region of ga (DPPO_PPO_L2_DEFERRED)
+int launch_time_bwd(const Dims& D, int precision, const PpoWorkspace& ws, const void* packed_actor,
+                    const float* actor_params, float* ga, int nb, int TS, hipStream_t s, bool l2_back = true);
+// the critic's l2 weight gradient from ws.cpl2 (N = 1); with zcnt, the launch also zeroes the
+// minibatch's sample counts zcnt[ws.crow_n[r]], r < *ws.crow_cnt
+int launch_critic_l2_back(const Dims& D, int precision, const PpoWorkspace& ws, const void* packed_critic, float* gc,
+                          uint32_t* zcnt, hipStream_t s);
+
+// ---- update.hip ---------------------------------------------------------------------------------
+// zero up to 4 byte ranges (4-B aligned, sizes multiples of 4) in one launch of `blocks` workgroups
+struct ZeroArgs { void* p[4]; size_t n[4]; };
+int launch_zero(const ZeroArgs& z, unsigned blocks, hipStream_t s);
+// Per-(device, stream) device scratch that kernels leave zeroed between uses, created zeroed on first
+// use and kept for the process (one process-wide table, update.hip)
+enum { SCRATCH_TICKET = 0, SCRATCH_CRIT_COUNT = 1 };
+int stream_scratch(hipStream_t s, int kind, size_t bytes, void** out);

@@ -470,10 +470,9 @@ static inline uint8_t* P_out(void* p) { return (uint8_t*)p; }
 // split sampler's tables: W_XS, FOLD / ROUT, TIN, B_OUT2), PACK_SAMPLER (those tables only),
 // PACK_SAMPLER_TEMB (those tables and the TEMB table: after a fused actor step, any precision). Every
 // pack with the main jobs of an actor is followed by the row tiles' fold (launch_rt_fold).
+// PACK_UPDATE leaves the TEMB rows out too: the row tiles derive theirs (writing them, the r04 pack,
+// measured no different; profiles/r05h_pack_temb_ab.txt)
 enum { PACK_ALL = 0, PACK_UPDATE = 1, PACK_SAMPLER = 2, PACK_SAMPLER_TEMB = 3 };
-#ifndef DPPO_PACK_UPDATE_TEMB
-#define DPPO_PACK_UPDATE_TEMB 0   // 1: PACK_UPDATE still writes the TEMB rows (the r04 pack; A/B builds)
-#endif
 static int add_mlp_jobs(PackArgs& a, int in_dim, int hidden, int out_dim, int time_dim, int precision,
                         const float* params, void* packed, int temb_steps, int time_stride, int what = PACK_ALL) {
     const MlpLayout L = make_mlp_layout(in_dim, hidden, out_dim, time_dim, precision, temb_steps);
@@ -485,7 +484,7 @@ static int add_mlp_jobs(PackArgs& a, int in_dim, int hidden, int out_dim, int ti
     const bool split_tables = actor && L.temb_steps > 0;
     const bool main_jobs = what == PACK_ALL || what == PACK_UPDATE;
     const bool sampler_tables = split_tables && (what == PACK_ALL || what == PACK_SAMPLER || what == PACK_SAMPLER_TEMB);
-    const bool temb_rows = L.temb_steps > 0 && (what != PACK_UPDATE || DPPO_PACK_UPDATE_TEMB);
+    const bool temb_rows = L.temb_steps > 0 && what != PACK_UPDATE;
     const int jobs = (main_jobs ? 11 + (actor ? 1 : 0) : 0) + (sampler_tables ? 1 : 0);
     if (a.njobs + jobs > PACK_MAXJ) return dppo_set_error(DPPO_EINVAL, "pack: too many images in one launch");
     auto mat = [&](size_t src, int K, int N, bool tr, int seg) {
@@ -703,7 +702,7 @@ int dppo_pack_models(const Dims& D, int precision, const float* actor_params, vo
         rc = add_mlp_jobs(a, D.IN, D.H, D.XD, D.TD, precision, actor_params, packed_actor, D.K, D.TS,
                           defer ? PACK_UPDATE : PACK_ALL);
         if (rc) return rc;
-        if (defer) rc = mark_stale(D, precision, actor_params, packed_actor, !DPPO_PACK_UPDATE_TEMB);
+        if (defer) rc = mark_stale(D, precision, actor_params, packed_actor, true);
         else clear_stale(packed_actor);   // a full pack makes a pending refresh moot
         if (rc) return rc;
     }

@@ -17,10 +17,9 @@
 #include "rowtile_common.cuh"
 
 
-// weight-stream queue depth of the actor row tile (k-steps in flight per wave; tuning knob)
-#ifndef DPPO_ROWTILE_QD
-#define DPPO_ROWTILE_QD 3
-#endif
+// weight-stream queue depth of the actor row tile: k-steps in flight per wave (2 and 4 measured
+// within noise of 3; profiles/r06n_rowtile_qd_ab.txt)
+constexpr int ROWTILE_QD = 3;
 
 // Phase timing for tuning builds (tools/variant_build.sh ... -DDPPO_ROWTILE_TIMING): wave 0 of
 // every workgroup adds the shader-clock cycles it spent in each phase (barrier waits included).
@@ -131,7 +130,7 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
     const int ntile0 = wave * NT;
     const __amdgpu_buffer_rsrc_t rs = packed_rsrc(a.packed);
     auto W = [&](int seg) { return wsrc(rs, L.off[seg]); };
-    constexpr int QD = DPPO_ROWTILE_QD;   // weight k-steps in flight per wave
+    constexpr int QD = ROWTILE_QD;   // weight k-steps in flight per wave
     WQueue<QD, NT> R;
     // the stream after L1: l1 (L2), then (train) the backward's W_out^T, M^T and l1^T
     const NextLayers after_l1 = train ? NextLayers{W(SEG_W_L1), KSH, W(SEG_T_OUT), KSO}
@@ -896,13 +895,13 @@ static int dispatch_critic(const CriticArgs& a, hipStream_t s) {
     return dppo_set_error(DPPO_EUNSUPPORTED, "critic: hidden %d not instantiated", a.HC);
 }
 
-#ifndef DPPO_CRITIC_MT
-#define DPPO_CRITIC_MT 2   // 16-row MFMA tiles per critic row tile (measurement knob of tuning builds)
-#endif
+// 16-row MFMA tiles per critic row tile: 2 (4, a 64-row tile, measured slower at N = 1 and equal on
+// the emulated 8-rank line; profiles/r04t_critic_tile64_ab.txt, profiles/r06n_rowtile_qd_ab.txt)
+constexpr int CRITIC_MT = 2;
 int launch_critic_rowtile(const CriticArgs& a, int precision, hipStream_t s) {
-    return precision == DPPO_BF16 ? dispatch_critic<PolicyBF16, DPPO_CRITIC_MT, 8, true>(a, s)
-         : precision == DPPO_F16  ? dispatch_critic<PolicyF16, DPPO_CRITIC_MT, 8, true>(a, s)
-                                  : dispatch_critic<PolicyF32, 2, 8, true>(a, s);
+    return precision == DPPO_BF16 ? dispatch_critic<PolicyBF16, CRITIC_MT, 8, true>(a, s)
+         : precision == DPPO_F16  ? dispatch_critic<PolicyF16, CRITIC_MT, 8, true>(a, s)
+                                  : dispatch_critic<PolicyF32, CRITIC_MT, 8, true>(a, s);
 }
 
 // =============================================================================================

@@ -82,29 +82,14 @@ extern "C" DPPO_API int dppo_debug_split_cycles(unsigned long long* out, int res
 #define XSTEP(i) do {} while (0)
 #endif
 
-// Host hand-off of a pipelined step (DPPO_SPLIT_SIGNAL, tuning knob):
-//   0: acquire poll of go per iteration; plain output stores; __threadfence_system() + release add
-//   1: relaxed poll of go + one system acquire after it matches
-//   2: 1 + the launch's device outputs stored write-through (sc1), so the final system release
-//      has no dirty L2 lines to write back
-#ifndef DPPO_SPLIT_SIGNAL
-#define DPPO_SPLIT_SIGNAL 2
-#endif
-
-// timing probes (tools/variant_build.sh ... -DDPPO_PROBE_NOSYNC=k, results wrong): drop barrier k of a
-// folded-kernel step (1 in-Dense, 2 partial sums, 3 step end)
-#ifndef DPPO_PROBE_NOSYNC
-#define DPPO_PROBE_NOSYNC 0
-#endif
+// Host hand-off of a pipelined step: a relaxed poll of go and one system acquire after it matches;
+// the launch's device outputs are stored write-through (sc1, store_out), so the final system release
+// has no dirty L2 lines to write back.
 namespace {
 
-// a store of a kernel output that leaves no dirty line in L2 (write-through; see DPPO_SPLIT_SIGNAL)
+// a store of a kernel output that leaves no dirty line in L2 (write-through; see the hand-off above)
 __device__ inline void store_out(float* p, float v) {
-#if DPPO_SPLIT_SIGNAL >= 2
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    *p = v;
-#endif
 }
 
 constexpr int SPLIT_P = 8;         // the most members per 16-env group (fp32); the exchange regions' stride
@@ -139,23 +124,9 @@ __device__ inline int xcc_id() {
 
 
 
-// tuning knobs of the split kernel (tools/variant_build.sh <tag> "-D..." + tools/ab_variants.sh)
-#ifndef DPPO_S4_L1D
-#define DPPO_S4_L1D 1        // l1: u1 fragment reads kept in flight ahead of the MFMA chain (r06, same box,
-                             // 300 launches x 2: 1 46.8 / 4 47.8 / 2 47.1-47.5 / 3 47.7-47.9 / 6 47.5 / 0
-                             // 58.0 us at hopper bf16; fp32 neutral; profiles/r06l_sampler_l1d_ab.txt)
-#endif
-#ifndef DPPO_S4_INREADY
-#define DPPO_S4_INREADY 0    // 1: the in-Dense's LDS operands forced into one round trip (the r02-r05 form); r06 with
-                             // l1 read-ahead 1: left to the compiler measured 46.0-46.3 vs 46.8-47.0 us at hopper
-                             // bf16, -1.4 % at DDIM 512 fp16, -0.5 % walker2d 256, fp32 neutral (r06m A/B)
-#endif
-#ifndef DPPO_S4_PUBREADY
-#define DPPO_S4_PUBREADY 1   // publish: the 8 wave partials in one round trip
-#endif
-#ifndef DPPO_S4_EPIEARLY
-#define DPPO_S4_EPIEARLY 1   // epilogue inputs read at the step start (else after the publish)
-#endif
+// l1: u1 fragment reads kept in flight ahead of the MFMA chain (1 measured 46.8 us at hopper bf16
+// against 47.1-47.9 for 2, 3, 4, 6 and 58.0 for 0; fp32 neutral; profiles/r06l_sampler_l1d_ab.txt)
+constexpr int S4_L1D = 1;
 
 // relu as one v_max_i32 on the bits (fmaxf(x, 0) canonicalises its MFMA-produced input first: two
 // VALU ops per element); negative values and -0 map to +0, as fmaxf(x, 0) does up to the sign of 0
@@ -170,7 +141,7 @@ __device__ inline float dpp_f32(float v) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// P = 2 (2-byte operands) or 4 (fp32, or -DDPPO_S4_P=4) members per 16-env group. Fewer members mean a
+// P = 2 (2-byte operands) or 8 (fp32) members per 16-env group. Fewer members mean a
 // cheaper exchange (tools/xchg_probe2.hip, sc0 one-XCD granules at 16 envs: P = 2 0.59 us per step, 4
 // 0.98, 8 1.55) and less arrival skew, for more l1 MFMAs per wave. Member c
 // keeps 1/P of l1 in registers (P = 2: 128 of 228 VGPRs), written below for P = 4:
@@ -187,7 +158,7 @@ __device__ inline float dpp_f32(float v) {
 //              in-Dense tiles w*NTI + r*P + c (h1 hi/lo against SEG_ROUT). No l2 GEMM, no l2
 //              weights resident, no LDS round trip or barrier between l1 and the exchange.
 // so no wave adds a bias or a residual outside an MFMA, and no wave re-sums l1 partials.
-// PM = members per group: 2 (the default, DPPO_S4_P: 1/2 of l1 per member, 2 l1 n-tiles per wave,
+// PM = members per group: 2 (the 2-byte default, S4_P: 1/2 of l1 per member, 2 l1 n-tiles per wave,
 // a 2-member exchange; possible once l2 is folded away), 4, or 8 (fp32 with SWV = 4: one wave per
 // SIMD, one l1 n-tile each; the member sum adds a third DPP level)
 template <class Pol, int XQ, int KX, bool INJ, int SWV, int PM = 4>
@@ -523,19 +494,12 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
             for (int n = 0; n < NTI; ++n) h1[n] = *(const f32x4*)(tin + (TRING ? (i & 1) : t) * H + 16 * (NTI * wave + n) + 4 * jq);
 #pragma unroll
             for (int n = 0; n < NTI; ++n) wf[0][n] = wxs[((wave * NTI + n) * KX + 0) * 64 + lane];
-            // one LDS round trip for all of them (2-byte KX = 2: the second k-step's operands in a second
-            // round trip after the first k-step's MFMAs, which keeps the walker2d form within 256 VGPRs
-            // — all at once it spilled the epilogue's output addresses to scratch)
-#if DPPO_S4_INREADY
-            asm volatile("" ::"v"(af[0]), "v"(h1[0]), "v"(h1[1]), "v"(h1[2]), "v"(h1[3]), "v"(wf[0][0]), "v"(wf[0][1]),
-                         "v"(wf[0][2]), "v"(wf[0][3]));
-            if constexpr (NTI == 8)
-                asm volatile("" ::"v"(h1[NTI - 4]), "v"(h1[NTI - 3]), "v"(h1[NTI - 2]), "v"(h1[NTI - 1]), "v"(wf[0][NTI - 4]),
-                             "v"(wf[0][NTI - 3]), "v"(wf[0][NTI - 2]), "v"(wf[0][NTI - 1]));
-#endif
-#if DPPO_S4_EPIEARLY
+            // the in-Dense's LDS operands are left to the compiler's schedule (forced into one round trip,
+            // the r02-r05 form, measured 46.8-47.0 against 46.0-46.3 us at hopper bf16 with l1 read-ahead 1:
+            // profiles/r06m_sampler_knobs_ab.txt); the epilogue inputs are read here, at the step start
+            // (2-byte KX = 2: the second k-step's operands are read after the first k-step's MFMAs, which
+            // keeps the walker2d form within 256 VGPRs)
             asm volatile("" ::"v"(ec), "v"(esd), "v"(xe), "v"(ze), "v"(be));
-#endif
             if constexpr (SBP)
 #pragma unroll
                 for (int n = 0; n < NTI; ++n) h1[n] += sb[n];
@@ -544,11 +508,6 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
             if constexpr (KXS == 2) {
 #pragma unroll
                 for (int n = 0; n < NTI; ++n) wf[1][n] = wxs[((wave * NTI + n) * KX + 1) * 64 + lane];
-#if DPPO_S4_INREADY
-                asm volatile("" ::"v"(af[1]), "v"(wf[1][0]), "v"(wf[1][1]), "v"(wf[1][2]), "v"(wf[1][3]));
-                if constexpr (NTI == 8)
-                    asm volatile("" ::"v"(wf[1][NTI - 4]), "v"(wf[1][NTI - 3]), "v"(wf[1][NTI - 2]), "v"(wf[1][NTI - 1]));
-#endif
 #pragma unroll
                 for (int n = 0; n < NTI; ++n) h1[n] = Pol::mma(wf[1][n], af[1], h1[n]);
             }
@@ -592,9 +551,7 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
             for (int n = 0; n < NO; ++n) po[n] = Pol::mma(rres[r][n], bh, po[n]);
         }
         XPHASE(11);
-#if DPPO_PROBE_NOSYNC != 1   // timing probe only (wrong actions): drop the in-Dense barrier
         lds_sync();
-#endif
         XPHASE(2);
         // ---- l1 (transposed): n-tile `wave` of this member's output columns over all 512 inputs,
         //      from b_l1; a = relu(h2) feeds the folded l2 + out-Dense (mlp.py:202-206)
@@ -611,7 +568,7 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
                 for (int tt = 0; tt < NL1; ++tt) acc[tt] = Pol::mma(rl1[tt][j], fb[j], acc[tt]);
             // schedule: the bias and L1D fragment reads first, then one read per MFMA, so L1D reads
             // stay in flight ahead of the chain (left alone, hipcc issued read -> wait -> MFMA)
-            constexpr int L1D = DPPO_S4_L1D, MPC = TWO ? 1 : 4;   // hardware MFMAs per Pol::mma
+            constexpr int L1D = S4_L1D, MPC = TWO ? 1 : 4;   // hardware MFMAs per Pol::mma
             __builtin_amdgcn_sched_group_barrier(0x100, L1D + NL1, 0);
 #pragma unroll
             for (int j = 0; j < KSH - L1D; ++j) {
@@ -643,9 +600,7 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
                 if (16 * n + 4 * jq < XD) *(f32x4*)(part + wave * NV + env * XD + 16 * n + 4 * jq) = po[n];
         }
         XPHASE(14);
-#if DPPO_PROBE_NOSYNC != 2   // timing probe only (wrong actions): drop the partial-sum barrier
         lds_sync();
-#endif
         XPHASE(4);
         // ---- exchange + DDPM epilogue (as the P = 8 kernel; lane = P * slot + member, the member
         //      sum is log2 P DPP levels inside the quad)
@@ -657,10 +612,9 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
                 float pp[SW];
 #pragma unroll
                 for (int w = 0; w < SW; ++w) pp[w] = part[w * NV + vw + lane];
-#if DPPO_S4_PUBREADY
+                // the wave partials in one round trip
                 asm volatile("" ::"v"(pp[0]), "v"(pp[1]), "v"(pp[2]), "v"(pp[3]));
                 if constexpr (SW == 8) asm volatile("" ::"v"(pp[SW - 4]), "v"(pp[SW - 3]), "v"(pp[SW - 2]), "v"(pp[SW - 1]));
-#endif
                 float sum = pp[0];
 #pragma unroll
                 for (int w = 1; w < SW; ++w) sum += pp[w];
@@ -687,9 +641,6 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
                 bool ok = true;
 #pragma unroll
                 for (int k = 0; k < KW; ++k) ok &= (uint32_t)(xa[k] >> 32) == tag;
-#ifdef DPPO_SPLIT_NOXCHG
-                ok = true;   // timing probe only: one sweep, no wait for the peers (wrong actions)
-#endif
                 if (__all(ok)) break;
                 if (__builtin_amdgcn_s_memrealtime() > t_end) {
                     failed = true;
@@ -740,9 +691,7 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
                 }
             }
         }
-#if DPPO_PROBE_NOSYNC != 3   // timing probe only (wrong actions): drop the step-end barrier
         lds_sync();
-#endif
         XPHASE(6);
     }
     XPHASE(9);
@@ -911,25 +860,18 @@ int device_cus() {
     return g_cus;
 }
 
-// waves per member of the P = 4 kernel. The kernel also builds with 4 (one wave per SIMD, 512
-// registers: the l1 / l2 fragments partly in AGPRs, each wave two l1 n-tiles and eight in-Dense /
-// l2 n-tiles): measured 63.7 vs 59.3 us per launch at 8 (no second wave to hide its latencies), so
-// 8 is the default (-DDPPO_S4_WAVES=4 builds the one-wave-per-SIMD form as an A/B variant)
-#ifndef DPPO_S4_WAVES
-#define DPPO_S4_WAVES 8
-#endif
-constexpr int SPLIT4_WAVES = DPPO_S4_WAVES;
-int split_waves() { return SPLIT4_WAVES; }
+// waves per member of the 2-byte kernel: 8, two per SIMD (4, one wave per SIMD with 512 registers,
+// measured 63.7 vs 59.3 us per launch: no second wave to hide its latencies;
+// profiles/r05d_sampler_xreg_w4_ab.txt)
+constexpr int S4_WAVES = 8;
 
 template <class Pol, int XQ, int KX, bool INJ, int SWV, int PM>
 int launch_split4_kw(const SplitArgs& sa, hipStream_t s) {
     constexpr int NO = (4 * XQ + 15) / 16;
     // the finishing lanes are the members' lanes: a wave's 16 x XD / SWV coordinates in (64 / PM)
-    // slots at most PM deep (the one-wave-per-SIMD form covers XD <= 16 at PM = 2)
+    // slots at most PM deep
     constexpr int NVW = 16 * 4 * XQ / SWV, KW = (NVW + 64 / PM - 1) / (64 / PM);
-    if constexpr (KW > PM) {
-        return dppo_set_error(DPPO_EUNSUPPORTED, "split sampler: %d waves per member do not cover XD = %d", SWV, 4 * XQ);
-    } else {
+    static_assert(KW <= PM, "the waves of a member do not cover XD");
     auto k = sample_split4_kernel<Pol, XQ, KX, INJ, SWV, PM>;
     const SampleArgs& a = sa.a;
     const size_t lds = split4_lds_bytes(a.XD, a.SD, a.K, KX, NO, SWV, (int)sizeof(typename Pol::AT));
@@ -940,25 +882,18 @@ int launch_split4_kw(const SplitArgs& sa, hipStream_t s) {
     hipLaunchKernelGGL(k, dim3(blocks), dim3(SWV * 64), lds, s, sa);
     DPPO_HIP(hipGetLastError());
     return DPPO_OK;
-    }
 }
 
-// members per group of the folded kernel: 2 (default: 47.2 us per bench launch), or 4 with
-// -DDPPO_S4_P=4 (50.4 us; same box, tools/ab_variants.sh) — a build-time A/B knob
-#ifndef DPPO_S4_P
-#define DPPO_S4_P 2
-#endif
-constexpr int S4P = DPPO_S4_P;
+// members per group of the 2-byte kernel: 2 (47.2 us per bench launch against 50.4 at 4;
+// profiles/r06m_sampler_knobs_ab.txt)
+constexpr int S4_P = 2;
 // fp32: P = 8 members of 4 waves (one per SIMD: the 16x16x4 MFMA's 32-cycle issue is the step's bound,
-// so halving each SIMD's l1 share pays for the 8-member exchange), or P = 4 of 8 waves (-DDPPO_F32_P=4)
-#ifndef DPPO_F32_P
-#define DPPO_F32_P 8
-#endif
-constexpr int F32P = DPPO_F32_P, F32W = F32P == 8 ? 4 : 8;
+// so halving each SIMD's l1 share pays for the 8-member exchange; P = 4 of 8 waves was the alternative)
+constexpr int F32_P = 8, F32_WAVES = 4;
 
 template <class Pol, int XQ, int KX, bool INJ>
 int launch_split4_k(const SplitArgs& sa, hipStream_t s) {
-    return launch_split4_kw<Pol, XQ, KX, INJ, SPLIT4_WAVES, S4P>(sa, s);
+    return launch_split4_kw<Pol, XQ, KX, INJ, S4_WAVES, S4_P>(sa, s);
 }
 
 // the split sampler's plan for a shape: P members per 16-env group (2 for 2-byte operands, 4 for fp32;
@@ -968,8 +903,8 @@ int launch_split4_k(const SplitArgs& sa, hipStream_t s) {
 struct SplitPlan { int P; bool dual; int blocks; };
 
 SplitPlan split_plan(int precision, int H, int XD, int SD, int E, int K, int KF) {
-    // fp32 (r06): the folded kernel at P = F32P members (an fp32 l1 eighth on 4 waves, or a quarter on 8, is
-    // 128 VGPRs of fragments per lane), for the instantiated width XD = 12 (hopper; other fp32 shapes stream
+    // fp32 (r06): the folded kernel at P = F32_P members (an fp32 l1 eighth on 4 waves is 128 VGPRs of
+    // fragments per lane), for the instantiated width XD = 12 (hopper; other fp32 shapes stream
     // the weights, sampler.hip)
     const bool f32 = precision == DPPO_F32;
     if ((!dppo_prec_2b(precision) && !(f32 && XD == 12)) || H != SPLIT_H || XD % 4 != 0 || XD > 32 || K > 62)
@@ -977,10 +912,10 @@ SplitPlan split_plan(int precision, int H, int XD, int SD, int E, int K, int KF)
     const int G = dppo_cdiv(E, 16);
     if (G < 1 || G > XMAX_G) return {0, false, 0};
     const int cus = device_cus();
-    const int P = f32 ? F32P : S4P;   // members per group
+    const int P = f32 ? F32_P : S4_P;   // members per group
     const int KX = dppo_cdiv(XD + SD, f32 ? 16 : 32);
     // every workgroup of the launch co-resident (one per CU: the register budget)
-    if (KX > 2 || split4_lds_bytes(XD, SD, K, KX, dppo_cdiv(XD, 16), f32 ? F32W : split_waves(), f32 ? 4 : 2) > 160 * 1024 ||
+    if (KX > 2 || split4_lds_bytes(XD, SD, K, KX, dppo_cdiv(XD, 16), f32 ? F32_WAVES : S4_WAVES, f32 ? 4 : 2) > 160 * 1024 ||
         (cus && 8 * P * ((G + 7) / 8) > cus))
         return {0, false, 0};
     // two member sets (one per actor) only while two launches of them still fit side by side (the
@@ -1027,12 +962,12 @@ int launch_sample_split(const SampleArgs& a, int precision, hipStream_t s) {
     const bool inj = a.noise != nullptr;
     const bool f16 = precision == DPPO_F16;
     if (precision == DPPO_F32) {   // split_plan took XD = 12 only
-        if (a.XD != 12 || P != F32P) return DPPO_EUNSUPPORTED;
+        if (a.XD != 12 || P != F32_P) return DPPO_EUNSUPPORTED;
         if (a.XD + a.SD > 16)
-            return inj ? launch_split4_kw<PolicyF32, 3, 2, true, F32W, F32P>(sa, s)
-                       : launch_split4_kw<PolicyF32, 3, 2, false, F32W, F32P>(sa, s);
-        return inj ? launch_split4_kw<PolicyF32, 3, 1, true, F32W, F32P>(sa, s)
-                   : launch_split4_kw<PolicyF32, 3, 1, false, F32W, F32P>(sa, s);
+            return inj ? launch_split4_kw<PolicyF32, 3, 2, true, F32_WAVES, F32_P>(sa, s)
+                       : launch_split4_kw<PolicyF32, 3, 2, false, F32_WAVES, F32_P>(sa, s);
+        return inj ? launch_split4_kw<PolicyF32, 3, 1, true, F32_WAVES, F32_P>(sa, s)
+                   : launch_split4_kw<PolicyF32, 3, 1, false, F32_WAVES, F32_P>(sa, s);
     }
     const bool kx2 = a.XD + a.SD > 32;
     switch (a.XD / 4) {

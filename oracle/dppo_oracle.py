@@ -256,7 +256,7 @@ def residual_mlp_backward(p, cache, dy, act, prefix):
     dh3 = dyr @ wo.T
     dh3r = Rg(dh3)
     # l2's weight gradient through the linear out layer (the kernels form no dh3 image for it,
-    # csrc/update.hip l2_back_rows): u2^T (dy W_out^T) = (u2^T dy) W_out^T, unrounded dh3
+    # csrc/backward_tail.hip l2_back_cols): u2^T (dy W_out^T) = (u2^T dy) W_out^T, unrounded dh3
     g[prefix + "l2_w"] = (cache["u2"].T @ dyr) @ wo.T
     g[prefix + "l2_b"] = g[prefix + "out_b"] @ wo.T
     if cache.get("fold"):   # the folded row tile: dy (R(W_l2) R(W_out))^T, dh3 unrounded on this path

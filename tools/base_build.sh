@@ -11,7 +11,7 @@ cd "$src/diffusionpolicyoptimization_amd/csrc"
 out="$root/diffusionpolicyoptimization_amd/lib/variants/libdppo_hip_$tag.so"
 mkdir -p "$(dirname "$out")" obj
 objs=""
-for f in api pack sampler sampler_split scan rowtile update; do
+for f in $(sed -n 's/^SRCS := //p' Makefile | sed 's/\.hip//g'); do   # the revision's own source list
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -mcode-object-version=5 -fvisibility=hidden \
         -I../../include -mllvm -amdgpu-mfma-vgpr-form $extra -c $f.hip -o obj/$f.o &
     objs="$objs obj/$f.o"

@@ -144,9 +144,16 @@ __device__ inline float dpp_f32(float v) {
 // P = 2 (2-byte operands) or 8 (fp32) members per 16-env group. Fewer members mean a
 // cheaper exchange (tools/xchg_probe2.hip, sc0 one-XCD granules at 16 envs: P = 2 0.59 us per step, 4
 // 0.98, 8 1.55) and less arrival skew, for more l1 MFMAs per wave. Member c
-// keeps 1/P of l1 in registers (P = 2: 128 of 228 VGPRs), written below for P = 4:
+// keeps 1/P of l1 in registers (P = 2: 128 of hopper's 236 VGPRs), written below for P = 4:
 //   in-Dense   W_in rows [x ; state] only (K = XD + SD <= 32 KX); the time part b_in + W_in^T
-//              t_emb(t) is the pack step's TIN table (dppo_layout.h), the MFMA accumulator's start
+//              t_emb(t) is the pack step's TIN table (dppo_layout.h), the MFMA accumulator's start.
+//              The 2-byte one-k-step form (hopper) holds the wave's 4 fragments in 16 VGPRs for the
+//              launch (RIN: copied from the wave's LDS image once per actor); KX = 2 and fp32 read
+//              them from LDS every step (16 / 32 more VGPRs do not fit beside their second k-step)
+//   step head  nothing a step's epilogue reads besides eps depends on that step: schedule row, noise
+//              and out bias of step i + 1 (and its TIN start where all K rows are in LDS) are read in
+//              step i behind the publish store, under the exchange wait; x of a finishing lane's
+//              coordinate is the y it stored itself and stays in a register
 //   l1         output columns [128c, 128c+128): wave w owns n-tile w over ALL 512 inputs, so its
 //              result is final (b_l1 is the accumulator's start): a = relu(h2), rounded as the
 //              reference's l2 input
@@ -242,10 +249,16 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
     };
 
     // ---- resident weight fragments (one actor at a time): l1 and the folded out-Dense in
-    //      registers; the in-Dense fragments in this wave's own LDS ----
+    //      registers; the in-Dense fragments in this wave's own LDS (RIN: and from there in registers) ----
     const __amdgpu_buffer_rsrc_t rs_base = packed_rsrc(a.packed_base), rs_ft = packed_rsrc(a.packed_ft);
     auto W = [&](int ft, int seg) { return wsrc(ft ? rs_ft : rs_base, L.off[seg]); };
     u32x4 rl1[NL1][KSH], rfold[NL1][NO], rres[NR][NO];
+    // RIN: the 2-byte one-k-step form (hopper) also keeps the current actor's NTI in-Dense fragments in
+    // registers (16 VGPRs), copied once from this wave's LDS image after the DMA has landed: in the
+    // prologue and after a non-dual actor switch. (KX = 2 spills with 16 more VGPRs; fp32's NTI = 8
+    // fragments are 32.)
+    constexpr bool RIN = TWO && KX == 1;
+    u32x4 rin[RIN ? NTI : 1];
     // LDS-DMA of one 1 KiB fragment (lane l's 16 B land at dst + 16 l); wave-private destinations,
     // consumed only after this wave's vmcnt(0)
     auto dma_frag = [&](int ft, int seg, int KS, int ntile, int ks, u32x4* dst) {
@@ -257,6 +270,12 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
         for (int ks = 0; ks < KX; ++ks)
 #pragma unroll
             for (int n = 0; n < NTI; ++n) dma_frag(ft, SEG_W_XS, KSX, NTI * wave + n, ks, wxs + ((wave * NTI + n) * KX + ks) * 64);
+    };
+    // RIN: this wave's landed in-Dense fragments, LDS -> registers (after the vmcnt(0) that covers load_in)
+    auto take_in = [&]() {
+        if constexpr (RIN)
+#pragma unroll
+            for (int n = 0; n < NTI; ++n) rin[n] = wxs[(wave * NTI + n) * KX * 64 + lane];
     };
     auto load_l1 = [&](int ft) {
 #pragma unroll
@@ -371,6 +390,7 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
 #endif
     }
     __syncthreads();
+    take_in();
     // a0 = [x | state | 0]: everything but the state columns before the observation wait
     constexpr int k1w = KX * KGP;
     for (int idx = tid; idx < 16 * k1w; idx += ST) {
@@ -465,6 +485,43 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
     const int xm = lane & (P - 1), xsl = lane / P;
     const bool fin = xm < KW && xsl + SL * xm < NVW;
     const int ve = wave * NVW + (fin ? xsl + SL * xm : 0), re = ve / XD, qe = ve % XD;
+    // The step head is software-pipelined: what a step's epilogue reads besides the exchanged eps
+    // (schedule row, noise, out bias) and, where every TIN row is in LDS (!TRING), the in-Dense
+    // accumulator's start depend on nothing the step computes, so step i + 1's are read in step i
+    // behind the publish store, under the exchange wait; x of this lane's coordinate is the y the lane
+    // itself stored in the step before (fin, ve are launch-constant) and stays in a register.
+    constexpr bool TPF = !TRING;            // the accumulator start is prefetched too
+    struct Head {
+        f32x4 ec;                           // c0 c1 c2 c3
+        float esd, ze, be;
+        f32x4 h1s[TPF ? NTI : 1];           // TPF: TIN[t] of this wave's in-Dense tiles
+    };
+    auto read_head = [&](int ii) {          // ii in [i0, i1)
+        const int tt = K - 1 - ii;
+        const float* bh = bias + (sa.dual ? ft0 : (tt < KF ? 1 : 0)) * NB;
+        Head h;
+        h.ec = *(const f32x4*)(sch + ii * DPPO_SCHED_COLS);
+        h.esd = sch[ii * DPPO_SCHED_COLS + 4];
+        h.ze = zt[ii * 16 * XD + ve];
+        h.be = bh[H + qe];
+        if constexpr (TPF)
+#pragma unroll
+            for (int n = 0; n < NTI; ++n) h.h1s[n] = *(const f32x4*)(tin + tt * H + 16 * (NTI * wave + n) + 4 * jq);
+        return h;
+    };
+    // the reads of a head issue together, ahead of whatever follows the pin
+    auto pin_head = [&](const Head& h) {
+        asm volatile("" ::"v"(h.ec), "v"(h.esd), "v"(h.ze), "v"(h.be));
+        if constexpr (TPF)
+#pragma unroll
+            for (int n = 0; n < NTI; ++n) asm volatile("" ::"v"(h.h1s[n]));
+    };
+    Head hd = {};
+    float xe = 0.f;
+    if (i0 < i1) {
+        hd = read_head(i0);
+        xe = xs[ve];                        // x_T, or the base set's x (dual hand-off above)
+    }
     XPHASE(0);
     for (int i = i0; i < i1; ++i) {
         XSTEP(i);
@@ -476,13 +533,12 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
             __builtin_amdgcn_s_waitcnt(0x0F70);   // the other actor's fragments (load_in / load_l1 / load_fold)
             cur = PK;
             state_part();
+            take_in();
         }
         XPHASE(1);
         const float* bb = bias + PK * NB;
-        // this step's epilogue inputs, read with the in-Dense operands (none depends on this step)
-        const f32x4 ec = *(const f32x4*)(sch + i * DPPO_SCHED_COLS);      // c0 c1 c2 c3
-        const float esd = sch[i * DPPO_SCHED_COLS + 4];
-        const float xe = xs[ve], ze = zt[i * 16 * XD + ve], be = bb[H + qe];
+        const f32x4 ec = hd.ec;
+        const float esd = hd.esd, ze = hd.ze, be = hd.be;
         // ---- in-Dense (transposed): h1 = TIN[t] + W_xs^T [x; state]; no activation (mlp.py:144)
         f32x4 h1[NTI];
         {
@@ -491,15 +547,20 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
 #pragma unroll
             for (int ks = 0; ks < KXS; ++ks) af[ks] = lds_afrag<Pol>(a0, lda0, 0, ks, lane);
 #pragma unroll
-            for (int n = 0; n < NTI; ++n) h1[n] = *(const f32x4*)(tin + (TRING ? (i & 1) : t) * H + 16 * (NTI * wave + n) + 4 * jq);
+            for (int n = 0; n < NTI; ++n) {
+                if constexpr (TPF) h1[n] = hd.h1s[n];
+                else h1[n] = *(const f32x4*)(tin + (TRING ? (i & 1) : t) * H + 16 * (NTI * wave + n) + 4 * jq);
+            }
 #pragma unroll
-            for (int n = 0; n < NTI; ++n) wf[0][n] = wxs[((wave * NTI + n) * KX + 0) * 64 + lane];
+            for (int n = 0; n < NTI; ++n) {
+                if constexpr (RIN) wf[0][n] = rin[n];
+                else wf[0][n] = wxs[((wave * NTI + n) * KX + 0) * 64 + lane];
+            }
             // the in-Dense's LDS operands are left to the compiler's schedule (forced into one round trip,
             // the r02-r05 form, measured 46.8-47.0 against 46.0-46.3 us at hopper bf16 with l1 read-ahead 1:
-            // profiles/r06m_sampler_knobs_ab.txt); the epilogue inputs are read here, at the step start
+            // profiles/r06m_sampler_knobs_ab.txt)
             // (2-byte KX = 2: the second k-step's operands are read after the first k-step's MFMAs, which
             // keeps the walker2d form within 256 VGPRs)
-            asm volatile("" ::"v"(ec), "v"(esd), "v"(xe), "v"(ze), "v"(be));
             if constexpr (SBP)
 #pragma unroll
                 for (int n = 0; n < NTI; ++n) h1[n] += sb[n];
@@ -625,6 +686,8 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
                     __hip_atomic_store(xb + (size_t)c * NV + vw + lane, gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             XPHASE(15);
+            // the next step's head (the last step re-reads its own: a valid slot, unused)
+            const Head hn = read_head(i + 1 < i1 ? i + 1 : i);
             const float c0 = ec[0], c1 = ec[1], c2 = ec[2], c3 = ec[3], sd = esd;
             const int m = xm, sl = xsl;
             const uint64_t* src = xb + (size_t)m * NV + vw;
@@ -638,6 +701,7 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
                     const int v = sl + SL * k < NVW ? sl + SL * k : NVW - 1;   // clamped lanes re-read a valid granule
                     xa[k] = __hip_atomic_load(src + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
+                pin_head(hn);   // behind the sweep's first loads: the head's LDS reads delay no poll
                 bool ok = true;
 #pragma unroll
                 for (int k = 0; k < KW; ++k) ok &= (uint32_t)(xa[k] >> 32) == tag;
@@ -676,6 +740,7 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
                 float y = ddpm_post(c0, c1, c2, c3, sd, x, ep, ze);   // (:198-242, :301-320)
                 if (a.final_clip > 0.f && i == K - 1) y = fminf(fmaxf(y, -a.final_clip), a.final_clip);
                 if (failed) y = __builtin_nanf("");
+                xe = y;
                 xs[v] = y;
                 a0[r * lda0 + q] = Pol::cvt(y);
                 if (c == 0 && row < a.E) {
@@ -690,6 +755,7 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
                     }
                 }
             }
+            hd = hn;
         }
         lds_sync();
         XPHASE(6);

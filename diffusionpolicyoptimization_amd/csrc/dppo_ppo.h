@@ -134,5 +134,9 @@ struct CriticArgs {
     const int* crow_cnt;
 };
 
+// the actor row tile of a launch over `rows` rows (the 64-padded image rows in the TRAIN modes):
+// mt 16-row MFMA tiles per row tile (2 = 32 rows, 4 = 64 rows) on `waves` waves
+struct ActorTilePlan { int mt, waves; };
+ActorTilePlan actor_tile_plan(int precision, int H, int XD, int64_t rows);
 int launch_actor_rowtile(const ActorArgs& a, int precision, hipStream_t s);
 int launch_critic_rowtile(const CriticArgs& a, int precision, hipStream_t s);

@@ -21,6 +21,11 @@ enum class DWTile { ACTOR, CRITIC };
 // seed scale); rows_dev, when non-null, is a device-side row count that caps the rows summed.
 int launch_dw(DWTile tile, int precision, const DWItem* items, int n_items, const PpoWorkspace& ws, float out_scale,
               const int* rows_dev, int min_chunk_rows, hipStream_t s);
+// The m-chunks launch_dw cuts the ldm rows into for these items (host arithmetic only: launch_dw and the
+// plan query, dppo_ppo_plan, both take them from here): output tiles over all items, chunks, rows per
+// chunk (a multiple of 64; the last chunk is shorter when nchunks * mchunk > ldm)
+struct DWPlan { int tiles, nchunks, mchunk; };
+DWPlan dw_plan(DWTile tile, const DWItem* items, int n_items, size_t ldm, int min_chunk_rows);
 
 // ---- backward_tail.hip: what follows the dW launches -------------------------------------------
 // after the actor's dW: the time-MLP backward over nb buckets at t = q * TS (the bucket sums in

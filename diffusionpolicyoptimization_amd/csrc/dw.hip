@@ -286,6 +286,24 @@ static int launch_dw_p(const DWArgs& a, DWTile tile, hipStream_t s) {
     return DPPO_OK;
 }
 
+static int dw_item_tiles(DWTile tile, const DWItem& it) {
+    return dppo_cdiv(it.Kx, tile == DWTile::ACTOR ? 256 : 128) * dppo_cdiv(it.N, DW_TN);
+}
+
+DWPlan dw_plan(DWTile tile, const DWItem* items, int n_items, size_t ldm, int min_chunk_rows) {
+    DWPlan p = {};
+    for (int i = 0; i < n_items; ++i) p.tiles += dw_item_tiles(tile, items[i]);
+    // m-chunks: about one workgroup per CU (the ring takes most of its LDS) in a single round, but no
+    // chunk under min_chunk_rows rows (a multiple of 64)
+    const int span = (int)ldm;
+    int nch = dw_device_cus() / p.tiles;
+    if (nch > span / min_chunk_rows) nch = span / min_chunk_rows;
+    if (nch < 1) nch = 1;
+    p.mchunk = dppo_cdiv(span, nch * 64) * 64;
+    p.nchunks = dppo_cdiv(span, p.mchunk);
+    return p;
+}
+
 int launch_dw(DWTile tile, int precision, const DWItem* items, int n_items, const PpoWorkspace& ws, float out_scale,
               const int* rows_dev, int min_chunk_rows, hipStream_t s) {
     DPPO_CHECK(n_items >= 1 && n_items <= DW_MAXP, "dW: %d problems in one launch", n_items);
@@ -296,21 +314,16 @@ int launch_dw(DWTile tile, int precision, const DWItem* items, int n_items, cons
         DWProb& p = w.p[i];
         p.XT = it.XT; p.DT = it.DT; p.G = it.G; p.Gx = it.Gx; p.Kx = it.Kx; p.N = it.N; p.extra = it.extra;
         p.ktiles = dppo_cdiv(it.Kx, tk); p.ntiles = dppo_cdiv(it.N, DW_TN);
-        w.tile_start[i + 1] = w.tile_start[i] + p.ktiles * p.ntiles;
+        w.tile_start[i + 1] = w.tile_start[i] + dw_item_tiles(tile, it);
     }
     w.nprob = n_items;
     w.rows_dev = rows_dev;
     w.ldm = ws.ldm;
     w.seg = ws.seg;
     w.out_scale = out_scale;
-    // m-chunks: about one workgroup per CU (the ring takes most of its LDS) in a single round, but no
-    // chunk under min_chunk_rows rows (a multiple of 64)
-    const int span = (int)ws.ldm;
-    int nch = dw_device_cus() / w.tile_start[w.nprob];
-    if (nch > span / min_chunk_rows) nch = span / min_chunk_rows;
-    if (nch < 1) nch = 1;
-    w.mchunk = dppo_cdiv(span, nch * 64) * 64;
-    w.nchunks = dppo_cdiv(span, w.mchunk);
+    const DWPlan plan = dw_plan(tile, items, n_items, ws.ldm, min_chunk_rows);
+    w.mchunk = plan.mchunk;
+    w.nchunks = plan.nchunks;
     return precision == DPPO_BF16 ? launch_dw_p<PolicyBF16>(w, tile, s)
          : precision == DPPO_F16  ? launch_dw_p<PolicyF16>(w, tile, s) : launch_dw_p<PolicyF32>(w, tile, s);
 }

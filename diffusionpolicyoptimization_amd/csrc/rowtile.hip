@@ -832,9 +832,12 @@ static int64_t actor_device_cus() {
     return n;
 }
 
-// the 2-byte operand policies (bf16, fp16) share the tile configurations
-template <class P2>
-static int launch_actor_2b(const ActorArgs& a, hipStream_t s) {
+// The tile decision, host arithmetic only: launch_actor_rowtile and the plan query (dppo_ppo_plan)
+// both take it from here. The 2-byte operand policies (bf16, fp16) share the tile configurations
+ActorTilePlan actor_tile_plan(int precision, int H, int XD, int64_t rows) {
+    // fp32: 32-row tiles on 16 waves (four per SIMD behind the 16x16x4 MFMA chains): update 41.5 ->
+    // 40.5 ms per iteration against 8 waves (profiles/r06zz_f32_tile_16wave_ab.txt)
+    if (!dppo_prec_2b(precision)) return ActorTilePlan{2, 16};
     const int v = row_tile_cfg().actor;
     // (r04: a 128-row tile, one activation tile in LDS with in-place layers, 8 or 4 waves of 8 x 4 /
     // 8 x 8 accumulator tiles, ran SLOWER: 0.464 / 0.543 vs 0.421 ms per fused 50,000-row minibatch,
@@ -843,7 +846,7 @@ static int launch_actor_2b(const ActorArgs& a, hipStream_t s) {
     // bf16, H = 512: 64-row tiles on 16 waves halve the weight stream per row of 32-row tiles; their
     // out-layer partials (16 waves x 64 rows x 16*NO) only fit the aliased LDS tile for XD <= 16
     // (walker2d / halfcheetah, XD = 24, run the 32-row tile)
-    if (a.H == 512 && v == 0 && a.XD <= 16) {
+    if (H == 512 && v == 0 && XD <= 16) {
         // (r05: running the short last round of 64-row tiles as twice as many 32-row tiles in a launch
         // of their own cost more than it saved, update 16.5 vs 15.5 ms per iteration: the critic's half
         // on the side stream fills the CUs that round leaves idle. Removed.)
@@ -851,18 +854,27 @@ static int launch_actor_2b(const ActorArgs& a, hipStream_t s) {
         // under the reference's global minibatch: 6,250 rows = 98 tiles) finishes in one tile's
         // latency either way, and a 32-row tile's is about 0.6 of a 64-row tile's (update 50.1 ->
         // 47.1 ms per iteration at 6,250-row minibatches, tools/ab_small_mb.sh)
-        const int64_t rows = (a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN) ? (int64_t)a.ws.ldm : a.nrows;
-        if ((rows + 63) / 64 < actor_device_cus()) return dispatch_actor<P2, 2, 8>(a, s);
-        return dispatch_actor<P2, 4, 16>(a, s);
+        if ((rows + 63) / 64 < actor_device_cus()) return ActorTilePlan{2, 8};
+        return ActorTilePlan{4, 16};
     }
-    return dispatch_actor<P2, 2, 8>(a, s);
+    return ActorTilePlan{2, 8};
+}
+
+template <class P2>
+static int launch_actor_2b(const ActorArgs& a, const ActorTilePlan& p, hipStream_t s) {
+    if (p.mt == 4 && p.waves == 16) return dispatch_actor<P2, 4, 16>(a, s);
+    if (p.mt == 2 && p.waves == 8) return dispatch_actor<P2, 2, 8>(a, s);
+    return dppo_set_error(DPPO_EUNSUPPORTED, "actor: no %d-row tile on %d waves", 16 * p.mt, p.waves);
 }
 
 int launch_actor_rowtile(const ActorArgs& a, int precision, hipStream_t s) {
-    if (precision == DPPO_BF16) return launch_actor_2b<PolicyBF16>(a, s);
-    if (precision == DPPO_F16) return launch_actor_2b<PolicyF16>(a, s);
-    // fp32: 32-row tiles on 16 waves (four per SIMD behind the 16x16x4 MFMA chains): update 41.5 ->
-    // 40.5 ms per iteration against 8 waves (profiles/r06zz_f32_tile_16wave_ab.txt)
+    // TRAIN modes cover the 64-padded images (launch_actor_t), the others the rows given
+    const int64_t rows = (a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN) ? (int64_t)a.ws.ldm : a.nrows;
+    const ActorTilePlan p = actor_tile_plan(precision, a.H, a.XD, rows);
+    if (precision == DPPO_BF16) return launch_actor_2b<PolicyBF16>(a, p, s);
+    if (precision == DPPO_F16) return launch_actor_2b<PolicyF16>(a, p, s);
+    if (p.mt != 2 || p.waves != 16)
+        return dppo_set_error(DPPO_EUNSUPPORTED, "actor: no fp32 %d-row tile on %d waves", 16 * p.mt, p.waves);
     return dispatch_actor<PolicyF32, 2, 16>(a, s);
 }
 

@@ -317,6 +317,62 @@ extern "C" int dppo_ppo_clear_ranges(const dppo_dims* d, int precision, int batc
     return DPPO_OK;
 }
 
+// The weight gradients of one network are one grouped dW launch. No m-chunk under 768 rows in the PPO
+// update: at small minibatches (6,250 rows, an 8-GPU rank's share) thinner chunks cost more in
+// partial-tile atomics than they gain in parallelism (0.177 -> 0.154 ms per minibatch; more, thinner
+// chunks measured slower on the emulated 8-rank line too, profiles/r05z_dw_chunks_ab.txt)
+constexpr int PPO_MIN_CHUNK_ROWS = 768;
+constexpr int PRETRAIN_MIN_CHUNK_ROWS = 64;
+
+// The problems of the grouped dW launches (the launches and dppo_ppo_plan both build them here; the plan
+// query passes a workspace without a base and null gradients, and reads the shapes only)
+static float* grad_at(float* g, size_t off) { return g ? g + off : nullptr; }
+// the actor's: PPO (the in-layer's bias and time-MLP gradients from the one-hot bucket rows) or
+// pretraining (those come from K bucket sums, seg_reduce + time_bwd)
+static void actor_dw_items(const Dims& D, const PpoWorkspace& ws, float* ga, bool pretrain, bool l2_def, DWItem (&it)[4]) {
+    const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
+    it[0] = pretrain ? DWItem{ws.a0T, D.IN, ws.dh1T, D.H, grad_at(ga, FA.in_w), EXTRA_NONE, nullptr}
+                     : DWItem{ws.a0T, D.IN, ws.dh1T, D.H, grad_at(ga, FA.in_w), EXTRA_ONEHOT, ws.gseg};
+    it[1] = DWItem{ws.u1T, D.H, ws.dh2T, D.H, grad_at(ga, FA.l1_w), EXTRA_ONES, grad_at(ga, FA.l1_b)};
+    it[2] = DWItem{ws.u2T, D.H, ws.dyT, D.XD, l2_def ? grad_at(ga, FA.l2_w) : ws.pl2, EXTRA_NONE, nullptr};   // l2 through the out layer
+    it[3] = DWItem{ws.a0T, D.IN, ws.dyT, D.XD, ws.pa0, EXTRA_ONES, grad_at(ga, FA.out_b)};   // out through the fold (out_back)
+}
+static void critic_dw_items(const Dims& D, const PpoWorkspace& ws, float* gc, DWItem (&it)[4]) {
+    const FlatOffsets FC = make_flat_offsets(D.SD, D.HC, 1, 0);
+    it[0] = DWItem{ws.csT, D.SD, ws.cdh1T, D.HC, grad_at(gc, FC.in_w), EXTRA_ONES, grad_at(gc, FC.in_b)};
+    it[1] = DWItem{ws.cu1T, D.HC, ws.cdh2T, D.HC, grad_at(gc, FC.l1_w), EXTRA_ONES, grad_at(gc, FC.l1_b)};
+    it[2] = DWItem{ws.cu2T, D.HC, ws.cdvT, 1, ws.cpl2, EXTRA_NONE, nullptr};
+    it[3] = DWItem{ws.ch3T, D.HC, ws.cdvT, 1, grad_at(gc, FC.out_w), EXTRA_ONES, grad_at(gc, FC.out_b)};
+}
+
+extern "C" int dppo_ppo_plan(const dppo_dims* d, int precision, int rows, int mode, int* out) {
+    Dims D;
+    int rc = dppo_check_dims(d, &D);
+    if (rc) return rc;
+    DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
+    DPPO_CHECK(out && rows > 0, "dppo_ppo_plan: bad arguments");
+    DPPO_CHECK(mode == DPPO_PLAN_TRAIN || mode == DPPO_PLAN_PRETRAIN || mode == DPPO_PLAN_LOGPROB,
+               "dppo_ppo_plan: mode must be 0 (train), 1 (pretrain) or 2 (logprob)");
+    const PpoWorkspace ws = make_ppo_workspace(D, precision, rows, nullptr);
+    // the row counts launch_actor_rowtile sees: the 64-padded images, or the log-prob pass's rows as given
+    const ActorTilePlan t = actor_tile_plan(precision, D.H, D.XD, mode == DPPO_PLAN_LOGPROB ? (int64_t)rows : (int64_t)ws.ldm);
+    out[0] = 16 * t.mt;
+    out[1] = t.waves;
+    out[2] = out[3] = out[4] = out[5] = 0;
+    if (mode == DPPO_PLAN_LOGPROB) return DPPO_OK;
+    DWItem it[4];
+    actor_dw_items(D, ws, nullptr, mode == DPPO_PLAN_PRETRAIN, false, it);
+    const DWPlan pa = dw_plan(DWTile::ACTOR, it, 4, ws.ldm, mode == DPPO_PLAN_PRETRAIN ? PRETRAIN_MIN_CHUNK_ROWS : PPO_MIN_CHUNK_ROWS);
+    out[2] = pa.nchunks;
+    out[3] = pa.mchunk;
+    if (mode == DPPO_PLAN_PRETRAIN) return DPPO_OK;
+    critic_dw_items(D, ws, nullptr, it);
+    const DWPlan pc = dw_plan(DWTile::CRITIC, it, 4, ws.ldm, PPO_MIN_CHUNK_ROWS);
+    out[4] = pc.nchunks;
+    out[5] = pc.mchunk;
+    return DPPO_OK;
+}
+
 // dppo_ppo_minibatch{,_part}'s arguments (include/dppo.h), in their order
 struct MinibatchArgs {
     const dppo_dims* d;
@@ -354,7 +410,6 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     const PpoWorkspace ws = make_ppo_workspace(D, precision, rows, (uint8_t*)m.workspace);
     DPPO_CHECK(ws.total < ((size_t)1 << 31), "dppo_ppo_minibatch: workspace for %d rows exceeds 2 GiB", rows);
     const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
-    const FlatOffsets FC = make_flat_offsets(D.SD, D.HC, 1, 0);
     float* ga = m.grads;
     float* gc = m.grads + FA.count;
     DPPO_CHECK(part >= MB_ACTOR && part <= MB_ACTOR_DW, "dppo_ppo_minibatch: bad part %d", (int)part);
@@ -412,11 +467,6 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     ca.fk = fk; ca.start = m.start; ca.row_index = m.row_index; ca.returns = m.returns; ca.hp = lh; ca.ws = ws;
     ca.metrics = m.metrics;
 
-    // The weight gradients of one network are one grouped dW launch. No m-chunk under 768 rows: at
-    // small minibatches (6,250 rows, an 8-GPU rank's share) thinner chunks cost more in partial-tile
-    // atomics than they gain in parallelism (0.177 -> 0.154 ms per minibatch; more, thinner chunks
-    // measured slower on the emulated 8-rank line too, profiles/r05z_dw_chunks_ab.txt)
-    constexpr int MIN_CHUNK_ROWS = 768;
     // the critic's half on stream st: its distinct samples (sample-weighted value loss,
     // crit_rows_kernel), its row tiles, its dW (on the small ring, beside the actor's tail) and its
     // l2 gradient, which also zeroes the sample counts
@@ -434,28 +484,20 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
         }
         int rc_ = launch_critic_rowtile(ca, precision, st);
         if (rc_) return rc_;
-        const DWItem items[] = {
-            {ws.csT, D.SD, ws.cdh1T, D.HC, gc + FC.in_w, EXTRA_ONES, gc + FC.in_b},
-            {ws.cu1T, D.HC, ws.cdh2T, D.HC, gc + FC.l1_w, EXTRA_ONES, gc + FC.l1_b},
-            {ws.cu2T, D.HC, ws.cdvT, 1, ws.cpl2, EXTRA_NONE, nullptr},
-            {ws.ch3T, D.HC, ws.cdvT, 1, gc + FC.out_w, EXTRA_ONES, gc + FC.out_b},
-        };
+        DWItem items[4];
+        critic_dw_items(D, ws, gc, items);
         {
             DppoKtScope kt(KT_DW_CRITIC, st);
-            rc_ = launch_dw(DWTile::CRITIC, precision, items, 4, ws, 1.f / gscale, ca.crow_cnt, MIN_CHUNK_ROWS, st);
+            rc_ = launch_dw(DWTile::CRITIC, precision, items, 4, ws, 1.f / gscale, ca.crow_cnt, PPO_MIN_CHUNK_ROWS, st);
         }
         if (rc_) return rc_;
         return launch_critic_l2_back(D, precision, ws, m.packed_critic, gc, crit_cnt, st);
     };
     auto actor_grads = [&]() -> int {
-        const DWItem items[] = {
-            {ws.a0T, D.IN, ws.dh1T, D.H, ga + FA.in_w, EXTRA_ONEHOT, ws.gseg},
-            {ws.u1T, D.H, ws.dh2T, D.H, ga + FA.l1_w, EXTRA_ONES, ga + FA.l1_b},
-            {ws.u2T, D.H, ws.dyT, D.XD, l2_def ? ga + FA.l2_w : ws.pl2, EXTRA_NONE, nullptr},   // l2 through the out layer
-            {ws.a0T, D.IN, ws.dyT, D.XD, ws.pa0, EXTRA_ONES, ga + FA.out_b},   // out through the fold (out_back)
-        };
+        DWItem items[4];
+        actor_dw_items(D, ws, ga, false, l2_def, items);
         DppoKtScope kt(KT_DW_ACTOR, s);
-        return launch_dw(DWTile::ACTOR, precision, items, 4, ws, 1.f / gscale, nullptr, MIN_CHUNK_ROWS, s);
+        return launch_dw(DWTile::ACTOR, precision, items, 4, ws, 1.f / gscale, nullptr, PPO_MIN_CHUNK_ROWS, s);
     };
     // after the actor's dW: the time-MLP backward, W_out's gradient and (materialised) l2's in one launch.
     // (Forking the time-MLP backward beside the dW (r05, profiles/r05y_tb_fork_ab.txt) and running it
@@ -588,13 +630,9 @@ extern "C" int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const 
     if (rc) return rc;
 
     // the in-layer's bias and time-MLP gradients come from K bucket sums (seg_reduce + time_bwd)
-    const DWItem items[] = {
-        {ws.a0T, D.IN, ws.dh1T, D.H, ga + FA.in_w, EXTRA_NONE, nullptr},
-        {ws.u1T, D.H, ws.dh2T, D.H, ga + FA.l1_w, EXTRA_ONES, ga + FA.l1_b},
-        {ws.u2T, D.H, ws.dyT, D.XD, ws.pl2, EXTRA_NONE, nullptr},   // l2 through the out layer
-        {ws.a0T, D.IN, ws.dyT, D.XD, ws.pa0, EXTRA_ONES, ga + FA.out_b},   // out through the fold (out_back)
-    };
-    rc = launch_dw(DWTile::ACTOR, precision, items, 4, ws, 1.f / gscale, nullptr, 64, s);
+    DWItem items[4];
+    actor_dw_items(D, ws, ga, true, false, items);
+    rc = launch_dw(DWTile::ACTOR, precision, items, 4, ws, 1.f / gscale, nullptr, PRETRAIN_MIN_CHUNK_ROWS, s);
     if (rc) return rc;
     const float inv = 1.f / gscale;
     if (precision == DPPO_BF16)

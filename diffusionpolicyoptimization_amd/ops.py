@@ -740,6 +740,21 @@ def ppo_workspace(d: ModelDims, precision, rows, device):
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
+_PLAN_MODES = {"train": 0, "pretrain": 1, "logprob": 2}
+
+
+def ppo_plan(d: ModelDims, precision, rows, mode="train"):
+    """The kernel paths a launch of `rows` rows takes on the current device (dppo_ppo_plan: the host
+    functions the launchers themselves call): dict(actor_tile_rows (32 or 64), actor_waves,
+    dw_chunks_actor, dw_chunk_rows_actor, dw_chunks_critic, dw_chunk_rows_critic). mode: "train"
+    (ppo_minibatch), "pretrain" (pretrain_minibatch) or "logprob" (rows = samples x K'); the dW fields
+    are 0 where the mode has no such launch."""
+    out = (ctypes.c_int * 6)()
+    _lib.call("dppo_ppo_plan", ctypes.byref(d.c()), _prec(precision), int(rows), _PLAN_MODES[mode], out)
+    return dict(actor_tile_rows=out[0], actor_waves=out[1], dw_chunks_actor=out[2], dw_chunk_rows_actor=out[3],
+                dw_chunks_critic=out[4], dw_chunk_rows_critic=out[5])
+
+
 def ppo_adv_stats(advantages, total, kf, perm_seed, epoch, start, rows, out, row_index=None):
     _lib.call("dppo_ppo_adv_stats", ptr(advantages), int(total), int(kf), ctypes.c_uint64(perm_seed), int(epoch),
               int(start), int(rows), ptr(row_index), ptr(out), stream_handle(advantages.device))

@@ -355,6 +355,18 @@ DPPO_API int dppo_eta_step(float* eta_state, const double* metrics, int64_t step
                            const float* ddim_base, float* sched, int ddim_steps, float* eta_out, void* stream);
 
 DPPO_API size_t dppo_ppo_workspace_bytes(const dppo_dims* d, int precision, int batch_rows);
+/* Which kernel paths a launch of `rows` rows takes on the current device (read-only host arithmetic,
+ * the same functions the launchers call; no device work; an addition within ABI 15). mode: a
+ * dppo_ppo_minibatch (DPPO_PLAN_TRAIN), a dppo_pretrain_minibatch (DPPO_PLAN_PRETRAIN) or a
+ * dppo_logprob pass over rows = n * K' rows (DPPO_PLAN_LOGPROB). out[6] =
+ *   {actor row tile's rows (32 or 64), its waves per workgroup,
+ *    m-chunks of the actor's weight-gradient launch, rows per chunk (the last may be shorter),
+ *    the same two of the critic's launch (host-side: with sample dedup the kernel re-cuts the same
+ *    number of chunks over the device-side count of distinct samples)};
+ * the weight-gradient fields are 0 where the mode has no such launch (logprob: all four; pretrain:
+ * the critic's). */
+enum { DPPO_PLAN_TRAIN = 0, DPPO_PLAN_PRETRAIN = 1, DPPO_PLAN_LOGPROB = 2 };
+DPPO_API int dppo_ppo_plan(const dppo_dims* d, int precision, int rows, int mode, int* out);
 DPPO_API int dppo_ppo_adv_stats(const float* advantages, int64_t total, int K_ft, uint64_t perm_seed, int epoch,
                        int64_t start, int rows, const int64_t* row_index, double* adv_stats, void* stream);
 /* The adv_stats of every minibatch of an update phase in one launch: minibatch m = e * n_batch + b

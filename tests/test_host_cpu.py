@@ -103,6 +103,48 @@ def test_ppo_clear_ranges_are_what_each_part_zeroes(lib):
         ops.ClearRanges(d, "bf16", rows, ws, met, 5)
 
 
+def test_ppo_plan_host_arithmetic(lib):
+    """dppo_ppo_plan (host arithmetic, no device work) on whatever CU count the library sees (256
+    without a device): the tile rule's fixed cases, one 32 -> 64 switch at a 64-row boundary of the
+    padded row count, and the m-chunks tiling the padded rows with no chunk under the update's minimum."""
+    from diffusionpolicyoptimization_amd import ops
+    hopper, walker = ops.ModelDims(), ops.ModelDims(obs_dim=17, action_dim=6)
+    for rows in (1, 150, 100000):
+        p = ops.ppo_plan(hopper, "fp32", rows)
+        assert (p["actor_tile_rows"], p["actor_waves"]) == (32, 16)
+        p = ops.ppo_plan(walker, "bf16", rows)      # XD = 24: the 64-row tile's partials do not fit
+        assert (p["actor_tile_rows"], p["actor_waves"]) == (32, 8)
+    p = ops.ppo_plan(hopper, "bf16", 150)
+    assert p == dict(actor_tile_rows=32, actor_waves=8, dw_chunks_actor=1, dw_chunk_rows_actor=192,
+                     dw_chunks_critic=1, dw_chunk_rows_critic=192)
+    for prec in ("bf16", "fp16"):
+        tiles = [ops.ppo_plan(hopper, prec, 64 * k)["actor_tile_rows"] for k in range(1, 1100)]
+        k64 = tiles.index(64) + 1               # the first padded size on the 64-row tile: one round
+        assert tiles[:k64 - 1] == [32] * (k64 - 1) and set(tiles[k64 - 1:]) == {64}
+        assert ops.ppo_plan(hopper, prec, 64 * (k64 - 1) + 1)["actor_waves"] == 16
+        assert ops.ppo_plan(hopper, prec, 64 * (k64 - 1))["actor_waves"] == 8
+        for mode in ("pretrain", "logprob"):    # logprob: the rows as given, not padded
+            assert ops.ppo_plan(hopper, prec, 64 * k64, mode)["actor_tile_rows"] == 64
+            assert ops.ppo_plan(hopper, prec, 64 * (k64 - 1), mode)["actor_tile_rows"] == 32
+    assert ops.ppo_plan(hopper, "bf16", 64 * (k64 - 1) + 1, "logprob")["actor_tile_rows"] == 64
+    for rows in (767, 1536, 1600, 6250, 16321, 50000):
+        ldm = -(-rows // 64) * 64
+        p = ops.ppo_plan(hopper, "bf16", rows)
+        for net in ("actor", "critic"):
+            n, m = p[f"dw_chunks_{net}"], p[f"dw_chunk_rows_{net}"]
+            assert n >= 1 and m % 64 == 0 and (n - 1) * m < ldm <= n * m
+            assert n == 1 or m >= 768
+        q = ops.ppo_plan(hopper, "bf16", rows, "pretrain")
+        assert q["dw_chunks_actor"] >= p["dw_chunks_actor"] and q["dw_chunks_critic"] == q["dw_chunk_rows_critic"] == 0
+        assert ops.ppo_plan(hopper, "bf16", rows, "logprob")["dw_chunks_actor"] == 0
+    p = ops.ppo_plan(hopper, "bf16", 1600)
+    assert (p["dw_chunks_actor"], p["dw_chunk_rows_actor"]) == (2, 832)
+    with pytest.raises(Exception):
+        ops.ppo_plan(hopper, "bf16", 0)
+    assert lib.dppo_ppo_plan(ctypes.byref(hopper.c()), 1, 100, 3, (ctypes.c_int * 6)()) == 1   # a bad mode
+    assert "mode" in lib.dppo_last_error().decode()
+
+
 @pytest.mark.parametrize("field,value,msg", [("actor_hidden", 100, "actor_hidden"), ("time_dim", 3, "time_dim"),
                                              ("ft_denoising_steps", 30, "ft_denoising_steps"),
                                              ("action_dim", 9, "horizon_steps*action_dim")])

@@ -43,7 +43,8 @@ int dppo_pack_rt_fold(int in_dim, int hidden, int out_dim, int time_dim, int pre
                       void* packed_actor, int temb_steps, int time_stride, hipStream_t s);
 // temb: the TEMB table is stale too (the fused actor step), not only the split-sampler tables
 int dppo_mark_tables_stale(const Dims& D, int precision, const float* actor_params, const void* packed_actor, bool temb);
-
+// device address of mapped pinned host memory (dppo_host_alloc), cached; null if not mapped (host_staging.hip)
+void* mapped_ptr(const void* host);
 
 // precision enum values the library implements; the two 2-byte operand policies share layouts
 inline bool dppo_prec_ok(int p) { return p == DPPO_F32 || p == DPPO_BF16 || p == DPPO_F16; }

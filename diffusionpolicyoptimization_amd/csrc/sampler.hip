@@ -7,9 +7,7 @@
 // (diffusion_vpg.py:198-243, 301-320). Activations never leave LDS; weights stream from L2.
 // The actor used at step t is actor_ft when t < K' else the frozen base actor (diffusion_vpg.py:161-180);
 // the reference's always-computed base forward (:161) does not change the result and is skipped.
-#include <mutex>
 #include <stdlib.h>
-#include <string.h>
 #include "dppo_common.cuh"
 #include "dppo_internal.h"
 #include "dppo_sampler.h"
@@ -81,11 +79,10 @@ __device__ inline void squeue_prime(WQueue<D, NT>& Q, const SSeg& s0, const SNex
 // acc = A[16 rows][KSF*KG] x W[:, ntile0*16 ..): k-steps [0, RKL) from the resident fragments
 // (computed first: they cover the latency of the queue's first loads after the layer barrier),
 // k-steps [RKL, KSF) from the queue, which keeps D k-steps of look-ahead into the next segments.
-// k-steps [RKL, RKL+LKL) come from fragments kept in LDS (lw: [LKL][NTOT n-tiles][64 lanes] x 16 B).
-template <class P, int NT, int KSF, int RKL, int LKL, int NTOT, int D>
-__device__ inline void gemm_res(const typename P::AT* A, int lda, WSrc Ws, const u32x4 (*res)[NT], const u32x4* lw,
+template <class P, int NT, int KSF, int RKL, int D>
+__device__ inline void gemm_res(const typename P::AT* A, int lda, WSrc Ws, const u32x4 (*res)[NT],
                                 int ntile0, f32x4 (&acc)[1][NT], int lane, WQueue<D, NT>& Q, const SNext& nx) {
-    constexpr int KS = KSF - RKL - LKL;
+    constexpr int KS = KSF - RKL;
 #pragma unroll
     for (int n = 0; n < NT; ++n) zero_acc(acc[0][n]);
 #pragma unroll
@@ -93,12 +90,6 @@ __device__ inline void gemm_res(const typename P::AT* A, int lda, WSrc Ws, const
         const u32x4 a = lds_afrag<P>(A, lda, 0, ks, lane);
 #pragma unroll
         for (int n = 0; n < NT; ++n) acc[0][n] = P::mma(a, res[ks][n], acc[0][n]);
-    }
-#pragma unroll
-    for (int kl = 0; kl < LKL; ++kl) {
-        const u32x4 a = lds_afrag<P>(A, lda, 0, RKL + kl, lane);
-#pragma unroll
-        for (int n = 0; n < NT; ++n) acc[0][n] = P::mma(a, lw[(kl * NTOT + ntile0 + n) * 64 + lane], acc[0][n]);
     }
 #pragma unroll
     for (int j = 0; j < KS; ++j) {
@@ -111,26 +102,46 @@ __device__ inline void gemm_res(const typename P::AT* A, int lda, WSrc Ws, const
             for (int n = 0; n < NT; ++n) Q.b[d][n] = Q.b[d + 1][n];
 #pragma unroll
         for (int n = 0; n < NT; ++n) Q.b[D - 1][n] = sfrag<KS>(Ws, KSF, nx, ntile0 + n, j + D, lane);
-        const u32x4 a = lds_afrag<P>(A, lda, 0, RKL + LKL + j, lane);
+        const u32x4 a = lds_afrag<P>(A, lda, 0, RKL + j, lane);
 #pragma unroll
         for (int n = 0; n < NT; ++n) acc[0][n] = P::mma(a, c[n], acc[0][n]);
     }
 }
 
-// SW waves per workgroup, each owning NT = H/(16*SW) n-tiles of every hidden layer. RK hidden
-// k-steps and (RIO) the whole in- and out-layers are resident in registers, LK more hidden
-// k-steps in LDS; QD k-steps of the rest in flight.
-template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, int LK, int RIO>
+// The two geometries the streaming kernel runs (r01 measured five other resident sets, among them
+// hidden k-steps kept in LDS and the in- or out-layer resident alone, and two more 16-wave forms: all
+// slower, removed; profiles/README.md "Retired build variants"): SW waves per workgroup, each owning
+// NT = H/(16*SW) n-tiles of every hidden layer; RK hidden k-steps and (RES) the whole in- and out-layers
+// resident in registers; QD k-steps of the rest in flight.
+struct StreamGeom { int SW, RK; bool RES; int QD; };
+constexpr StreamGeom STREAM_GEOM[2] = {
+    {16, 0, false, 3},   // fp32, or H != 512: nothing resident
+    {8, 2, true, 3},     // 2-byte operands at H = 512
+};
+constexpr const StreamGeom& stream_geom(bool two_byte, int H) { return STREAM_GEOM[two_byte && H == 512 ? 1 : 0]; }
+
+// dynamic LDS of the streaming kernel for NO out n-tiles on SW waves
+template <class P>
+static size_t stream_lds_total(const SampleArgs& a, int NO, int SW) {
+    const size_t ESZ = sizeof(typename P::AT);
+    const int pad = lds_pad_elems<P>(), H = a.H, ldh = H + pad, lda0 = a.L.ks_in * P::KG + pad;
+    const int XD = a.XD, SD = a.SD, TD = a.TD, K = a.K, NOC = 16 * NO;
+    size_t o = 0;
+#define DPPO_SUM(T, name, bytes) o += bytes;
+    STREAM_LDS_REGIONS(DPPO_SUM)
+#undef DPPO_SUM
+    return o;
+}
+
+template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, bool RES>
 __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
     SPHASE_START;
     using AT = typename P::AT;
     constexpr int ST = SW * 64;
     constexpr int KSH = ksh_for<P>(NT, SW);
     constexpr int NOK = KSH / SW;
-    constexpr bool RIN = RIO & 1, ROUT = RIO & 2;   // in-layer / out-layer resident
-    constexpr int RKI = RIN ? KSI : 0;       // resident in-layer k-steps
-    constexpr int NTOT = NT * SW;            // n-tiles of a hidden layer
-    static_assert(RK + LK < KSH, "at least one streamed hidden k-step");
+    constexpr int RKI = RES ? KSI : 0;       // resident in-layer k-steps
+    static_assert(RK < KSH, "at least one streamed hidden k-step");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
     const int row0 = blockIdx.x * 16;
@@ -143,20 +154,12 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
     const int XD = a.XD, SD = a.SD, TD = a.TD, K = a.K, KF = a.KF;
     const int NOC = 16 * NO;
 
-    // ---- LDS carve (all offsets multiples of 16 B) ----
+    // ---- LDS carve (STREAM_LDS_REGIONS, dppo_sampler.h: all offsets multiples of 16 B) ----
+    constexpr size_t ESZ = sizeof(AT);
     size_t o = 0;
-    AT* tA = (AT*)(smem + o); o += dppo_align16(sizeof(AT) * 16 * ldh);
-    AT* tB = (AT*)(smem + o); o += dppo_align16(sizeof(AT) * 16 * ldh);
-    AT* a0 = (AT*)(smem + o); o += dppo_align16(sizeof(AT) * 16 * lda0);
-    float* xs = (float*)(smem + o); o += dppo_align16(4 * 16 * XD);
-    float* st = (float*)(smem + o); o += dppo_align16(4 * 16 * SD);
-    float* temb = (float*)(smem + o); o += dppo_align16(4 * K * TD);
-    float* part = (float*)(smem + o); o += dppo_align16(4 * SW * 16 * NOC);
-    float* sch = (float*)(smem + o); o += dppo_align16(4 * K * DPPO_SCHED_COLS);
-    float* bias = (float*)(smem + o); o += dppo_align16(4 * 2 * (3 * H + NOC));  // [actor][in,l1,l2,out]
-    float* zt = (float*)(smem + o); o += dppo_align16(4 * K * 16 * XD);           // clipped noise [i][row][q]
-    u32x4* lw1 = (u32x4*)(smem + o); o += (size_t)LK * NTOT * 1024;                // LDS-resident hidden k-steps
-    u32x4* lw2 = (u32x4*)(smem + o); o += (size_t)LK * NTOT * 1024;
+#define DPPO_CARVE(T, name, bytes) T* name = (T*)(smem + o); o += bytes;
+    STREAM_LDS_REGIONS(DPPO_CARVE)
+#undef DPPO_CARVE
 
     const int ntile0 = wave * NT;
     const __amdgpu_buffer_rsrc_t rs_base = packed_rsrc(a.packed_base), rs_ft = packed_rsrc(a.packed_ft);
@@ -165,18 +168,8 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
     auto W = [&](int ft, int seg) { return wsrc(ft ? rs_ft : rs_base, L.off[seg]); };
     // the streamed segments of a denoising step: [in (unless resident)], l1[RK..], l2[RK..]
     auto s_in = [&](int ft) { return sseg(W(ft, SEG_W_IN), KSI, 0); };
-    auto s_l1 = [&](int ft) { return sseg(W(ft, SEG_W_L1), KSH, RK + LK); };
-    auto s_l2 = [&](int ft) { return sseg(W(ft, SEG_W_L2), KSH, RK + LK); };
-    // hidden k-steps [RK, RK+LK) of both hidden layers into LDS, [k][n-tile][lane] (callers barrier)
-    auto load_lds = [&](int ft) {
-        const WSrc w1 = W(ft, SEG_W_L1), w2 = W(ft, SEG_W_L2);
-        for (int c = tid; c < LK * NTOT * 64; c += ST) {
-            const int kl = c / (NTOT * 64), nt = (c / 64) % NTOT, ln = c % 64;
-            const uint32_t so = (uint32_t)(nt * KSH + RK + kl) << 10;
-            lw1[c] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(w1.rsrc, ln << 4, w1.off + so, 0));
-            lw2[c] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(w2.rsrc, ln << 4, w2.off + so, 0));
-        }
-    };
+    auto s_l1 = [&](int ft) { return sseg(W(ft, SEG_W_L1), KSH, RK); };
+    auto s_l2 = [&](int ft) { return sseg(W(ft, SEG_W_L2), KSH, RK); };
 
     // resident fragments of the actor in use (reloaded when the actor changes, once per launch)
     u32x4 r_in[RKI > 0 ? RKI : 1][NT], r_l1[RK > 0 ? RK : 1][NT], r_l2[RK > 0 ? RK : 1][NT];
@@ -193,16 +186,15 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
                 r_l1[k][n] = load_bfrag_c(W(ft, SEG_W_L1), KSH, ntile0 + n, k, lane);
                 r_l2[k][n] = load_bfrag_c(W(ft, SEG_W_L2), KSH, ntile0 + n, k, lane);
             }
-        if constexpr (ROUT) out_prefetch<NOK, NO, SW>(r_out, W(ft, SEG_W_OUT), L.ks_h, wave, lane);
+        if constexpr (RES) out_prefetch<NOK, NO, SW>(r_out, W(ft, SEG_W_OUT), L.ks_h, wave, lane);
     };
     // the weight stream starts with step 0 (t = K-1); its first loads and the resident set go out
     // before anything waits (noise, the host's observation)
     const int ft0 = __builtin_amdgcn_readfirstlane(K - 1 < KF ? 1 : 0);
     WQueue<QD, NT> R;
-    if constexpr (RIN) squeue_prime(R, s_l1(ft0), SNext{s_l2(ft0), s_l1(ft0)}, ntile0, lane);
+    if constexpr (RES) squeue_prime(R, s_l1(ft0), SNext{s_l2(ft0), s_l1(ft0)}, ntile0, lane);
     else squeue_prime(R, s_in(ft0), SNext{s_l1(ft0), s_l2(ft0)}, ntile0, lane);
     load_resident(ft0);
-    if constexpr (LK > 0) load_lds(ft0);      // made visible by the prologue's barriers
     int cur = ft0;
 
     // ---- prologue: schedule, biases, state, x_T, time-embedding table ----
@@ -227,35 +219,8 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
         tv = ((const float*)((t < KF ? a.packed_ft : a.packed_base) + L.off[SEG_TEMB]))[tid];
     }
     float scv = tid < K * DPPO_SCHED_COLS ? a.sched[tid] : 0.f;
-    // noise: all K steps' draws up front (injected, or the Philox stream: one block gives the 4
-    // normals of a group of 4 action coordinates), clipped to +-randn_clip (:319), so the
-    // denoising loop carries no RNG state; slot K is x_T
-    const int XG = (XD + 3) / 4;
-    for (int it = tid; it < (K + 1) * 16 * XG; it += ST) {
-        const int step = it / (16 * XG), r = (it / XG) % 16, g = it % XG, row = row0 + r;
-        float z[4];
-        if (step == K && a.x_T) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) z[k] = (row < a.E && 4 * g + k < XD) ? a.x_T[(size_t)row * XD + 4 * g + k] : 0.f;
-        } else if (INJ && step < K) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                z[k] = (row < a.E && 4 * g + k < XD) ? a.noise[((size_t)step * a.E + row) * XD + 4 * g + k] : 0.f;
-        } else {
-            philox_normal4(a.seed, (uint32_t)g, (uint32_t)(a.env_offset + row), (uint32_t)step, a.call_id, z);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int q = 4 * g + k;
-            if (q >= XD) break;
-            if (step < K) {
-                zt[(step * 16 + r) * XD + q] = fminf(fmaxf(z[k], -a.randn_clip), a.randn_clip);
-            } else {
-                xs[r * XD + q] = z[k];
-                if (KF == K && a.chains && row < a.E) a.chains[((size_t)row * (KF + 1) + 0) * XD + q] = z[k];
-            }
-        }
-    }
+    // noise: all K steps' draws up front, slot K is x_T (sampler_draw_noise)
+    sampler_draw_noise<INJ, ST>(a, XD, row0, tid, zt, xs, KF == K && a.chains, [](float* p, float v) { *p = v; });
 #pragma unroll
     for (int u = 0; u < 4; ++u)
         if (tid + u * ST < NB4) ((float4*)bias)[tid + u * ST] = bv[u];
@@ -281,25 +246,13 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
             if (a.cond_out && row < a.E) a.cond_out[(size_t)row * SD + i % SD] = st[i];
         }
     } else {
-    if (a.go) {
-        if (tid == 0) {
-            const uint64_t t_end = __builtin_amdgcn_s_memrealtime() + 400000000ull;   // 100 MHz clock: 4 s
-            while (__hip_atomic_load(a.go, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < a.go_value) {
-                __builtin_amdgcn_s_sleep(8);
-                if (__builtin_amdgcn_s_memrealtime() > t_end) {
-                    __hip_atomic_fetch_or(a.done, 0x80000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    break;
-                }
-            }
+        if (a.go) sampler_wait_go(a, true, tid);
+        for (int i = tid; i < 16 * SD; i += ST) {
+            const int r = i / SD, c = i % SD, row = row0 + r;
+            const float v = row < a.E ? a.cond[(size_t)row * SD + c] : 0.f;
+            st[i] = v;
+            if (a.cond_out && row < a.E) a.cond_out[(size_t)row * SD + c] = v;
         }
-        __syncthreads();
-    }
-    for (int i = tid; i < 16 * SD; i += ST) {
-        const int r = i / SD, c = i % SD, row = row0 + r;
-        const float v = row < a.E ? a.cond[(size_t)row * SD + c] : 0.f;
-        st[i] = v;
-        if (a.cond_out && row < a.E) a.cond_out[(size_t)row * SD + c] = v;
-    }
     }
     __syncthreads();
     // a0 = [x, temb(t), state, 0-pad] for step 0 (t = K-1); later steps get x and temb from the
@@ -322,27 +275,20 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
         const int PKn = __builtin_amdgcn_readfirstlane(t - 1 >= 0 ? (t - 1 < KF ? 1 : 0) : is_ft);
         if (PK != cur) {                                    // the actor switch (t = K'-1): once per launch
             load_resident(PK);
-            if constexpr (LK > 0) load_lds(PK);
             // wait for the reload HERE (a real s_waitcnt the waitcnt pass sees, not inline asm):
             // otherwise the pass treats the resident registers as possibly in flight on every
             // iteration and drains the weight queue before their first use in each layer
             __builtin_amdgcn_s_waitcnt(0x0F70);             // vmcnt(0)
-            if constexpr (LK > 0) __syncthreads();
             cur = PK;
         }
         const float* bb = bias + is_ft * (3 * H + NOC);
         ORing<NOK, NO> ob;                                 // out-layer fragments, consumed 3 layers later
-        if constexpr (ROUT) ob = r_out;
+        if constexpr (RES) ob = r_out;
         else out_prefetch<NOK, NO, SW>(ob, W(PK, SEG_W_OUT), L.ks_h, wave, lane);
         SPHASE(1);
         // b) in-Dense: h1 = a0 W_in + b_in  (no activation after the input layer, mlp.py:144)
         f32x4 h1[1][NT], acc[1][NT];
-        if constexpr (RIN)
-            gemm_res<P, NT, KSI, KSI, 0, NTOT, QD>(a0, lda0, W(PK, SEG_W_IN), r_in, nullptr, ntile0, h1, lane, R,
-                                                   SNext{s_l1(PK), s_l2(PK)});
-        else
-            gemm_res<P, NT, KSI, 0, 0, NTOT, QD>(a0, lda0, s_in(PK).W, r_in, nullptr, ntile0, h1, lane, R,
-                                                 SNext{s_l1(PK), s_l2(PK)});
+        gemm_res<P, NT, KSI, RKI, QD>(a0, lda0, W(PK, SEG_W_IN), r_in, ntile0, h1, lane, R, SNext{s_l1(PK), s_l2(PK)});
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
             const int col = (ntile0 + n) * 16 + ccol(lane);
@@ -356,8 +302,8 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
         lds_sync();
         SPHASE(2);
         // c) l1: relu(h1) W_l1 + b -> relu -> tB   (pre-activation block, mlp.py:192-193,202-203)
-        gemm_res<P, NT, KSH, RK, LK, NTOT, QD>(tA, ldh, s_l1(PK).W, r_l1, lw1, ntile0, acc, lane, R,
-                                     RIN ? SNext{s_l2(PK), s_l1(PKn)} : SNext{s_l2(PK), s_in(PKn)});
+        gemm_res<P, NT, KSH, RK, QD>(tA, ldh, s_l1(PK).W, r_l1, ntile0, acc, lane, R,
+                                     RES ? SNext{s_l2(PK), s_l1(PKn)} : SNext{s_l2(PK), s_in(PKn)});
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
             const int col = (ntile0 + n) * 16 + ccol(lane);
@@ -369,8 +315,8 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
         SPHASE(3);
         // d) l2: relu(h2) W_l2 + b + h1 (residual, mlp.py:206) -> tA; the stream moves on to the
         //    next denoising step (possibly the other actor)
-        gemm_res<P, NT, KSH, RK, LK, NTOT, QD>(tB, ldh, s_l2(PK).W, r_l2, lw2, ntile0, acc, lane, R,
-                                     RIN ? SNext{s_l1(PKn), s_l2(PKn)} : SNext{s_in(PKn), s_l1(PKn)});
+        gemm_res<P, NT, KSH, RK, QD>(tB, ldh, s_l2(PK).W, r_l2, ntile0, acc, lane, R,
+                                     RES ? SNext{s_l1(PKn), s_l2(PKn)} : SNext{s_in(PKn), s_l1(PKn)});
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
             const int col = (ntile0 + n) * 16 + ccol(lane);
@@ -400,12 +346,7 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
             for (int w = 0; w < SW; ++w) eps += part[(w * 16 + r) * NOC + q];
             const float* sc = sch + t * DPPO_SCHED_COLS;
             const float x = xs[tid];
-            float sd = expf(0.5f * sc[4]);
-            // eval noise rule of the table row (include/dppo.h: DDPM t = 0 or any DDIM row -> 0;
-            // other DDPM rows clip at 1e-3; diffusion_vpg.py:303-315)
-            if (a.deterministic && sc[6] != 0.f) sd = 0.f;
-            else if (a.deterministic) sd = fminf(fmaxf(sd, sc[5]), 1e6f);
-            else sd = fminf(fmaxf(sd, a.min_std), 1e6f);
+            const float sd = sampler_noise_std(a, sc);
             float xn = ddpm_post(sc[0], sc[1], sc[2], sc[3], sd, x, eps, zt[i * 16 * XD + tid]);   // (:198-242, :301-320)
             if (a.final_clip > 0.f && i == K - 1) xn = fminf(fmaxf(xn, -a.final_clip), a.final_clip);
             xs[tid] = xn;
@@ -437,33 +378,13 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
     }
 }
 
-template <class P>
-static size_t sample_lds_bytes(const SampleArgs& a, int NO, int SW, int LK) {
-    using AT = typename P::AT;
-    const int pad = lds_pad_elems<P>();
-    const int ldh = a.H + pad;
-    const int lda0 = a.L.ks_in * P::KG + pad;
-    size_t o = 0;
-    o += dppo_align16(sizeof(AT) * 16 * ldh) * 2;
-    o += dppo_align16(sizeof(AT) * 16 * lda0);
-    o += dppo_align16(4 * 16 * a.XD);
-    o += dppo_align16(4 * 16 * a.SD);
-    o += dppo_align16(4 * a.K * a.TD);
-    o += dppo_align16(4 * SW * 16 * 16 * NO);
-    o += dppo_align16(4 * a.K * DPPO_SCHED_COLS);
-    o += dppo_align16(4 * 2 * (3 * a.H + 16 * NO));
-    o += dppo_align16(4 * a.K * 16 * a.XD);
-    o += (size_t)2 * LK * (a.H / 16) * 1024;
-    return o;
-}
-
-template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, int LK, int RIO>
+template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, bool RES>
 static int launch_sample_q(const SampleArgs& a, hipStream_t s) {
     if (a.L.ks_h != ksh_for<P>(NT, SW) || a.L.ks_in != KSI || a.L.ks_h % SW != 0)
         return dppo_set_error(DPPO_EUNSUPPORTED, "sampler: hidden %d not supported at this precision", a.H);
-    const size_t lds = sample_lds_bytes<P>(a, NO, SW, LK);
+    const size_t lds = stream_lds_total<P>(a, NO, SW);
     if (lds > 160 * 1024) return dppo_set_error(DPPO_EUNSUPPORTED, "sampler needs %zu B of LDS", lds);
-    auto k = sample_kernel<P, NT, NO, KSI, INJ, QD, SW, RK, LK, RIO>;
+    auto k = sample_kernel<P, NT, NO, KSI, INJ, QD, SW, RK, RES>;
     { const int rc_ = dppo_func_lds((const void*)k, (size_t)lds); if (rc_) return rc_; }
     DppoKtScope kt(KT_SAMPLER, s);
     hipLaunchKernelGGL(k, dim3(dppo_cdiv(a.E, 16)), dim3(SW * 64), lds, s, a);
@@ -473,11 +394,8 @@ static int launch_sample_q(const SampleArgs& a, hipStream_t s) {
 
 // Sampler selection (DPPO_SAMPLER_CFG, default "x"):
 //   "x": the split register-resident kernel (sampler_split.hip) where it applies (2-byte operands,
-//        H = 512, <= 512 envs), else the weight-streaming kernel below;
-//   "r": the weight-streaming kernel always (8 waves, in/out layers + 2 hidden k-steps resident,
-//        QD 3, for 2-byte operands at H = 512; 16 waves with nothing resident otherwise).
-// (r01 measured five other resident-set geometries of the streaming kernel, "l", "m", "q", "i",
-// "e", and two 16-wave ones: all slower; they were removed in r03 with the binary's size in mind.)
+//        H = 512, <= 512 envs), else the weight-streaming kernel above;
+//   "r": the weight-streaming kernel always (STREAM_GEOM).
 static char sampler_cfg() {
     static char c = [] {
         const char* e = getenv("DPPO_SAMPLER_CFG");
@@ -486,13 +404,10 @@ static char sampler_cfg() {
     return c;
 }
 
-template <class P, int NT16, int NO, int KSI, bool INJ>
+template <class P, int NT16, int NO, int KSI, bool INJ>   // NT16: n-tiles per wave of a 16-wave layout
 static int launch_sample_k(const SampleArgs& a, hipStream_t s) {
-    if constexpr (P::KG == 32 && NT16 == 2) {   // 2-byte operands, H = 512
-        return launch_sample_q<P, 4, NO, KSI, INJ, 3, 8, 2, 0, 3>(a, s);
-    } else {
-        return launch_sample_q<P, NT16, NO, KSI, INJ, 3, 16, 0, 0, 0>(a, s);
-    }
+    constexpr StreamGeom g = stream_geom(P::KG == 32, NT16 * 256);
+    return launch_sample_q<P, NT16 * 16 / g.SW, NO, KSI, INJ, g.QD, g.SW, g.RK, g.RES>(a, s);
 }
 
 template <class P, int NT, int NO, int KSI>
@@ -518,13 +433,6 @@ static int dispatch_sample(const SampleArgs& a, hipStream_t s) {
                           a.H, a.XD, KSI);
 }
 
-// the geometry launch_sample_k picks, for dppo_sampler_stream_bytes
-struct SamplerGeom { int SW, RK, LK, RIO; };
-static SamplerGeom sampler_geom(int precision, int H) {
-    if (dppo_prec_2b(precision) && H == 512) return {8, 2, 0, 3};
-    return {16, 0, 0, 0};
-}
-
 extern "C" int dppo_sampler_stream_bytes(const dppo_dims* d, int precision, int64_t* bytes_per_tile, int* waves) {
     Dims D;
     int rc = dppo_check_dims(d, &D);
@@ -532,47 +440,35 @@ extern "C" int dppo_sampler_stream_bytes(const dppo_dims* d, int precision, int6
     DPPO_CHECK(bytes_per_tile, "dppo_sampler_stream_bytes: null output");
     DPPO_CHECK(dppo_prec_ok(precision), "dppo_sampler_stream_bytes: bad precision %d", precision);
     const MlpLayout L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
-    const SamplerGeom g = sampler_geom(precision, D.H);
+    const StreamGeom& g = stream_geom(dppo_prec_2b(precision), D.H);
     const int64_t ntot = D.H / 16, no = dppo_cdiv(D.XD, 16);
     const int64_t in_f = (int64_t)L.ks_in * ntot, out_f = (int64_t)L.ks_h * no;
-    const int64_t rin = (g.RIO & 1) ? in_f : 0, rout = (g.RIO & 2) ? out_f : 0;
-    const int64_t per_step = (in_f - rin) + 2 * (L.ks_h - g.RK - g.LK) * ntot + (out_f - rout);
-    const int64_t resident = rin + rout + 2 * (int64_t)(g.RK + g.LK) * ntot;
+    const int64_t rio = g.RES ? in_f + out_f : 0;
+    const int64_t per_step = in_f + out_f - rio + 2 * (L.ks_h - g.RK) * ntot;
+    const int64_t resident = rio + 2 * (int64_t)g.RK * ntot;
     const int actors = (D.KF > 0 && D.KF < D.K) ? 2 : 1;        // the resident set is reloaded at the switch
     *bytes_per_tile = ((int64_t)D.K * per_step + actors * resident) * 1024;
     if (waves) *waves = g.SW;
     return DPPO_OK;
 }
 
-static int sample_impl(const dppo_dims* d, int precision, const void* packed_base, const void* packed_ft,
-                       const float* sched, const float* cond, int n_envs, const float* x_T, const float* noise,
-                       uint64_t seed, uint64_t call_id, int env_offset, int deterministic,
-                       float min_sampling_std, float randn_clip, float final_clip,
-                       float* actions, float* chains, float* cond_out, float* actions_host, void* stream,
-                       const uint32_t* go = nullptr, uint32_t go_value = 0, uint32_t* done = nullptr,
-                       const uint64_t* cond_tagged = nullptr, uint32_t cond_tag = 0,
-                       uint64_t* actions_tagged = nullptr) {
+// The one launch path: `a` carries the caller's pointers and scalars (fields it does not use are
+// zero); the dimension fields and the layout are filled here, tables an optimizer step deferred are
+// refreshed, and the split kernel or the streaming kernel is chosen.
+static int sample_impl(const dppo_dims* d, int precision, SampleArgs a, void* stream) {
     Dims D;
     int rc = dppo_check_dims(d, &D);
     if (rc) return rc;
-    DPPO_CHECK(n_envs >= 0, "dppo_sample: n_envs < 0");
+    DPPO_CHECK(a.E >= 0, "dppo_sample: n_envs < 0");
     DPPO_CHECK(dppo_prec_ok(precision), "dppo_sample: bad precision %d", precision);
-    if (n_envs == 0) return DPPO_OK;
-    DPPO_CHECK(packed_base && packed_ft && sched && (cond || cond_tagged) && actions, "dppo_sample: null pointer argument");
+    if (a.E == 0) return DPPO_OK;
+    DPPO_CHECK(a.packed_base && a.packed_ft && a.sched && (a.cond || a.cond_tagged) && a.actions,
+               "dppo_sample: null pointer argument");
     // tables an optimizer step deferred (DPPO_STEP_DEFER_SAMPLER_TABLES) are re-derived first, on this stream
-    rc = dppo_refresh_sampler_tables(packed_ft, stream);
+    rc = dppo_refresh_sampler_tables(a.packed_ft, stream);
     if (rc) return rc;
-    rc = dppo_refresh_sampler_tables(packed_base, stream);
+    rc = dppo_refresh_sampler_tables(a.packed_base, stream);
     if (rc) return rc;
-    SampleArgs a;
-    a.packed_base = (const uint8_t*)packed_base;
-    a.packed_ft = (const uint8_t*)packed_ft;
-    a.sched = sched; a.cond = cond; a.x_T = x_T; a.noise = noise; a.actions = actions; a.chains = chains;
-    a.cond_out = cond_out; a.actions_host = actions_host;
-    a.go = go; a.go_value = go_value; a.done = done;
-    a.cond_tagged = cond_tagged; a.cond_tag = cond_tag; a.actions_tagged = actions_tagged;
-    a.seed = seed; a.call_id = (uint32_t)call_id; a.E = n_envs; a.env_offset = env_offset;
-    a.deterministic = deterministic; a.min_std = min_sampling_std; a.randn_clip = randn_clip; a.final_clip = final_clip;
     a.XD = D.XD; a.SD = D.SD; a.TD = D.TD; a.H = D.H; a.K = D.K; a.KF = D.KF; a.IN = D.IN;
     a.L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
     hipStream_t s = (hipStream_t)stream;
@@ -584,52 +480,48 @@ static int sample_impl(const dppo_dims* d, int precision, const void* packed_bas
          : precision == DPPO_F16  ? dispatch_sample<PolicyF16>(a, s) : dispatch_sample<PolicyF32>(a, s);
 }
 
-extern "C" int dppo_sampler_layout(const dppo_dims* d, int precision, int n_envs, int* members) {
+// the three plan queries: dims checked and the split kernel's plan looked up once ({0, ...} under
+// DPPO_SAMPLER_CFG=r)
+static int plan_query(const dppo_dims* d, int precision, int n_envs, const void* out, const char* who, SplitPlan* plan) {
     Dims D;
     int rc = dppo_check_dims(d, &D);
     if (rc) return rc;
-    DPPO_CHECK(members, "dppo_sampler_layout: null output");
-    const MlpLayout L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
-    *members = sampler_cfg() == 'x' ? split_members_for(precision, D.H, D.XD, D.SD, L.ks_in, n_envs, D.K, D.KF) : 0;
+    DPPO_CHECK(out, "%s: null output", who);
+    *plan = sampler_cfg() == 'x' ? split_plan(precision, D.H, D.XD, D.SD, n_envs, D.K, D.KF) : SplitPlan{};
+    return DPPO_OK;
+}
+
+extern "C" int dppo_sampler_layout(const dppo_dims* d, int precision, int n_envs, int* members) {
+    SplitPlan p;
+    int rc = plan_query(d, precision, n_envs, members, "dppo_sampler_layout", &p);
+    if (rc) return rc;
+    *members = p.P * (p.dual ? 2 : 1);
     return DPPO_OK;
 }
 
 // The split kernel's members wait on each other inside a launch, so every active workgroup of a
 // launch must be resident at once; a second launch in flight (the pipelined rollout's next step)
-// must not take the CUs the first one still needs. One workgroup per CU (register budget), G * P
-// active workgroups per launch. The streaming kernel has no inter-workgroup wait.
+// must not take the CUs the first one still needs. One workgroup per CU (register budget), the plan's
+// workgroups active per launch. The streaming kernel has no inter-workgroup wait.
 extern "C" int dppo_sampler_max_in_flight(const dppo_dims* d, int precision, int n_envs, int* launches) {
-    int members = 0;
-    int rc = dppo_sampler_layout(d, precision, n_envs, &members);
+    SplitPlan p;
+    int rc = plan_query(d, precision, n_envs, launches, "dppo_sampler_max_in_flight", &p);
     if (rc) return rc;
-    DPPO_CHECK(launches, "dppo_sampler_max_in_flight: null output");
-    if (members == 0 || n_envs <= 0) {
-        *launches = 8;
-        return DPPO_OK;
-    }
-    Dims D;
-    dppo_check_dims(d, &D);
-    const MlpLayout L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
-    int plan[4];
-    split_plan_query(precision, D.H, D.XD, D.SD, L.ks_in, n_envs, D.K, D.KF, plan);
-    // the launch's own workgroup count (rounded as the launch rounds it), one per CU
-    const int active = plan[3] > 0 ? plan[3] : dppo_cdiv(n_envs, 16) * members, cus = sampler_device_cus();
-    *launches = cus > 0 ? (cus / active > 0 ? cus / active : 1) : 1;
+    if (p.P == 0) *launches = 8;
+    else *launches = p.cus > 0 ? (p.cus / p.blocks > 0 ? p.cus / p.blocks : 1) : 1;
     return DPPO_OK;
 }
 
+// plan[4] = kernel (0 weight streaming, 2 folded split; 1 and 3, the removed 8-member and pair
+// kernels, are no longer returned), members P per set, member sets, workgroups per launch
 extern "C" int dppo_sampler_plan(const dppo_dims* d, int precision, int n_envs, int* plan) {
-    Dims D;
-    int rc = dppo_check_dims(d, &D);
+    SplitPlan p;
+    int rc = plan_query(d, precision, n_envs, plan, "dppo_sampler_plan", &p);
     if (rc) return rc;
-    DPPO_CHECK(plan, "dppo_sampler_plan: null output");
-    const MlpLayout L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
-    if (sampler_cfg() == 'x') {
-        split_plan_query(precision, D.H, D.XD, D.SD, L.ks_in, n_envs, D.K, D.KF, plan);
-    } else {
-        plan[0] = plan[1] = plan[2] = plan[3] = 0;
-    }
-    if (plan[0] == 0) plan[3] = dppo_cdiv(n_envs, 16);
+    plan[0] = p.P ? 2 : 0;
+    plan[1] = p.P;
+    plan[2] = p.P ? (p.dual ? 2 : 1) : 0;
+    plan[3] = p.P ? p.blocks : dppo_cdiv(n_envs, 16);
     return DPPO_OK;
 }
 
@@ -638,36 +530,12 @@ extern "C" int dppo_sample(const dppo_dims* d, int precision, const void* packed
                            uint64_t seed, uint64_t call_id, int env_offset, int deterministic,
                            float min_sampling_std, float randn_clip, float final_clip,
                            float* actions, float* chains, void* stream) {
-    return sample_impl(d, precision, packed_base, packed_ft, sched, cond, n_envs, x_T, noise, seed, call_id, env_offset,
-                       deterministic, min_sampling_std, randn_clip, final_clip, actions, chains, nullptr, nullptr,
+    return sample_impl(d, precision,
+                       {.packed_base = (const uint8_t*)packed_base, .packed_ft = (const uint8_t*)packed_ft, .sched = sched,
+                        .cond = cond, .x_T = x_T, .noise = noise, .actions = actions, .chains = chains, .seed = seed,
+                        .call_id = (uint32_t)call_id, .E = n_envs, .env_offset = env_offset, .deterministic = deterministic,
+                        .min_std = min_sampling_std, .randn_clip = randn_clip, .final_clip = final_clip},
                        stream);
-}
-
-// device address of pinned host memory (a cache: the rollout reuses the same staging buffers and
-// counters every step); null if the memory is not mapped. One process-wide table under a mutex: a
-// mapped pinned allocation has one device address for every device (unified addressing), so the
-// entry does not depend on the calling thread or its current device; entries are never freed
-// (dropping one only costs a hipHostGetDevicePointer), so no eviction waits on a device.
-static void* mapped_ptr(const void* host) {
-    constexpr int N = 32;
-    static std::mutex mu;
-    static const void* keys[N] = {};
-    static void* vals[N] = {};
-    static int next = 0;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        for (int i = 0; i < N; ++i)
-            if (keys[i] == host && vals[i]) return vals[i];
-    }
-    void* dev = nullptr;
-    if (hipHostGetDevicePointer(&dev, const_cast<void*>(host), 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    std::lock_guard<std::mutex> lk(mu);
-    keys[next] = host; vals[next] = dev;
-    next = (next + 1) % N;
-    return dev;
 }
 
 // One rollout step's device work in one call (train_ppo_diffusion_agent.py:106-122): the sampler
@@ -689,9 +557,13 @@ extern "C" int dppo_sample_step(const dppo_dims* d, int precision, const void* p
     const float* cond_dev_view = (const float*)mapped_ptr(cond_host);
     float* act_dev_view = (float*)mapped_ptr(actions_host);
     if (cond_dev_view && act_dev_view) {
-        rc = sample_impl(d, precision, packed_base, packed_ft, sched, cond_dev_view, n_envs, nullptr, nullptr, seed,
-                         call_id, env_offset, deterministic, min_sampling_std, randn_clip, final_clip, actions, chains,
-                         cond, act_dev_view, stream);
+        rc = sample_impl(d, precision,
+                         {.packed_base = (const uint8_t*)packed_base, .packed_ft = (const uint8_t*)packed_ft, .sched = sched,
+                          .cond = cond_dev_view, .actions = actions, .chains = chains, .cond_out = cond,
+                          .actions_host = act_dev_view, .seed = seed, .call_id = (uint32_t)call_id, .E = n_envs,
+                          .env_offset = env_offset, .deterministic = deterministic, .min_std = min_sampling_std,
+                          .randn_clip = randn_clip, .final_clip = final_clip},
+                         stream);
         if (rc) return rc;
     } else {
         DPPO_HIP(hipMemcpyAsync(cond, cond_host, sizeof(float) * (size_t)n_envs * D.SD, hipMemcpyHostToDevice, s));
@@ -705,61 +577,6 @@ extern "C" int dppo_sample_step(const dppo_dims* d, int precision, const void* p
 }
 
 // ---- pipelined rollout steps (see include/dppo.h) ----
-extern "C" int dppo_host_alloc(size_t bytes, void** ptr) {
-    DPPO_CHECK(ptr && bytes > 0, "dppo_host_alloc: bad arguments");
-    DPPO_HIP(hipHostMalloc(ptr, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    memset(*ptr, 0, bytes);
-    return DPPO_OK;
-}
-
-// Up to 4 host-mapped -> device copies in ONE kernel launch (the rollout's reward / termination /
-// first flags into the update's device buffers). hipMemcpyAsync of the same pinned buffers went through
-// the SDMA path, where the second and third copies started ~0.9 ms after they were issued with the
-// device idle (r03 HIP trace: rollout -> update gap 1.2-2.1 ms per iteration); a kernel reading the
-// coherent mapped memory over the bus runs as soon as the stream reaches it.
-struct HostCopies { const uint8_t* src[4]; uint8_t* dst[4]; size_t n[4]; };
-__global__ __launch_bounds__(256) void copy_host_kernel(HostCopies c) {
-    const size_t stride = (size_t)gridDim.x * 256, t0 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    for (int r = 0; r < 4; ++r) {
-        if (!c.n[r]) continue;
-        const uint8_t* s = c.src[r];
-        uint8_t* d = c.dst[r];
-        const size_t n = c.n[r];
-        if ((((uintptr_t)s | (uintptr_t)d) & 15) == 0) {
-            const size_t n16 = n / 16;
-            for (size_t i = t0; i < n16; i += stride) ((uint4*)d)[i] = ((const uint4*)s)[i];
-            for (size_t i = 16 * n16 + t0; i < n; i += stride) d[i] = s[i];
-        } else {
-            for (size_t i = t0; i < n; i += stride) d[i] = s[i];
-        }
-    }
-}
-
-extern "C" int dppo_copy_from_host(int n, void* const* dst, const void* const* src_host, const size_t* bytes, void* stream) {
-    DPPO_CHECK(n >= 0 && n <= 4 && (n == 0 || (dst && src_host && bytes)), "dppo_copy_from_host: bad arguments");
-    HostCopies c = {};
-    size_t total = 0;
-    for (int i = 0; i < n; ++i) {
-        DPPO_CHECK(bytes[i] == 0 || (dst[i] && src_host[i]), "dppo_copy_from_host: null range %d", i);
-        c.src[i] = (const uint8_t*)mapped_ptr(src_host[i]);
-        DPPO_CHECK(bytes[i] == 0 || c.src[i], "dppo_copy_from_host: source %d is not mapped host memory (dppo_host_alloc)", i);
-        c.dst[i] = (uint8_t*)dst[i];
-        c.n[i] = bytes[i];
-        total += bytes[i];
-    }
-    if (total == 0) return DPPO_OK;
-    const size_t blocks = (total / 16 + 255) / 256;
-    hipLaunchKernelGGL(copy_host_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks))), dim3(256), 0,
-                       (hipStream_t)stream, c);
-    DPPO_HIP(hipGetLastError());
-    return DPPO_OK;
-}
-
-extern "C" int dppo_host_free(void* ptr) {
-    if (ptr) DPPO_HIP(hipHostFree(ptr));
-    return DPPO_OK;
-}
-
 extern "C" int dppo_rollout_enqueue(const dppo_dims* d, int precision, const void* packed_base, const void* packed_ft,
                                     const float* sched, const float* cond_host, float* cond, int n_envs, uint64_t seed,
                                     uint64_t call_id, int env_offset, int deterministic, float min_sampling_std,
@@ -772,9 +589,13 @@ extern "C" int dppo_rollout_enqueue(const dppo_dims* d, int precision, const voi
     uint32_t* done_dev = (uint32_t*)mapped_ptr(done);
     DPPO_CHECK(cond_dev && act_dev && go_dev && done_dev,
                "dppo_rollout_enqueue: staging buffers must come from dppo_host_alloc (mapped, coherent)");
-    return sample_impl(d, precision, packed_base, packed_ft, sched, cond_dev, n_envs, nullptr, nullptr, seed, call_id,
-                       env_offset, deterministic, min_sampling_std, randn_clip, final_clip, actions, chains, cond,
-                       act_dev, stream, go_dev, go_value, done_dev);
+    return sample_impl(d, precision,
+                       {.packed_base = (const uint8_t*)packed_base, .packed_ft = (const uint8_t*)packed_ft, .sched = sched,
+                        .cond = cond_dev, .actions = actions, .chains = chains, .cond_out = cond, .actions_host = act_dev,
+                        .go = go_dev, .go_value = go_value, .done = done_dev, .seed = seed, .call_id = (uint32_t)call_id,
+                        .E = n_envs, .env_offset = env_offset, .deterministic = deterministic,
+                        .min_std = min_sampling_std, .randn_clip = randn_clip, .final_clip = final_clip},
+                       stream);
 }
 
 extern "C" int dppo_rollout_enqueue_tagged(const dppo_dims* d, int precision, const void* packed_base,
@@ -791,7 +612,12 @@ extern "C" int dppo_rollout_enqueue_tagged(const dppo_dims* d, int precision, co
     uint32_t* done_dev = (uint32_t*)mapped_ptr(done);
     DPPO_CHECK(obs_dev && act_dev && done_dev,
                "dppo_rollout_enqueue_tagged: staging buffers must come from dppo_host_alloc (mapped, coherent)");
-    return sample_impl(d, precision, packed_base, packed_ft, sched, nullptr, n_envs, nullptr, nullptr, seed, call_id,
-                       env_offset, deterministic, min_sampling_std, randn_clip, final_clip, actions, chains, cond,
-                       nullptr, stream, nullptr, 0, done_dev, obs_dev, tag, act_dev);
+    return sample_impl(d, precision,
+                       {.packed_base = (const uint8_t*)packed_base, .packed_ft = (const uint8_t*)packed_ft, .sched = sched,
+                        .actions = actions, .chains = chains, .cond_out = cond, .actions_tagged = act_dev,
+                        .done = done_dev, .cond_tagged = obs_dev, .cond_tag = tag, .seed = seed,
+                        .call_id = (uint32_t)call_id, .E = n_envs, .env_offset = env_offset,
+                        .deterministic = deterministic, .min_std = min_sampling_std, .randn_clip = randn_clip,
+                        .final_clip = final_clip},
+                       stream);
 }

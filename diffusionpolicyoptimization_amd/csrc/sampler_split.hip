@@ -204,7 +204,7 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
     constexpr int NB = H + NOC;            // per-actor bias floats: b_l1 | B_OUT2
     // TIN rows in LDS: all K (hopper's KX = 1), or a 2-row ring refilled one step ahead by LDS-DMA
     // (KX = 2, walker2d / halfcheetah: the K rows' 40 KB on top of the 2-k-step in-Dense fragments
-    // would exceed the CU's 160 KB, split4_lds_bytes)
+    // would exceed the CU's 160 KB, split_lds_total)
     constexpr bool TRING = KX == 2 || !TWO;
 
     const SampleArgs& a = sa.a;
@@ -225,20 +225,13 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
     const int KSX = packed_ksteps(XD + SD, KGP);  // k-step stride of the W_XS image
     const int i0 = sa.dual && set == 1 ? K - KF : 0, i1 = sa.dual && set == 0 ? K - KF : K;   // steps of this set
 
-    // ---- LDS carve (all offsets multiples of 16 B) ----
+    // ---- LDS carve (SPLIT_LDS_REGIONS, dppo_sampler.h: all offsets multiples of 16 B) ----
+    constexpr size_t ESZ = sizeof(AT);
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     size_t o = 0;
-    AT* a0 = (AT*)(smem + o); o += dppo_align16(sizeof(AT) * 16 * lda0);
-    AT* u1 = (AT*)(smem + o); o += dppo_align16(sizeof(AT) * 16 * ldh);
-    float* part = (float*)(smem + o); o += dppo_align16(4 * SW * NV);      // [wave][16 x XD]
-    int* xfail = (int*)(smem + o); o += 16;                // [0] exchange failure, [1] exchange mode
-    float* xs = (float*)(smem + o); o += dppo_align16(4 * 16 * XD);
-    float* st = (float*)(smem + o); o += dppo_align16(4 * 16 * SD);
-    float* tin = (float*)(smem + o); o += dppo_align16(4 * (TRING ? 2 : K) * H);
-    float* sch = (float*)(smem + o); o += dppo_align16(4 * K * DPPO_SCHED_COLS);
-    float* bias = (float*)(smem + o); o += dppo_align16(4 * 2 * NB);
-    float* zt = (float*)(smem + o); o += dppo_align16(4 * K * 16 * XD);
-    u32x4* wxs = (u32x4*)(smem + o); o += (size_t)SW * NTI * KX * 1024;   // [wave][n][ks] in-Dense fragments
+#define DPPO_CARVE(T, name, bytes) T* name = (T*)(smem + o); o += bytes;
+    SPLIT_LDS_REGIONS(DPPO_CARVE)
+#undef DPPO_CARVE
     // TRING: row t of the actor that runs it (fine-tuned below K'), as 2 KB of LDS-DMA by waves 0 and 1
     // (lane l's 16 B at slot + 16 l); waited for by the issuing wave's vmcnt(0) and published by a barrier
     auto tin_dma = [&](int tr, int slot) {
@@ -333,17 +326,16 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
         }
     }
     // per-step epilogue constants [i][c0 c1 c2 c3 sd]: schedule row t = K-1-i and the noise rule
-    // (include/dppo.h: eval DDPM t = 0 or any DDIM row -> 0; other DDPM rows clip at 1e-3; train:
-    // min_std; diffusion_vpg.py:303-315)
+    // (sampler_noise_std)
     for (int i = tid; i < K; i += ST) {
         const float* sc = a.sched + (K - 1 - i) * DPPO_SCHED_COLS;
-        float sd = expf(0.5f * sc[4]);
-        if (a.deterministic && sc[6] != 0.f) sd = 0.f;
-        else if (a.deterministic) sd = fminf(fmaxf(sd, sc[5]), 1e6f);
-        else sd = fminf(fmaxf(sd, a.min_std), 1e6f);
+        const float sd = sampler_noise_std(a, sc);
         float* e = sch + i * DPPO_SCHED_COLS;
         e[0] = sc[0]; e[1] = sc[1]; e[2] = sc[2]; e[3] = sc[3]; e[4] = sd;
     }
+    // the noise / x_T draws: this kernel's own copy of sampler_draw_noise (dppo_sampler.h), kept because
+    // calling the helper moved this kernel's register allocation; chain row 0 goes out through store_out
+    // from member 0
     const int XG = (XD + 3) / 4;
     for (int it = tid; it < (K + 1) * 16 * XG; it += ST) {
         const int step = it / (16 * XG), r = (it / XG) % 16, gq = it % XG, row = row0 + r;
@@ -409,20 +401,7 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
             if (a.cond_out && c == 0 && row < a.E) store_out(a.cond_out + (size_t)row * SD + cc, st[i]);
         }
     } else {
-        if (a.go) {
-            if (tid == 0) {
-                const uint64_t t_end = __builtin_amdgcn_s_memrealtime() + 400000000ull;   // 100 MHz: 4 s
-                while (__hip_atomic_load(a.go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < a.go_value) {
-                    __builtin_amdgcn_s_sleep(8);
-                    if (__builtin_amdgcn_s_memrealtime() > t_end) {
-                        if (c == 0) __hip_atomic_fetch_or(a.done, 0x80000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        break;
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");    // one system acquire after the match
-            }
-            __syncthreads();
-        }
+        if (a.go) sampler_wait_go(a, c == 0, tid);
         XPHASE(8);
         for (int i = tid; i < 16 * SD; i += ST) {
             const int r = i / SD, cc = i % SD, row = row0 + r;
@@ -781,24 +760,6 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
     XPHASE(10);
 }
 
-size_t split4_lds_bytes(int XD, int SD, int K, int KX, int NO, int sw, int esz = 2) {
-    const int pad = 16, ldh = SPLIT_H + pad, lda0 = KX * (esz == 2 ? 32 : 16) + pad;
-    size_t o = 0;
-    o += dppo_align16((size_t)esz * 16 * lda0);
-    o += dppo_align16((size_t)esz * 16 * ldh);
-    o += dppo_align16(4 * sw * 16 * XD);
-    o += 16;
-    o += dppo_align16(4 * 16 * XD);
-    o += dppo_align16(4 * 16 * SD);
-    o += dppo_align16(4 * ((KX == 2 || esz == 4) ? 2 : K) * SPLIT_H);   // TIN: all K rows, or the 2-row ring (TRING)
-    o += dppo_align16(4 * K * DPPO_SCHED_COLS);
-    o += dppo_align16(4 * 2 * (SPLIT_H + 16 * NO));
-    o += dppo_align16(4 * K * 16 * XD);
-    o += (size_t)32 * KX * 1024;                  // sw waves x 32/sw n-tiles x KX k-steps
-    (void)NO; (void)sw;
-    return o;
-}
-
 __global__ void xchg_zero_kernel(uint64_t* p, size_t n) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         __hip_atomic_store(p + i, (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -933,14 +894,13 @@ constexpr int S4_WAVES = 8;
 
 template <class Pol, int XQ, int KX, bool INJ, int SWV, int PM>
 int launch_split4_kw(const SplitArgs& sa, hipStream_t s) {
-    constexpr int NO = (4 * XQ + 15) / 16;
     // the finishing lanes are the members' lanes: a wave's 16 x XD / SWV coordinates in (64 / PM)
     // slots at most PM deep
     constexpr int NVW = 16 * 4 * XQ / SWV, KW = (NVW + 64 / PM - 1) / (64 / PM);
     static_assert(KW <= PM, "the waves of a member do not cover XD");
     auto k = sample_split4_kernel<Pol, XQ, KX, INJ, SWV, PM>;
     const SampleArgs& a = sa.a;
-    const size_t lds = split4_lds_bytes(a.XD, a.SD, a.K, KX, NO, SWV, (int)sizeof(typename Pol::AT));
+    const size_t lds = split_lds_total(sizeof(typename Pol::AT), KX, a.XD, a.SD, a.K, SWV);
     if (lds > 160 * 1024) return dppo_set_error(DPPO_EUNSUPPORTED, "split sampler needs %zu B of LDS", lds);
     { const int rc_ = dppo_func_lds((const void*)k, (size_t)lds); if (rc_) return rc_; }
     const int blocks = 8 * PM * ((sa.G + 7) / 8) * (sa.dual ? 2 : 1);
@@ -962,58 +922,32 @@ int launch_split4_k(const SplitArgs& sa, hipStream_t s) {
     return launch_split4_kw<Pol, XQ, KX, INJ, S4_WAVES, S4_P>(sa, s);
 }
 
-// the split sampler's plan for a shape: P members per 16-env group (2 for 2-byte operands, 4 for fp32;
-// 0 = not taken: the weight-streaming sampler, sampler.hip), whether the two actors run on two member
-// sets (dual), blocks = workgroups of one launch. (r06: the r01 8-member kernel and the r03 pair kernel,
-// both measured slower than this one, were removed; walker2d / halfcheetah run it since their TIN ring.)
-struct SplitPlan { int P; bool dual; int blocks; };
+}  // namespace
 
+// the split sampler's plan for a shape (SplitPlan, dppo_sampler.h). (r06: the r01 8-member kernel and the
+// r03 pair kernel, both measured slower than this one, were removed; walker2d / halfcheetah run it since
+// their TIN ring.)
 SplitPlan split_plan(int precision, int H, int XD, int SD, int E, int K, int KF) {
     // fp32 (r06): the folded kernel at P = F32_P members (an fp32 l1 eighth on 4 waves is 128 VGPRs of
     // fragments per lane), for the instantiated width XD = 12 (hopper; other fp32 shapes stream
     // the weights, sampler.hip)
     const bool f32 = precision == DPPO_F32;
     if ((!dppo_prec_2b(precision) && !(f32 && XD == 12)) || H != SPLIT_H || XD % 4 != 0 || XD > 32 || K > 62)
-        return {0, false, 0};
+        return {0, false, 0, 0};
     const int G = dppo_cdiv(E, 16);
-    if (G < 1 || G > XMAX_G) return {0, false, 0};
     const int cus = device_cus();
+    if (G < 1 || G > XMAX_G) return {0, false, 0, cus};
     const int P = f32 ? F32_P : S4_P;   // members per group
     const int KX = dppo_cdiv(XD + SD, f32 ? 16 : 32);
     // every workgroup of the launch co-resident (one per CU: the register budget)
-    if (KX > 2 || split4_lds_bytes(XD, SD, K, KX, dppo_cdiv(XD, 16), f32 ? F32_WAVES : S4_WAVES, f32 ? 4 : 2) > 160 * 1024 ||
+    if (KX > 2 || split_lds_total(f32 ? 4 : 2, KX, XD, SD, K, f32 ? F32_WAVES : S4_WAVES) > 160 * 1024 ||
         (cus && 8 * P * ((G + 7) / 8) > cus))
-        return {0, false, 0};
+        return {0, false, 0, cus};
     // two member sets (one per actor) only while two launches of them still fit side by side (the
     // pipelined rollout keeps the next step's launch resident while this one runs)
     const bool dual = KF > 0 && KF < K && (cus == 0 || 2 * 2 * 8 * P * ((G + 7) / 8) <= cus);
-    return {P, dual, 8 * P * ((G + 7) / 8) * (dual ? 2 : 1)};
+    return {P, dual, 8 * P * ((G + 7) / 8) * (dual ? 2 : 1), cus};
 }
-
-}  // namespace
-
-int split_members_for(int precision, int H, int XD, int SD, int ks_in, int E, int K, int KF) {
-    (void)ks_in;
-    const SplitPlan p = split_plan(precision, H, XD, SD, E, K, KF);
-    return p.P * (p.dual ? 2 : 1);
-}
-
-// dppo_sampler_plan's fields: kernel (0 weight streaming, 2 folded split; 1 and 3, the removed 8-member
-// and pair kernels, are no longer returned), members P per set, member sets, workgroups per launch
-void split_plan_query(int precision, int H, int XD, int SD, int ks_in, int E, int K, int KF, int* out) {
-    (void)ks_in;
-    const SplitPlan p = split_plan(precision, H, XD, SD, E, K, KF);
-    out[0] = p.P == 0 ? 0 : 2;
-    out[1] = p.P;
-    out[2] = p.P ? (p.dual ? 2 : 1) : 0;
-    out[3] = p.blocks;
-}
-
-bool sample_split_supported(int precision, int H, int XD, int SD, int ks_in, int E, int K, int KF) {
-    return split_members_for(precision, H, XD, SD, ks_in, E, K, KF) > 0;
-}
-
-int sampler_device_cus() { return device_cus(); }
 
 int launch_sample_split(const SampleArgs& a, int precision, hipStream_t s) {
     const SplitPlan plan = split_plan(precision, a.H, a.XD, a.SD, a.E, a.K, a.KF);

@@ -263,11 +263,9 @@ class MappedDoubles:
     host reads as a numpy array (the PPO metric sums of dppo_optimizer_step)."""
 
     def __init__(self, n):
-        p = ctypes.c_void_p()
-        _lib.call("dppo_host_alloc", ctypes.c_size_t(8 * n), ctypes.byref(p))
-        self.address = p.value
-        self.array = np.ctypeslib.as_array((ctypes.c_double * n).from_address(self.address))
-        self.array[:] = 0.0
+        block = _HostBlock(8 * n)           # zeroed by dppo_host_alloc; the array's base holds the block
+        self.address = block.address
+        self.array = block.view().view(np.float64)
 
     def wait_tag(self, index, tag, timeout_s=30.0):
         """Spin until array[index] == tag (a tag the device stores after the data it guards)."""
@@ -278,11 +276,6 @@ class MappedDoubles:
         while a[index] != tag:
             if time.perf_counter() > t_end:
                 raise _lib.DppoError(f"mapped tag {tag} not seen within {timeout_s} s (found {a[index]})")
-
-    def __del__(self):
-        if getattr(self, "address", None) and _lib._lib is not None:
-            _lib.query("dppo_host_free", ctypes.c_void_p(self.address))
-            self.address = None
 
 
 def critic_packed_bytes(d: ModelDims, precision):
@@ -368,6 +361,29 @@ def sampler_plan(d: ModelDims, precision, n_envs):
     return dict(kernel=out[0], members=out[1], sets=out[2], workgroups=out[3])
 
 
+def _stream_ring(d, precision, E, dev):
+    """(torch streams, their handles) of a rollout's launches. Consecutive launches alternate over
+    DPPO_ROLLOUT_STREAMS streams (default 2): launch t+1 is dispatched, and runs its
+    observation-independent prologue (resident weights, noise), while launch t still runs, instead of
+    after it retires. begin() / end() order them against the caller's stream around a rollout. Two
+    launches in flight must both fit on the device (the split sampler's members wait for each other
+    inside a launch): above that size, one stream."""
+    nst = max(1, int(os.environ.get("DPPO_ROLLOUT_STREAMS", "2")))
+    nst = min(nst, sampler_max_in_flight(d, precision, E))
+    streams = [torch.cuda.current_stream(dev)] + [torch.cuda.Stream(device=dev) for _ in range(nst - 1)]
+    return streams, [ctypes.c_void_p(st.cuda_stream) for st in streams]
+
+
+def _step_args(m, dims, deterministic):
+    """A rollout step's model arguments in the C ABI's order: (dims, precision, images, schedule) and
+    (seed, call id, env offset, mode, min std, clips)."""
+    fc = m.final_action_clip_value
+    return ((ctypes.byref(dims), _prec(m.precision), ptr(m.packed_base), ptr(m.packed_ft), ptr(m.sched_for(deterministic))),
+            (ctypes.c_uint64(m.seed & (2 ** 64 - 1)), ctypes.c_uint64(m._call_id), m._env_offset,
+             int(bool(deterministic)), float(m.get_min_sampling_denoising_std()), float(m.randn_clip_value),
+             float(fc) if fc is not None else 0.0))
+
+
 class SampleStepper:
     """dppo_sample_step with every argument but the step index, call counter and mode bound once
     (the rollout's buffers never move), so a rollout step costs one ctypes call."""
@@ -389,30 +405,17 @@ class SampleStepper:
         self._obs0, self._obs_step = obs_traj.data_ptr(), E * d.sd * 4
         self._ch0, self._ch_step = chains_traj.data_ptr(), E * (d.ft_denoising_steps + 1) * d.xd * 4
         self._fixed = (ptr(cond_host), ptr(actions), ptr(actions_host))
-        # consecutive launches alternate over DPPO_ROLLOUT_STREAMS streams (default 2): launch t+1 is
-        # dispatched, and runs its observation-independent prologue (resident weights, noise), while
-        # launch t still runs, instead of after it retires. begin() / end() order them against the
-        # caller's stream around a rollout. Two launches in flight must both fit on the device (the
-        # split sampler's members wait for each other inside a launch): above that size, one stream.
-        nst = max(1, int(os.environ.get("DPPO_ROLLOUT_STREAMS", "2")))
-        nst = min(nst, sampler_max_in_flight(d, model.precision, E))
-        dev = obs_traj.device
-        self._tstreams = [torch.cuda.current_stream(dev)] + [torch.cuda.Stream(device=dev) for _ in range(nst - 1)]
-        self._handles = [ctypes.c_void_p(st.cuda_stream) for st in self._tstreams]
+        self._tstreams, self._handles = _stream_ring(d, model.precision, E, obs_traj.device)
         self._stream = self._handles[0]
 
     def __call__(self, i, deterministic=False):
         if not 0 <= i < self.S:
             raise IndexError(f"rollout step {i} outside [0, {self.S})")
         m = self.model
-        fc = m.final_action_clip_value
         cond_host, actions, actions_host = self._fixed
-        rc = self._fn(ctypes.byref(self._dims), _prec(m.precision), ptr(m.packed_base), ptr(m.packed_ft), ptr(m.sched_for(deterministic)),
-                      cond_host, ctypes.c_void_p(self._obs0 + i * self._obs_step), self.E,
-                      ctypes.c_uint64(m.seed & (2 ** 64 - 1)), ctypes.c_uint64(m._call_id), m._env_offset,
-                      int(bool(deterministic)), float(m.get_min_sampling_denoising_std()), float(m.randn_clip_value),
-                      float(fc) if fc is not None else 0.0, actions, actions_host,
-                      ctypes.c_void_p(self._ch0 + i * self._ch_step), 1, self._stream)
+        common, scalars = _step_args(m, self._dims, deterministic)
+        rc = self._fn(*common, cond_host, ctypes.c_void_p(self._obs0 + i * self._obs_step), self.E, *scalars,
+                      actions, actions_host, ctypes.c_void_p(self._ch0 + i * self._ch_step), 1, self._stream)
         if rc:
             raise _lib.DppoError(f"dppo_sample_step failed ({rc}): {_lib.load().dppo_last_error().decode()}")
         m._call_id += 1
@@ -437,23 +440,17 @@ class RolloutPipe:
         _check(actions, (E, d.xd), torch.float32, "actions")
         lib = _lib.load()
         self._lib, self.model, self.S, self.E = lib, model, S, E
-        self._bufs = []
-
-        def alloc(nbytes):
-            p = ctypes.c_void_p()
-            _lib.call("dppo_host_alloc", ctypes.c_size_t(nbytes), ctypes.byref(p))
-            self._bufs.append(p.value)
-            return p.value
-        po, pa, pc = alloc(4 * E * d.sd), alloc(4 * E * d.xd), alloc(256)
+        # the five staging blocks (observation, actions, counters, tagged observation, tagged actions)
+        self._blocks = [_HostBlock(n) for n in (4 * E * d.sd, 4 * E * d.xd, 256, 8 * E * d.sd, 8 * E * d.xd)]
+        po, pa, pc, pt, pat = (b.address for b in self._blocks)
         # the observation protocol: "tagged" (default: the observation is published as tagged
         # granules the launch polls itself, dppo_rollout_enqueue_tagged) or "go" (a go counter, then
         # the launch reads the float buffer); DPPO_ROLLOUT_PROTOCOL=go selects the latter
         self.protocol = os.environ.get("DPPO_ROLLOUT_PROTOCOL", "tagged")
         if self.protocol not in ("tagged", "go"):
             raise ValueError(f"DPPO_ROLLOUT_PROTOCOL must be 'tagged' or 'go', got {self.protocol!r}")
-        pt = alloc(8 * E * d.sd)
         self._obs_tag = np.ctypeslib.as_array((ctypes.c_uint64 * (E * d.sd)).from_address(pt))
-        pat = alloc(8 * E * d.xd)   # tagged actions (tagged protocol): the host polls the actions themselves
+        # tagged actions (tagged protocol): the host polls the actions themselves
         self._act_tag = np.ctypeslib.as_array((ctypes.c_uint64 * (E * d.xd)).from_address(pat))
         self.obs = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * (E * d.sd)).from_address(po))).view(E, d.sd)
         self.obs_mapped = MappedRef(po, 4 * E * d.sd)   # for copy_from_host
@@ -468,16 +465,7 @@ class RolloutPipe:
         self._obs0, self._obs_step = obs_traj.data_ptr(), E * d.sd * 4
         self._ch0, self._ch_step = chains_traj.data_ptr(), E * (d.ft_denoising_steps + 1) * d.xd * 4
         self._actions = ptr(actions)
-        # consecutive launches alternate over DPPO_ROLLOUT_STREAMS streams (default 2): launch t+1 is
-        # dispatched, and runs its observation-independent prologue (resident weights, noise), while
-        # launch t still runs, instead of after it retires. begin() / end() order them against the
-        # caller's stream around a rollout. Two launches in flight must both fit on the device (the
-        # split sampler's members wait for each other inside a launch): above that size, one stream.
-        nst = max(1, int(os.environ.get("DPPO_ROLLOUT_STREAMS", "2")))
-        nst = min(nst, sampler_max_in_flight(d, model.precision, E))
-        dev = obs_traj.device
-        self._tstreams = [torch.cuda.current_stream(dev)] + [torch.cuda.Stream(device=dev) for _ in range(nst - 1)]
-        self._handles = [ctypes.c_void_p(st.cuda_stream) for st in self._tstreams]
+        self._tstreams, self._handles = _stream_ring(d, model.precision, E, obs_traj.device)
         self._stream = self._handles[0]
         self.nwg = (E + 15) // 16
         self.enqueued = 0      # steps launched so far (step s waits for go >= s + 1)
@@ -488,16 +476,11 @@ class RolloutPipe:
         if not 0 <= i < self.S:
             raise IndexError(f"rollout step {i} outside [0, {self.S})")
         m = self.model
-        fc = m.final_action_clip_value
         p = self._p
         self._stream = self._handles[self.enqueued % len(self._handles)]
         self.enqueued += 1
-        common = (ctypes.byref(self._dims), _prec(m.precision), ptr(m.packed_base), ptr(m.packed_ft),
-                  ptr(m.sched_for(deterministic)))
-        tail = (self.E, ctypes.c_uint64(m.seed & (2 ** 64 - 1)), ctypes.c_uint64(m._call_id), m._env_offset,
-                int(bool(deterministic)), float(m.get_min_sampling_denoising_std()), float(m.randn_clip_value),
-                float(fc) if fc is not None else 0.0, self._actions, p["act"],
-                ctypes.c_void_p(self._ch0 + i * self._ch_step))
+        common, scalars = _step_args(m, self._dims, deterministic)
+        tail = (self.E, *scalars, self._actions, p["act"], ctypes.c_void_p(self._ch0 + i * self._ch_step))
         obs_dev = ctypes.c_void_p(self._obs0 + i * self._obs_step)
         if self.protocol == "tagged":   # step s waits for granules tagged s + 1 (= its publish count)
             tail_t = tail[:-2] + (p["act_tag"],) + tail[-1:]          # tagged actions replace actions_host
@@ -587,13 +570,11 @@ class RolloutPipe:
             st.synchronize()
         for h in self._handles:     # the split sampler's exchange buffers of these streams go back to the pool
             _lib.call("dppo_sampler_release_stream", h)
-        for b in self._bufs:
-            self._lib.dppo_host_free(ctypes.c_void_p(b))
-        self._bufs = []
+        self._blocks = []     # freed here unless a view still holds one (each block frees itself)
 
     def __del__(self):
         try:
-            if self._bufs:
+            if self._blocks:
                 self.close()
         except Exception:
             pass

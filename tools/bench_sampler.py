@@ -1,7 +1,8 @@
 """Times the K-step sampler alone on the bench workload (hopper, bf16, 64 envs): back-to-back
 launches bracketed by HIP events on the launch stream. Writes the actions of a fixed-seed call
-to gpurun_out/sampler_<tag>.npy so variants (DPPO_SAMPLER_QD) can be compared bit for bit.
-    python tools/bench_sampler.py [--envs 64] [--reps 200] [--tag qd3]"""
+to sampler_<tag>.npy in the output directory, so two builds of the library (DPPO_LIB names the one to
+load) can be compared bit for bit.
+    python tools/bench_sampler.py [--envs 64] [--reps 200] [--precision bf16] [--tag parent]"""
 import argparse
 import json
 import os

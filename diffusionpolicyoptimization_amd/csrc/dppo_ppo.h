@@ -138,5 +138,7 @@ struct CriticArgs {
 // mt 16-row MFMA tiles per row tile (2 = 32 rows, 4 = 64 rows) on `waves` waves
 struct ActorTilePlan { int mt, waves; };
 ActorTilePlan actor_tile_plan(int precision, int H, int XD, int64_t rows);
-int launch_actor_rowtile(const ActorArgs& a, int precision, hipStream_t s);
-int launch_critic_rowtile(const CriticArgs& a, int precision, hipStream_t s);
+// dry: only check that the launch has an instantiation (DPPO_EUNSUPPORTED with the dispatch's message
+// otherwise); nothing is launched and no device state is read or written
+int launch_actor_rowtile(const ActorArgs& a, int precision, hipStream_t s, bool dry = false);
+int launch_critic_rowtile(const CriticArgs& a, int precision, hipStream_t s, bool dry = false);

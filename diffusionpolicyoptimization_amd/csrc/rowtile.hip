@@ -773,8 +773,11 @@ static RowTileCfg row_tile_cfg() { return RowTileCfg{0, 1}; }
 // =============================================================================================
 // launchers
 // =============================================================================================
+// dry (every launcher below): run the instantiation's host checks only and launch nothing. The
+// entries of several launches (dppo_ppo_minibatch, dppo_pretrain_minibatch) ask first, so a geometry
+// without an instantiation is rejected before their outputs are zeroed
 template <class P, int MT, int NT, int NO, int KSI, bool TRAIN, int WAVES, bool O4>
-static int launch_actor_t(const ActorArgs& a, hipStream_t s) {
+static int launch_actor_t(const ActorArgs& a, hipStream_t s, bool dry) {
     if (a.L.ks_in != KSI || a.L.ks_h != ksh_for<P>(NT, WAVES) || a.L.ks_out_t != 2 || a.L.ks_h != WAVES * nok_for<P>(NT))
         return dppo_set_error(DPPO_EUNSUPPORTED, "actor row tile: layout does not match the instantiation");
     const ActorSmem<P, MT> S(a);
@@ -783,6 +786,7 @@ static int launch_actor_t(const ActorArgs& a, hipStream_t s) {
     const size_t tb_bytes = sizeof(typename P::AT) * 16 * MT * (a.H + pad);
     if (part_bytes > tb_bytes) return dppo_set_error(DPPO_EUNSUPPORTED, "actor: partial buffer does not fit");
     if (S.total > 160 * 1024) return dppo_set_error(DPPO_EUNSUPPORTED, "actor row tile needs %zu B LDS", S.total);
+    if (dry) return DPPO_OK;
     auto k = O4 ? actor_rowtile_kernel_o4<P, MT, NT, NO, KSI, TRAIN, WAVES> : actor_rowtile_kernel<P, MT, NT, NO, KSI, TRAIN, WAVES>;
     { const int rc_ = dppo_func_lds((const void*)k, (size_t)S.total); if (rc_) return rc_; }
     // TRAIN mode covers every row of the 64-padded feature-major images (padding rows get
@@ -798,18 +802,18 @@ static int launch_actor_t(const ActorArgs& a, hipStream_t s) {
 }
 
 template <class P, int MT, int NT, int NO, int KSI, int WAVES, bool O4>
-static int launch_actor_m(const ActorArgs& a, hipStream_t s) {
-    return (a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN) ? launch_actor_t<P, MT, NT, NO, KSI, true, WAVES, O4>(a, s)
-                                : launch_actor_t<P, MT, NT, NO, KSI, false, WAVES, O4>(a, s);
+static int launch_actor_m(const ActorArgs& a, hipStream_t s, bool dry) {
+    return (a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN) ? launch_actor_t<P, MT, NT, NO, KSI, true, WAVES, O4>(a, s, dry)
+                                : launch_actor_t<P, MT, NT, NO, KSI, false, WAVES, O4>(a, s, dry);
 }
 
 // bf16: 64-row tiles, 16 waves (half the weight stream per row of 32-row tiles; LDS-limited);
 // fp32: 32-row tiles, 16 waves
 template <class P, int MT, int WAVES, bool O4 = false>
-static int dispatch_actor(const ActorArgs& a, hipStream_t s) {
+static int dispatch_actor(const ActorArgs& a, hipStream_t s, bool dry) {
     const int NT = a.H / (16 * WAVES), NO = dppo_cdiv(a.XD, 16), KSI = a.L.ks_in;
 #define DPPO_ACTOR_CASE(nt, no, ksi) \
-    if (NT == nt && NO == no && KSI == ksi) return launch_actor_m<P, MT, nt, no, ksi, WAVES, O4>(a, s);
+    if (NT == nt && NO == no && KSI == ksi) return launch_actor_m<P, MT, nt, no, ksi, WAVES, O4>(a, s, dry);
     if constexpr (P::KG == 32 && WAVES == 16) {   // bf16, H = 512 on 16 waves
         DPPO_ACTOR_CASE(2, 1, 2) DPPO_ACTOR_CASE(2, 2, 2) DPPO_ACTOR_CASE(2, 1, 4) DPPO_ACTOR_CASE(2, 2, 4)
     } else if constexpr (P::KG == 32) {           // bf16, 8 waves: the in-layer is 2 k-steps up to 64 inputs, 4 up to 128
@@ -819,7 +823,8 @@ static int dispatch_actor(const ActorArgs& a, hipStream_t s) {
         DPPO_ACTOR_CASE(4, 1, 4) DPPO_ACTOR_CASE(4, 2, 4) DPPO_ACTOR_CASE(2, 1, 4) DPPO_ACTOR_CASE(2, 2, 4)
     }
 #undef DPPO_ACTOR_CASE
-    return dppo_set_error(DPPO_EUNSUPPORTED, "actor: hidden %d / chunk %d not instantiated", a.H, a.XD);
+    return dppo_set_error(DPPO_EUNSUPPORTED, "actor: hidden %d / chunk %d / in-layer k-steps %d not instantiated", a.H, a.XD,
+                          KSI);
 }
 
 static int64_t actor_device_cus() {
@@ -861,31 +866,32 @@ ActorTilePlan actor_tile_plan(int precision, int H, int XD, int64_t rows) {
 }
 
 template <class P2>
-static int launch_actor_2b(const ActorArgs& a, const ActorTilePlan& p, hipStream_t s) {
-    if (p.mt == 4 && p.waves == 16) return dispatch_actor<P2, 4, 16>(a, s);
-    if (p.mt == 2 && p.waves == 8) return dispatch_actor<P2, 2, 8>(a, s);
+static int launch_actor_2b(const ActorArgs& a, const ActorTilePlan& p, hipStream_t s, bool dry) {
+    if (p.mt == 4 && p.waves == 16) return dispatch_actor<P2, 4, 16>(a, s, dry);
+    if (p.mt == 2 && p.waves == 8) return dispatch_actor<P2, 2, 8>(a, s, dry);
     return dppo_set_error(DPPO_EUNSUPPORTED, "actor: no %d-row tile on %d waves", 16 * p.mt, p.waves);
 }
 
-int launch_actor_rowtile(const ActorArgs& a, int precision, hipStream_t s) {
+int launch_actor_rowtile(const ActorArgs& a, int precision, hipStream_t s, bool dry) {
     // TRAIN modes cover the 64-padded images (launch_actor_t), the others the rows given
     const int64_t rows = (a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN) ? (int64_t)a.ws.ldm : a.nrows;
     const ActorTilePlan p = actor_tile_plan(precision, a.H, a.XD, rows);
-    if (precision == DPPO_BF16) return launch_actor_2b<PolicyBF16>(a, p, s);
-    if (precision == DPPO_F16) return launch_actor_2b<PolicyF16>(a, p, s);
+    if (precision == DPPO_BF16) return launch_actor_2b<PolicyBF16>(a, p, s, dry);
+    if (precision == DPPO_F16) return launch_actor_2b<PolicyF16>(a, p, s, dry);
     if (p.mt != 2 || p.waves != 16)
         return dppo_set_error(DPPO_EUNSUPPORTED, "actor: no fp32 %d-row tile on %d waves", 16 * p.mt, p.waves);
-    return dispatch_actor<PolicyF32, 2, 16>(a, s);
+    return dispatch_actor<PolicyF32, 2, 16>(a, s, dry);
 }
 
 template <class P, int MT, int NT, bool TRAIN, int WAVES, bool O4>
-static int launch_critic_t(const CriticArgs& a, hipStream_t s) {
+static int launch_critic_t(const CriticArgs& a, hipStream_t s, bool dry) {
     if (a.L.ks_in != 2 || a.L.ks_h != ksh_for<P>(NT, WAVES) || a.L.ks_out_t != 2 || a.L.ks_h != WAVES * nok_for<P>(NT))
         return dppo_set_error(DPPO_EUNSUPPORTED, "critic row tile: layout does not match the instantiation");
     const CriticSmem<P, MT> S(a);
     if (S.total > 160 * 1024) return dppo_set_error(DPPO_EUNSUPPORTED, "critic row tile needs %zu B LDS", S.total);
     if ((size_t)4 * WAVES * 16 * MT * 16 > sizeof(typename P::AT) * 16 * MT * (a.HC + lds_pad_elems<P>()))
         return dppo_set_error(DPPO_EUNSUPPORTED, "critic: partial buffer does not fit");
+    if (dry) return DPPO_OK;
     auto k = O4 ? critic_rowtile_kernel_o4<P, MT, NT, TRAIN, WAVES> : critic_rowtile_kernel<P, MT, NT, TRAIN, WAVES>;
     { const int rc_ = dppo_func_lds((const void*)k, (size_t)S.total); if (rc_) return rc_; }
     // TRAIN mode covers every row of the 64-padded feature-major images (padding rows get
@@ -900,20 +906,20 @@ static int launch_critic_t(const CriticArgs& a, hipStream_t s) {
 }
 
 template <class P, int MT, int WAVES, bool O4>
-static int dispatch_critic(const CriticArgs& a, hipStream_t s) {
+static int dispatch_critic(const CriticArgs& a, hipStream_t s, bool dry) {
     const int NT = a.HC / (16 * WAVES);
     const bool tr = a.mode == ROWS_TRAIN;
-    if (NT == 2) return tr ? launch_critic_t<P, MT, 2, true, WAVES, O4>(a, s) : launch_critic_t<P, MT, 2, false, WAVES, O4>(a, s);
+    if (NT == 2) return tr ? launch_critic_t<P, MT, 2, true, WAVES, O4>(a, s, dry) : launch_critic_t<P, MT, 2, false, WAVES, O4>(a, s, dry);
     return dppo_set_error(DPPO_EUNSUPPORTED, "critic: hidden %d not instantiated", a.HC);
 }
 
 // 16-row MFMA tiles per critic row tile: 2 (4, a 64-row tile, measured slower at N = 1 and equal on
 // the emulated 8-rank line; profiles/r04t_critic_tile64_ab.txt, profiles/r06n_rowtile_qd_ab.txt)
 constexpr int CRITIC_MT = 2;
-int launch_critic_rowtile(const CriticArgs& a, int precision, hipStream_t s) {
-    return precision == DPPO_BF16 ? dispatch_critic<PolicyBF16, CRITIC_MT, 8, true>(a, s)
-         : precision == DPPO_F16  ? dispatch_critic<PolicyF16, CRITIC_MT, 8, true>(a, s)
-                                  : dispatch_critic<PolicyF32, CRITIC_MT, 8, true>(a, s);
+int launch_critic_rowtile(const CriticArgs& a, int precision, hipStream_t s, bool dry) {
+    return precision == DPPO_BF16 ? dispatch_critic<PolicyBF16, CRITIC_MT, 8, true>(a, s, dry)
+         : precision == DPPO_F16  ? dispatch_critic<PolicyF16, CRITIC_MT, 8, true>(a, s, dry)
+                                  : dispatch_critic<PolicyF32, CRITIC_MT, 8, true>(a, s, dry);
 }
 
 // =============================================================================================

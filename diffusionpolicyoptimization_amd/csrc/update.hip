@@ -417,27 +417,9 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     DPPO_CHECK(part == MB_WHOLE || m.adv_stats || !needs_adv, "dppo_ppo_minibatch_part: the actor half needs adv_stats");
     DPPO_CHECK((hp->flags & ~(DPPO_PPO_L2_DEFERRED | DPPO_PPO_LEARN_ETA | DPPO_PPO_PRECLEARED)) == 0,
                "dppo_ppo_minibatch: unknown flags 0x%x", hp->flags);
-    // one launch zeroes the atomically accumulated outputs of the half (or whole) being run
-    // (minibatch_zero_args) unless the caller's optimizer step already did (DPPO_PPO_PRECLEARED).
-    // Few workgroups: the split update runs this while the other stream's row tiles hold most CUs,
-    // and a 256-block grid waited ~25 us for slots. MB_ACTOR_DW continues the actor half whose
-    // MB_ACTOR_TILES zeroed its outputs
-    if (part != MB_ACTOR_DW && !(hp->flags & DPPO_PPO_PRECLEARED)) {
-        DppoKtScope kt(KT_ZERO, s);
-        rc = launch_zero(minibatch_zero_args(D, ws, m.grads, m.metrics, part), 16, s);
-        if (rc) return rc;
-    }
     DPPO_CHECK((uint64_t)m.total < ((uint64_t)1 << 32), "dppo_ppo_minibatch: %lld samples x steps exceed 2^32",
                (long long)m.total);
     const FeistelKey fk = feistel_key((uint64_t)m.total, m.perm_seed, m.epoch);
-    const double* stats = m.adv_stats;
-    if (!stats && needs_adv) {
-        const int blocks = dppo_cdiv(rows, 256) < 512 ? dppo_cdiv(rows, 256) : 512;
-        hipLaunchKernelGGL(adv_stats_kernel, dim3(blocks), dim3(256), 0, s, m.advantages, fk, D.KF, m.start, rows,
-                           m.row_index, ws.stats);
-        DPPO_HIP(hipGetLastError());
-        stats = ws.stats;
-    }
     LossHP lh;
     lh.gamma_denoising = hp->gamma_denoising; lh.clip_coef = hp->clip_ploss_coef;
     lh.clip_coef_base = hp->clip_ploss_coef_base; lh.clip_coef_rate = hp->clip_ploss_coef_rate;
@@ -458,7 +440,7 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     aa.sched = m.sched; aa.obs = m.obs; aa.chains = m.chains;
     aa.XD = D.XD; aa.SD = D.SD; aa.TD = D.TD; aa.IN = D.IN; aa.H = D.H; aa.KF = D.KF; aa.Da = D.Da; aa.TS = D.TS;
     aa.mode = ROWS_TRAIN; aa.nrows = rows; aa.fk = fk; aa.start = m.start; aa.row_index = m.row_index;
-    aa.lp_old = m.lp_old_mean; aa.adv = m.advantages; aa.adv_stats = stats; aa.hp = lh; aa.ws = ws; aa.metrics = m.metrics;
+    aa.lp_old = m.lp_old_mean; aa.adv = m.advantages; aa.hp = lh; aa.ws = ws; aa.metrics = m.metrics;
 
     CriticArgs ca = {};
     ca.packed = (const uint8_t*)m.packed_critic;
@@ -467,6 +449,36 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     ca.fk = fk; ca.start = m.start; ca.row_index = m.row_index; ca.returns = m.returns; ca.hp = lh; ca.ws = ws;
     ca.metrics = m.metrics;
 
+    // Every row tile this part runs must have an instantiation before anything is launched: a geometry
+    // the dispatch rejects leaves the gradients, the metrics and the stream's sample counts (which the
+    // critic's last launch re-zeroes) as they were
+    if (part != MB_CRITIC && part != MB_ACTOR_DW) {
+        rc = launch_actor_rowtile(aa, precision, s, true);
+        if (rc) return rc;
+    }
+    if (part == MB_CRITIC || part == MB_WHOLE) {
+        rc = launch_critic_rowtile(ca, precision, s, true);
+        if (rc) return rc;
+    }
+    // one launch zeroes the atomically accumulated outputs of the half (or whole) being run
+    // (minibatch_zero_args) unless the caller's optimizer step already did (DPPO_PPO_PRECLEARED).
+    // Few workgroups: the split update runs this while the other stream's row tiles hold most CUs,
+    // and a 256-block grid waited ~25 us for slots. MB_ACTOR_DW continues the actor half whose
+    // MB_ACTOR_TILES zeroed its outputs
+    if (part != MB_ACTOR_DW && !(hp->flags & DPPO_PPO_PRECLEARED)) {
+        DppoKtScope kt(KT_ZERO, s);
+        rc = launch_zero(minibatch_zero_args(D, ws, m.grads, m.metrics, part), 16, s);
+        if (rc) return rc;
+    }
+    const double* stats = m.adv_stats;
+    if (!stats && needs_adv) {
+        const int blocks = dppo_cdiv(rows, 256) < 512 ? dppo_cdiv(rows, 256) : 512;
+        hipLaunchKernelGGL(adv_stats_kernel, dim3(blocks), dim3(256), 0, s, m.advantages, fk, D.KF, m.start, rows,
+                           m.row_index, ws.stats);
+        DPPO_HIP(hipGetLastError());
+        stats = ws.stats;
+    }
+    aa.adv_stats = stats;
     // the critic's half on stream st: its distinct samples (sample-weighted value loss,
     // crit_rows_kernel), its row tiles, its dW (on the small ring, beside the actor's tail) and its
     // l2 gradient, which also zeroes the sample counts
@@ -609,13 +621,6 @@ extern "C" int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const 
     DPPO_CHECK(ws.total < ((size_t)1 << 31), "dppo_pretrain_minibatch: workspace for %d rows exceeds 2 GiB", rows);
     const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
     float* ga = grads;
-    ZeroArgs z = {};
-    z.p[0] = grads; z.n[0] = FA.count * sizeof(float);
-    z.p[1] = metrics; z.n[1] = 16 * sizeof(double);
-    z.p[2] = ws.pl2; z.n[2] = (size_t)((const uint8_t*)ws.gseg - (const uint8_t*)ws.pl2);   // pl2 | pa0
-    rc = launch_zero(z, 256, s);
-    if (rc) return rc;
-
     ActorArgs aa = {};
     aa.packed = (const uint8_t*)packed_actor;
     aa.L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
@@ -626,6 +631,14 @@ extern "C" int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const 
     // loss = mean over global_rows * XD elements of (eps - noise)^2 (diffusion.py:192)
     const float gscale = dppo_grad_scale_rows(precision, global_rows);
     aa.pre_scale = 2.f * loss_scale / ((float)global_rows * (float)D.XD) * gscale;
+    rc = launch_actor_rowtile(aa, precision, s, true);   // rejected geometries leave the outputs untouched
+    if (rc) return rc;
+    ZeroArgs z = {};
+    z.p[0] = grads; z.n[0] = FA.count * sizeof(float);
+    z.p[1] = metrics; z.n[1] = 16 * sizeof(double);
+    z.p[2] = ws.pl2; z.n[2] = (size_t)((const uint8_t*)ws.gseg - (const uint8_t*)ws.pl2);   // pl2 | pa0
+    rc = launch_zero(z, 256, s);
+    if (rc) return rc;
     rc = launch_actor_rowtile(aa, precision, s);
     if (rc) return rc;
 

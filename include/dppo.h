@@ -89,6 +89,20 @@ typedef struct dppo_dims {
                                  K / S for DDIM (diffusion.py:76-82 uniform discretisation); since ABI 2 */
 } dppo_dims;
 
+/* Supported geometry of the update entries (dppo_logprob, dppo_critic_forward, dppo_ppo_minibatch,
+ * dppo_pretrain_minibatch). The dimension check every entry shares is wider than what the row tiles
+ * instantiate (it takes hidden widths 128/256/384/512, time_dim <= 64, any input width); the rest is
+ * refused with DPPO_EUNSUPPORTED and the dispatch's message before anything is launched, outputs
+ * untouched. With in = horizon_steps*action_dim + time_dim + cond_steps*obs_dim:
+ *   actor, fp32:         actor_hidden 512;        33 <= in <= 64
+ *   actor, bf16 / fp16:  actor_hidden 512, or 256 with horizon_steps*action_dim <= 16; in <= 128
+ *   critic, fp32:        critic_hidden 256;       cond_steps*obs_dim <= 32
+ *   critic, bf16 / fp16: critic_hidden 256;       cond_steps*obs_dim <= 64
+ *   all: horizon_steps*action_dim <= 32, time_dim <= 32 (the image's fold), ft_denoising_steps <= 16
+ *   in dppo_ppo_minibatch (bucket sums), denoising_steps <= 64 in dppo_pretrain_minibatch.
+ * An actor rejection fails dppo_logprob, dppo_pretrain_minibatch and dppo_ppo_minibatch; a critic
+ * rejection dppo_critic_forward and dppo_ppo_minibatch. tests/test_update_surface_gpu.py pins the table. */
+
 /* Schedule table, one fp32 row per sampling row r (r = t for DDPM; the DDIM sub-sequence index for
  * DDIM): {c0, c1, c2, c3, logvar, eval_floor, eval_zero, 0} with
  *   x0 = clip(c0 x - c1 eps, -1, 1);  mu = c2 x0 + c3 x;  sigma = exp(logvar / 2)

@@ -297,7 +297,7 @@ def time_mlp_backward(p, cache, dtemb):
 def diffusion_mlp_forward(p, x, t, state, act="ReLU", rnd=None, round_h3=True):
     """x [B,Ta,Da], t [B] int, state [B,To,Do] -> eps [B,Ta,Da]; cond concat [x, t_emb, state] (:86)."""
     B = x.shape[0]
-    temb, tcache = time_mlp_forward(p, t)
+    temb, tcache = time_mlp_forward(p, t, np.shape(p["time_w1"])[0])   # time_dim: time_w1 is [TD, 2 TD]
     inp = np.concatenate([x.reshape(B, -1), temb, state.reshape(B, -1)], axis=-1).astype(np.float64)
     y, cache = residual_mlp_forward(p, inp, act, "", rnd, round_h3)
     cache["time"] = tcache

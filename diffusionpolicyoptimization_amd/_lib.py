@@ -22,6 +22,7 @@ DPPO_PPO_LEARN_ETA = 2                   # (ABI 9) d loss / d eta into metrics[8
 DPPO_STEP_FUSED_PACK = 0x400             # (ABI 11) AdamW + the image in one launch
 DPPO_STEP_CLEAR_GRADS = 0x800            # (ABI 11) the step zeroes the range's gradients after reading
 DPPO_PPO_PRECLEARED = 4                  # (ABI 11) the part's accumulators are already zero
+DPPO_NET_ACTOR, DPPO_NET_CRITIC = 1, 2   # dppo_grad_clip_scales / dppo_optimizer_step_clip: OR'd, 3 = [actor | critic]
 SCHED_COLS = 8
 PRECISION = {"fp32": DPPO_F32, "f32": DPPO_F32, "bf16": DPPO_BF16, "fp16": DPPO_F16, "f16": DPPO_F16}
 
@@ -103,6 +104,10 @@ _SIGNATURES = {
                                  _P, _I, _U64, _P]),
     "dppo_optimizer_step_ex": (_I, [_DIMS, _I, _P, _P, _P, _P, _I64, _I64, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P,
                                     _P, _P, _I, _U64, _P, _P, _I, _P]),
+    "dppo_grad_clip_workspace_bytes": (_SZ, [_DIMS, _I]),
+    "dppo_grad_clip_scales": (_I, [_DIMS, _I, _P, _F, _P, _P, _P, _P]),
+    "dppo_optimizer_step_clip": (_I, [_DIMS, _I, _P, _P, _P, _P, _I64, _I64, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P,
+                                      _P, _P, _I, _U64, _P, _P, _I, _P, _P, _I]),
     "dppo_ipc_region_bytes": (_SZ, [_I64]),
     "dppo_ipc_alloc": (_I, [_SZ, ctypes.POINTER(ctypes.c_void_p), _P]),
     "dppo_ipc_open": (_I, [_P, ctypes.POINTER(ctypes.c_void_p)]),

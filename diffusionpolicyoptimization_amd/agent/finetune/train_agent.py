@@ -88,6 +88,11 @@ class TrainAgent:
         self.n_steps = cfg.train.n_steps
         self.best_reward_threshold_for_success = cfg.env.get("best_reward_threshold_for_success", 3)
         self.max_grad_norm = cfg.train.get("max_grad_norm", None)
+        # the reference clips every gradient tensor to norm 1.0 whenever max_grad_norm is set, whatever its
+        # value (train_ppo_diffusion_agent.py:349-354); grad_clip_norm (optional) replaces that 1.0
+        self.grad_clip_norm = cfg.train.get("grad_clip_norm", None)
+        if self.grad_clip_norm is not None and not float(self.grad_clip_norm) > 0:
+            raise ValueError("train.grad_clip_norm must be > 0")
 
         self.logdir = cfg.get("logdir", "outputs")
         self.render_dir = os.path.join(self.logdir, "render")

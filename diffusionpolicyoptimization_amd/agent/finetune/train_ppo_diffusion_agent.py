@@ -217,7 +217,7 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         m = self.model
         na, ne = m.n_actor, m.grads_ext.numel()
         # only the buckets the update issues: the split update's two (actor, critic + metrics), or the
-        # single "all" bucket of the unsplit path (max_grad_norm or DPPO_SPLIT_UPDATE=0)
+        # single "all" bucket of the unsplit path (DPPO_SPLIT_UPDATE=0)
         if split:
             self._ipc_groups = {"actor": IpcAllReduce(na, device=self.device),
                                 "critic": IpcAllReduce(ne - na, device=self.device)}
@@ -490,7 +490,17 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
                 return inf, self.target_kl is not None and inf["approx_kl"] > self.target_kl
 
             dp = self.world_size > 1
-            split = self.max_grad_norm is None and os.environ.get("DPPO_SPLIT_UPDATE", "1") != "0"
+            split = os.environ.get("DPPO_SPLIT_UPDATE", "1") != "0"
+            # train.max_grad_norm (agent :349-354: tf.clip_by_norm(grad, 1.0) per variable) keeps the split
+            # update: each half enqueues ONE norm launch (dppo_grad_clip_scales) right before its
+            # optimizer step (under data parallelism after that half's bucket all-reduce: the reference
+            # clips the whole batch's gradient), and the step applies the scales as it reads the gradients.
+            # The unsplit path (DPPO_SPLIT_UPDATE=0) keeps the per-variable torch clip as the independent
+            # statement the device path is tested against.
+            clip_c = None
+            if self.max_grad_norm is not None:
+                clip_c = 1.0 if self.grad_clip_norm is None else float(self.grad_clip_norm)
+            clip_ran = False
             if dp:
                 self._ipc_setup(split)
             # every minibatch's advantage moments (norm_adv, diffusion_ppo.py:74-75) in one launch, and
@@ -540,21 +550,40 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
             # the bound calls are reused across updates while every buffer they captured is the same
             # (~0.2 ms of host marshalling per update, with the device idle behind it)
             ptrs = lambda *ts: tuple((t.data_ptr(), tuple(t.shape)) for t in ts)
+            # the clip's norm table (12 actor + 8 critic variables), scale table and partial-sum workspaces:
+            # allocated once, captured by the bound norm launches and optimizer steps
+            clip_dev = split and clip_c is not None
+            if clip_dev and getattr(self, "_clip_buf", None) is None:
+                f32 = dict(dtype=torch.float32, device=self.device)
+                self._clip_buf = (torch.zeros(20, **f32), torch.ones(20, **f32),
+                                  torch.empty(ops.grad_clip_workspace_bytes(m.dims, "actor") // 8, dtype=torch.float64,
+                                              device=self.device),
+                                  torch.empty(ops.grad_clip_workspace_bytes(m.dims, "critic") // 8, dtype=torch.float64,
+                                              device=self.device))
             bkey = (ptrs(obs_flat, chains_flat, self.lp_old, adv_flat, ret_flat, m.grads, m.train_params,
                          m.packed_ft, m.packed_critic, m.sched, m.workspace(rows_local_full), opt.m, opt.v),
                     self.perm_seed, rows_local_full, self.reward_horizon, split,
-                    self.max_grad_norm is None, m.dims.ft_denoising_steps, m.precision, fuse)
+                    self.max_grad_norm is None, m.dims.ft_denoising_steps, m.precision, fuse,
+                    (ptrs(*self._clip_buf), clip_c) if clip_dev else None)
             if getattr(self, "_bound_key", None) != bkey:
                 bound = {"run_mb": m.bind_minibatch(obs_flat, chains_flat, self.lp_old, adv_flat, ret_flat,
                                                     self.perm_seed, rows_local_full, reward_horizon=self.reward_horizon,
                                                     old_values=self.values)}   # the clipped v_loss's (:110-116)
                 if split:
+                    sc_a = sc_c = None
+                    if clip_dev:
+                        norms, scales, ws_a, ws_c = self._clip_buf
+                        sc_a, sc_c = scales[:12], scales[12:]
+                        bound["clip_actor"] = ops.BoundGradClip(m.dims, "actor", m.grads[:na], clip_c, norms[:12], sc_a, ws_a)
+                        bound["clip_critic"] = ops.BoundGradClip(m.dims, "critic", m.grads[na:ng_all], clip_c, norms[12:],
+                                                                 sc_c, ws_c)
                     bound["actor"] = opt.bind_range(m.grads, 0, na, m.dims, m.precision,
                                                     packs={"actor": (m.actor_ft_params, m.packed_ft)},
-                                                    defer_sampler_tables=defer, fused_pack=fuse, clear_grads=fuse)
+                                                    defer_sampler_tables=defer, fused_pack=fuse, clear_grads=fuse,
+                                                    clip_scales=sc_a)
                     bound["critic"] = opt.bind_range(m.grads, na, ng_all, m.dims, m.precision,
                                                      packs={"critic": (m.critic_params, m.packed_critic)},
-                                                     fused_pack=fuse, clear_grads=fuse)
+                                                     fused_pack=fuse, clear_grads=fuse, clip_scales=sc_c)
                     if fuse:   # what each half of a full minibatch zeroes, per metrics buffer
                         ws_full = m.workspace(rows_local_full)
                         bound["clear"] = [(ops.ClearRanges(m.dims, m.precision, rows_local_full, ws_full, t, 1),
@@ -570,6 +599,7 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
             step_actor, step_critic = self._bound.get("actor"), self._bound.get("critic")
             step_all = self._bound.get("all")
             clear_next = self._bound.get("clear")
+            clip_actor, clip_critic = self._bound.get("clip_actor"), self._bound.get("clip_critic")
             cleared = False   # the previous optimizer step zeroed this minibatch's accumulators
             # raw device addresses and stream handles, computed once: per minibatch the host passes
             # ints instead of slicing tensors and entering stream contexts (~tens of us per minibatch,
@@ -668,13 +698,18 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
                         if split:
                             ctag = tag
                             ca, cc = clear_next[(k + 1) % 2] if fuse else (None, None)
+                            if clip_actor is not None:   # the norms of what each stream's step is about to read
+                                clip_actor(stream=st_main)
+                                clip_critic(stream=st_side)
+                                clip_ran = True
                             step_actor(lr, metrics=met_p, metrics_out=met_out.address, n_metrics=5, metrics_tag=tag,
                                        stream=st_main, clear=ca)
                             step_critic(lr, metrics=met_p + 8, metrics_out=self._cmet_map[slot].address,   # met[1]
                                         n_metrics=1, metrics_tag=ctag, stream=st_side, clear=cc)
                             cleared = fuse
                         elif self.max_grad_norm is not None:
-                            self._clip_by_norm_per_tensor()
+                            self._clip_by_norm_per_tensor(clip_c)
+                            clip_ran = True
                             opt.apply_range(m.grads, 0, ng, lr, m.dims, m.precision,
                                             packs={"actor": (m.actor_ft_params, m.packed_ft),
                                                    "critic": (m.critic_params, m.packed_critic)},
@@ -717,6 +752,10 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         info["explained_var"] = explained_variance_from_moments(
             self._ev_map.array.copy(), self.device, group=dist.group.WORLD if self.world_size > 1 else None)
         info["clipfrac"] = float(np.mean(clipfracs)) if clipfracs else 0.0
+        if clip_ran:   # the last applied minibatch's per-variable norms: one small copy per iteration
+            nrm = (self._clip_buf[0] if clip_dev else self._torch_norms).cpu().numpy()
+            info["grad_norm_max"] = float(nrm.max())
+            info["grad_clipped"] = int((nrm > np.float32(clip_c)).sum())
         return info
 
     def _bc_loss_report(self, mb, obs_flat, total_local, kf):
@@ -737,17 +776,22 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
             s, n_el = float(t[0]), float(t[1])
         return -s / max(n_el, 1.0)
 
-    def _clip_by_norm_per_tensor(self):
-        """Else-branch of agent :349-353: tf.clip_by_norm(grad, 1.0) per variable."""
+    def _clip_by_norm_per_tensor(self, clip_norm=1.0):
+        """Else-branch of agent :349-353: tf.clip_by_norm(grad, 1.0) per variable (clip_norm:
+        train.grad_clip_norm in place of the reference's 1.0). The unsplit path's clip, in plain torch;
+        the per-variable norms of the last call stay in self._torch_norms for the update's report."""
         g = self.model.grads
         o = 0
+        norms = []
         for spec in (self.model.actor_spec, self.model.critic_spec):
             for _, shape in spec:
                 k = int(np.prod(shape))
                 seg = g[o:o + k]
                 nrm = torch.linalg.vector_norm(seg)
-                seg.mul_(torch.clamp(1.0 / torch.clamp(nrm, min=1e-30), max=1.0))
+                seg.mul_(torch.clamp(clip_norm / torch.clamp(nrm, min=1e-30), max=1.0))
+                norms.append(nrm)
                 o += k
+        self._torch_norms = torch.stack(norms)
 
     # ------------------------------------------------------------------ one iteration / the loop
     def iteration(self, force_train=None):

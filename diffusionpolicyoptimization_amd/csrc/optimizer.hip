@@ -1,5 +1,7 @@
 // optimizer.hip — AdamW over the flat fp32 parameters: the plain kernel, the fused one-launch steps
-// that also write the packed images, and the learnable DDIM eta's step.
+// that also write the packed images, the per-variable gradient-clip norms and the steps that apply
+// their scales, and the learnable DDIM eta's step.
+#include <limits.h>
 #include <math.h>
 #include "dppo_update.h"
 #include "dppo_packed.cuh"
@@ -33,6 +35,27 @@ __device__ inline float l2_virtual_grad(const float* __restrict__ g, const L2Vir
     return sum;
 }
 
+// dppo_optimizer_step_clip: the per-variable clip scales (dppo_grad_clip_scales) of the step's range.
+// end[v] = one past variable v in the range (layout order), INT_MAX past the last variable. A step
+// kernel instantiated with a ClipTab as its trailing argument reads each gradient as the rounded fp32
+// product g[i] * scales[v]; instantiated without one it is the unclipped kernel, argument for argument.
+constexpr int CLIP_MAXV = 20;
+struct ClipTab { const float* scales; int end[CLIP_MAXV]; };
+__device__ inline int clip_var(const ClipTab& c, int i) {
+    int v = 0;
+#pragma unroll
+    for (int k = 0; k < CLIP_MAXV - 1; ++k) v += i >= c.end[k];
+    return v;
+}
+// g * s rounded to fp32 before AdamW uses it: the empty asm keeps the product out of any fused
+// multiply-add with the moment updates (the step then equals a step on pre-multiplied gradients)
+__device__ inline float clip_mul(float g, float s) {
+    float x = g * s;
+    asm("" : "+v"(x));
+    return x;
+}
+__device__ inline float clip_scale_at(const ClipTab& c, int i) { return c.scales[clip_var(c, i)]; }
+
 struct AdamHP { float lr, wd, b1, b2, eps, alpha, bc1, bc2; int mode; };
 __device__ inline void adamw_elem(float& pi, float& mi, float& vi, float gi, const AdamHP& h) {
     if (h.mode == DPPO_ADAMW_KERAS) {
@@ -65,17 +88,19 @@ __device__ inline void copy_metrics(const double* met, double* met_out, int nmet
     }
 }
 
+template <class... C>   // C: nothing, or ClipTab
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, float lr, float wd, float b1, float b2,
                                                     float eps, float alpha, float bc1, float bc2, int mode,
                                                     const double* __restrict__ met, double* __restrict__ met_out, int nmet,
-                                                    uint64_t tag, L2Virt vt) {
+                                                    uint64_t tag, L2Virt vt, C... clip) {
     if (blockIdx.x == 0) copy_metrics(met, met_out, nmet, tag);
     const AdamHP h = {lr, wd, b1, b2, eps, alpha, bc1, bc2, mode};
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         float pi = p[i], mi = m[i], vi = v[i];
         const bool virt = vt.on && i >= vt.w_off && i < vt.b_off + vt.H;   // [l2_w | l2_b] are adjacent
-        const float gi = virt ? l2_virtual_grad(g, vt, i) : g[i];
+        float gi = virt ? l2_virtual_grad(g, vt, i) : g[i];
+        if constexpr (sizeof...(C) > 0) gi = clip_mul(gi, clip_scale_at(clip..., (int)i));
         adamw_elem(pi, mi, vi, gi, h);
         p[i] = pi; m[i] = mi; v[i] = vi;
     }
@@ -155,15 +180,16 @@ __device__ inline void clear_words(void* const* clr, const uint32_t* words) {
 
 // The job loops stay rolled: unrolled they made the kernel ~20k instructions long.
 constexpr int FUSE_BLOCKS = 1024;
-template <class ET, int KG, int EPL>
+template <class ET, int KG, int EPL, class... C>
 __global__ __launch_bounds__(256) void adamw_fused_kernel(float* __restrict__ p, float* g, float* __restrict__ m,
                                                           float* __restrict__ v, int64_t n, AdamHP h,
                                                           const double* met, double* met_out, int nmet, uint64_t tag,
-                                                          StepFuse f) {
+                                                          StepFuse f, C... clip) {
     if (blockIdx.x == 0) copy_metrics(met, met_out, nmet, tag);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         float pi = p[i], mi = m[i], vi = v[i];
-        const float gi = g[i];
+        float gi = g[i];
+        if constexpr (sizeof...(C) > 0) gi = clip_mul(gi, clip_scale_at(clip..., (int)i));
         adamw_elem(pi, mi, vi, gi, h);
         p[i] = pi; m[i] = mi; v[i] = vi;
         if (f.clear_grads) g[i] = 0.f;
@@ -207,9 +233,10 @@ struct TileStep {
     uint32_t clr_words[4];
     unsigned* ticket;
 };
-template <class ET, int KG, int EPL>
+// CLIP: every gradient of the tensor is read times sc, its variable's clip scale
+template <class ET, int KG, int EPL, bool CLIP = false>
 __device__ inline void tile_block(float* p, float* g, float* m, float* v, const AdamHP& h, const L2Virt& vt,
-                                  const TileStep& a, const TileMat& M, int b, ET* tile, int lane) {
+                                  const TileStep& a, const TileMat& M, int b, ET* tile, int lane, float sc = 1.f) {
     static_assert(EPL * (int)sizeof(ET) == 16 && 4 * EPL == KG, "one 16-B slot per lane");
     const int nb = b % M.nb, kb = b / M.nb;
     const int n = 16 * nb + (lane & 15), jq = lane >> 4;
@@ -222,7 +249,8 @@ __device__ inline void tile_block(float* p, float* g, float* m, float* v, const 
             const int64_t i = M.off + (int64_t)k * M.N + n;
             float pi = p[i], mi = m[i], vi = v[i];
             const bool virt = vt.on && i >= vt.w_off && i < vt.b_off + vt.H;
-            const float gi = virt ? l2_virtual_grad(g, vt, i) : g[i];
+            float gi = virt ? l2_virtual_grad(g, vt, i) : g[i];
+            if constexpr (CLIP) gi = clip_mul(gi, sc);
             if (a.clear_grads && !in_range(i, a.keep[0]) && !in_range(i, a.keep[1])) g[i] = 0.f;
             adamw_elem(pi, mi, vi, gi, h);
             p[i] = pi; m[i] = mi; v[i] = vi;
@@ -252,10 +280,11 @@ __device__ inline void tile_block(float* p, float* g, float* m, float* v, const 
     }
     __builtin_amdgcn_wave_barrier();   // the tile is rewritten by this wave's next block
 }
-template <class ET, int KG, int EPL>
+template <class ET, int KG, int EPL, class... C>
 __global__ __launch_bounds__(TILE_THREADS) void actor_tile_step_kernel(float* p, float* g, float* m, float* v, AdamHP h,
                                                                       const double* met, double* met_out, int nmet,
-                                                                      uint64_t tag, L2Virt vt, TileStep a) {
+                                                                      uint64_t tag, L2Virt vt, TileStep a, C... clip) {
+    constexpr bool CLIP = sizeof...(C) > 0;
     __shared__ __attribute__((aligned(16))) ET tiles[TILE_THREADS / 64][KG * 16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (blockIdx.x == 0) copy_metrics(met, met_out, nmet, tag);
@@ -263,7 +292,9 @@ __global__ __launch_bounds__(TILE_THREADS) void actor_tile_step_kernel(float* p,
     if (gw < a.mstart[a.nmat]) {
         int mi = 0;
         while (gw >= a.mstart[mi + 1]) ++mi;
-        tile_block<ET, KG, EPL>(p, g, m, v, h, vt, a, a.mat[mi], gw - a.mstart[mi], tiles[wave], lane);
+        float sc = 1.f;   // a weight tensor is one variable: one scale per block
+        if constexpr (CLIP) sc = clip_scale_at(clip..., (int)a.mat[mi].off);
+        tile_block<ET, KG, EPL, CLIP>(p, g, m, v, h, vt, a, a.mat[mi], gw - a.mstart[mi], tiles[wave], lane, sc);
     } else {
         const int64_t e = (int64_t)(gw - a.mstart[a.nmat]) * 64 + lane;
         if (e < a.cstart[a.ncpy]) {
@@ -272,7 +303,8 @@ __global__ __launch_bounds__(TILE_THREADS) void actor_tile_step_kernel(float* p,
             const int64_t local = e - a.cstart[c], i = a.cpy[c].lo + local;
             float pi = p[i], mi = m[i], vi = v[i];
             const bool virt = vt.on && i >= vt.w_off && i < vt.b_off + vt.H;
-            const float gi = virt ? l2_virtual_grad(g, vt, i) : g[i];
+            float gi = virt ? l2_virtual_grad(g, vt, i) : g[i];
+            if constexpr (CLIP) gi = clip_mul(gi, clip_scale_at(clip..., (int)i));   // the time MLP's copy spans 4 variables
             if (a.clear_grads && !in_range(i, a.keep[0]) && !in_range(i, a.keep[1])) g[i] = 0.f;
             adamw_elem(pi, mi, vi, gi, h);
             p[i] = pi; m[i] = mi; v[i] = vi;
@@ -283,6 +315,7 @@ __global__ __launch_bounds__(TILE_THREADS) void actor_tile_step_kernel(float* p,
     if (a.last_mat >= 0) {
         const TileMat& M = a.mat[a.last_mat];
         const int nblk = M.nb * M.KS;
+        // (the virtual l2 gradient's W_out pass: never with a clip, dppo_optimizer_step_clip refuses the pair)
         for (int b = wave; b < nblk; b += TILE_THREADS / 64) tile_block<ET, KG, EPL>(p, g, m, v, h, vt, a, M, b, tiles[wave], lane);
         __syncthreads();   // every W_out slot read by an l2 element was read before the ticket
     }
@@ -332,7 +365,7 @@ struct AdamwArgs {
     int mode;
 };
 static int launch_adamw(const AdamwArgs& a, const double* met, double* met_out, int nmet, uint64_t tag, hipStream_t s,
-                        const L2Virt& vt = L2Virt{}) {
+                        const L2Virt& vt = L2Virt{}, const ClipTab* clip = nullptr) {
     DPPO_CHECK(a.n >= 0 && a.step >= 1, "dppo_adamw: n < 0 or step < 1");
     DPPO_CHECK(a.mode == DPPO_ADAMW_KERAS || a.mode == DPPO_ADAMW_TORCH, "dppo_adamw: bad mode");
     { const int rc_ = check_metrics_copy(met, met_out, nmet, tag); if (rc_) return rc_; }
@@ -342,8 +375,12 @@ static int launch_adamw(const AdamwArgs& a, const double* met, double* met_out, 
     const int64_t blocks64 = (a.n + 255) / 256;
     const unsigned blocks = (unsigned)(blocks64 < 1 ? 1 : (blocks64 < 4096 ? blocks64 : 4096));
     DppoKtScope kt(KT_ADAMW, s);
-    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, s, a.params, a.grads, a.m, a.v, a.n, h.lr, h.wd, h.b1,
-                       h.b2, h.eps, h.alpha, h.bc1, h.bc2, h.mode, met, met_out, nmet, tag, vt);
+    if (clip)
+        hipLaunchKernelGGL((adamw_kernel<ClipTab>), dim3(blocks), dim3(256), 0, s, a.params, a.grads, a.m, a.v, a.n, h.lr,
+                           h.wd, h.b1, h.b2, h.eps, h.alpha, h.bc1, h.bc2, h.mode, met, met_out, nmet, tag, vt, *clip);
+    else
+        hipLaunchKernelGGL((adamw_kernel<>), dim3(blocks), dim3(256), 0, s, a.params, a.grads, a.m, a.v, a.n, h.lr, h.wd,
+                           h.b1, h.b2, h.eps, h.alpha, h.bc1, h.bc2, h.mode, met, met_out, nmet, tag, vt);
     DPPO_HIP(hipGetLastError());
     return DPPO_OK;
 }
@@ -364,6 +401,7 @@ struct StepArgs {
     const double* metrics; double* metrics_out; int n_metrics; uint64_t metrics_tag;
     void* const* clear_ptrs; const size_t* clear_bytes; int n_clear;
     void* stream;
+    const float* clip_scales; int nets;   // dppo_optimizer_step_clip's (nets = 0: no clip)
 };
 // what the validated prologue derives from them
 struct StepCtx {
@@ -374,7 +412,27 @@ struct StepCtx {
     bool defer, l2v, fuse, clear_g;
     FlatOffsets FA, FC;
     L2Virt vt;
+    bool clipped;
+    ClipTab clip;
 };
+
+// The variables of the chosen networks (DPPO_NET_*) in layout order: end[v] = one past variable v,
+// counted from the start of the range; returns their number (12 actor, 8 critic)
+static int net_var_ends(const FlatOffsets& FA, const FlatOffsets& FC, int nets, int64_t* end) {
+    int nv = 0;
+    int64_t base = 0;
+    if (nets & DPPO_NET_ACTOR) {
+        const size_t e[12] = {FA.time_b1, FA.time_w2, FA.time_b2, FA.in_w, FA.in_b, FA.l1_w,
+                              FA.l1_b,    FA.l2_w,    FA.l2_b,    FA.out_w, FA.out_b, FA.count};
+        for (size_t x : e) end[nv++] = (int64_t)x;
+        base = (int64_t)FA.count;
+    }
+    if (nets & DPPO_NET_CRITIC) {
+        const size_t e[8] = {FC.in_b, FC.l1_w, FC.l1_b, FC.l2_w, FC.l2_b, FC.out_w, FC.out_b, FC.count};
+        for (size_t x : e) end[nv++] = base + (int64_t)x;
+    }
+    return nv;
+}
 
 static int step_prologue(const StepArgs& a, StepCtx& c) {
     int rc = dppo_check_dims(a.d, &c.D);
@@ -414,6 +472,20 @@ static int step_prologue(const StepArgs& a, StepCtx& c) {
         c.vt = L2Virt{1, (int64_t)c.FA.l2_w, (int64_t)c.FA.l2_b, (int64_t)c.FA.out_b, D.H, D.XD, a.precision,
                       (const uint8_t*)a.packed_actor + L.off[SEG_W_OUT]};
     }
+    c.clipped = a.nets != 0;
+    c.clip = ClipTab{};
+    if (c.clipped) {
+        DPPO_CHECK(a.nets >= 1 && a.nets <= 3, "dppo_optimizer_step_clip: nets %d outside 1..3", a.nets);
+        DPPO_CHECK(a.clip_scales, "dppo_optimizer_step_clip: clip_scales is NULL");
+        int64_t end[CLIP_MAXV];
+        const int nv = net_var_ends(c.FA, c.FC, a.nets, end);
+        const float* crit = a.w.params ? a.w.params + ((a.nets & DPPO_NET_ACTOR) ? c.FA.count : 0) : nullptr;
+        DPPO_CHECK(a.w.n == end[nv - 1] && ((a.nets & DPPO_NET_ACTOR) == 0 || !a.actor_params || a.actor_params == a.w.params) &&
+                   ((a.nets & DPPO_NET_CRITIC) == 0 || !a.critic_params || a.critic_params == crit),
+                   "dppo_optimizer_step_clip: the range must be exactly the network(s) nets = %d names", a.nets);
+        c.clip.scales = a.clip_scales;
+        for (int v = 0; v < CLIP_MAXV; ++v) c.clip.end[v] = v < nv ? (int)end[v] : INT_MAX;
+    }
     return DPPO_OK;
 }
 
@@ -435,9 +507,14 @@ static int fused_critic_step(const StepArgs& a, const StepCtx& c, const AdamHP& 
     DppoKtScope kt(KT_ADAMW, s);
     with_elem_fmt(a.precision, [&](auto e) {
         using E = decltype(e);
-        hipLaunchKernelGGL((adamw_fused_kernel<typename E::ET, E::KG, E::EPL>), dim3(blocks), dim3(256), 0, s, a.w.params,
-                           const_cast<float*>(a.w.grads), a.w.m, a.w.v, a.w.n, h, a.metrics, c.mout, a.n_metrics,
-                           a.metrics_tag, f);
+        if (c.clipped)
+            hipLaunchKernelGGL((adamw_fused_kernel<typename E::ET, E::KG, E::EPL, ClipTab>), dim3(blocks), dim3(256), 0, s,
+                               a.w.params, const_cast<float*>(a.w.grads), a.w.m, a.w.v, a.w.n, h, a.metrics, c.mout,
+                               a.n_metrics, a.metrics_tag, f, c.clip);
+        else
+            hipLaunchKernelGGL((adamw_fused_kernel<typename E::ET, E::KG, E::EPL>), dim3(blocks), dim3(256), 0, s, a.w.params,
+                               const_cast<float*>(a.w.grads), a.w.m, a.w.v, a.w.n, h, a.metrics, c.mout, a.n_metrics,
+                               a.metrics_tag, f);
     });
     DPPO_HIP(hipGetLastError());
     return DPPO_OK;
@@ -509,9 +586,14 @@ static int fused_actor_step(const StepArgs& a, const StepCtx& c, const AdamHP& h
         DppoKtScope kt(KT_ADAMW, s);
         with_elem_fmt(a.precision, [&](auto e) {
             using E = decltype(e);
-            hipLaunchKernelGGL((actor_tile_step_kernel<typename E::ET, E::KG, E::EPL>), dim3(blocks), dim3(TILE_THREADS), 0,
-                               s, a.w.params, const_cast<float*>(a.w.grads), a.w.m, a.w.v, h, a.metrics, c.mout,
-                               a.n_metrics, a.metrics_tag, c.vt, t);
+            if (c.clipped)
+                hipLaunchKernelGGL((actor_tile_step_kernel<typename E::ET, E::KG, E::EPL, ClipTab>), dim3(blocks),
+                                   dim3(TILE_THREADS), 0, s, a.w.params, const_cast<float*>(a.w.grads), a.w.m, a.w.v, h,
+                                   a.metrics, c.mout, a.n_metrics, a.metrics_tag, c.vt, t, c.clip);
+            else
+                hipLaunchKernelGGL((actor_tile_step_kernel<typename E::ET, E::KG, E::EPL>), dim3(blocks), dim3(TILE_THREADS), 0,
+                                   s, a.w.params, const_cast<float*>(a.w.grads), a.w.m, a.w.v, h, a.metrics, c.mout,
+                                   a.n_metrics, a.metrics_tag, c.vt, t);
         });
     }
     DPPO_HIP(hipGetLastError());
@@ -526,7 +608,7 @@ static int staged_step(const StepArgs& a, const StepCtx& c) {
     hipStream_t s = c.s;
     AdamwArgs w = a.w;
     w.mode = c.mode;
-    int rc = launch_adamw(w, a.metrics, c.mout, a.n_metrics, a.metrics_tag, s, c.vt);
+    int rc = launch_adamw(w, a.metrics, c.mout, a.n_metrics, a.metrics_tag, s, c.vt, c.clipped ? &c.clip : nullptr);
     if (rc) return rc;
     void* zp[5];
     size_t zb[5];
@@ -578,7 +660,7 @@ extern "C" int dppo_optimizer_step(const dppo_dims* d, int precision, float* par
     DPPO_CHECK((mode & DPPO_STEP_CLEAR_GRADS) == 0, "dppo_optimizer_step: DPPO_STEP_CLEAR_GRADS needs dppo_optimizer_step_ex");
     return optimizer_step_impl(StepArgs{d, precision, {params, grads, m, v, n, step, lr, weight_decay, beta1, beta2, eps, mode},
                                         actor_params, packed_actor, critic_params, packed_critic, metrics, metrics_out,
-                                        n_metrics, metrics_tag, nullptr, nullptr, 0, stream});
+                                        n_metrics, metrics_tag, nullptr, nullptr, 0, stream, nullptr, 0});
 }
 
 extern "C" int dppo_optimizer_step_ex(const dppo_dims* d, int precision, float* params, float* grads, float* m,
@@ -589,7 +671,170 @@ extern "C" int dppo_optimizer_step_ex(const dppo_dims* d, int precision, float* 
                                       const size_t* clear_bytes, int n_clear, void* stream) {
     return optimizer_step_impl(StepArgs{d, precision, {params, grads, m, v, n, step, lr, weight_decay, beta1, beta2, eps, mode},
                                         actor_params, packed_actor, critic_params, packed_critic, metrics, metrics_out,
-                                        n_metrics, metrics_tag, clear_ptrs, clear_bytes, n_clear, stream});
+                                        n_metrics, metrics_tag, clear_ptrs, clear_bytes, n_clear, stream, nullptr, 0});
+}
+
+extern "C" int dppo_optimizer_step_clip(const dppo_dims* d, int precision, float* params, float* grads, float* m,
+                                        float* v, int64_t n, int64_t step, float lr, float weight_decay, float beta1,
+                                        float beta2, float eps, int mode, const float* actor_params, void* packed_actor,
+                                        const float* critic_params, void* packed_critic, const double* metrics,
+                                        double* metrics_out, int n_metrics, uint64_t metrics_tag, void* const* clear_ptrs,
+                                        const size_t* clear_bytes, int n_clear, void* stream, const float* clip_scales,
+                                        int nets) {
+    DPPO_CHECK(nets >= 1 && nets <= 3, "dppo_optimizer_step_clip: nets %d outside 1..3", nets);
+    DPPO_CHECK((mode & DPPO_STEP_L2_FROM_PL2) == 0, "dppo_optimizer_step_clip: no clip with DPPO_STEP_L2_FROM_PL2 (the "
+               "factored l2 gradient has no norm before it is formed)");
+    return optimizer_step_impl(StepArgs{d, precision, {params, grads, m, v, n, step, lr, weight_decay, beta1, beta2, eps, mode},
+                                        actor_params, packed_actor, critic_params, packed_critic, metrics, metrics_out,
+                                        n_metrics, metrics_tag, clear_ptrs, clear_bytes, n_clear, stream, clip_scales, nets});
+}
+
+// ---------------------------------------------------------------------------------------------
+// Per-variable gradient norms and clip scales (dppo_grad_clip_scales): tf.clip_by_norm per variable
+// (the reference's max_grad_norm branch, train_ppo_diffusion_agent.py:349-354) without a launch per
+// variable. Every variable is cut into chunks of CLIP_CHUNK elements that never cross a variable
+// boundary; one workgroup per chunk sums its squares in fp64 ((double)g * (double)g is exact) in a
+// fixed order — per thread, then a wave64 shuffle tree, then the four waves in order — and stores ONE
+// partial. The last workgroup to arrive (per-XCD tickets, as last_workgroup above, here with the
+// agent-scope release / acquire the partials need) adds each variable's partials in chunk order
+// and writes norm = sqrt(sum) and scale = clip / max(norm, clip). No floating-point atomics: two
+// launches on the same data give the same bits. Bound by launch latency and the last workgroup's
+// serial sum (at most 64 partials per variable), not by the 2.7 MB it reads.
+// ---------------------------------------------------------------------------------------------
+constexpr int CLIP_CHUNK = 4096, CLIP_MAXCH = 512, CLIP_THREADS = 256;
+struct ClipVars {
+    int nv;
+    int end[CLIP_MAXV];          // one past variable v in the range
+    int cstart[CLIP_MAXV + 1];   // chunk prefix: variable v owns workgroups [cstart[v], cstart[v + 1])
+};
+
+// last_workgroup for a launch whose last workgroup READS what the others stored: every arrival
+// releases its stores at agent scope before its ticket add, and the chain's winners acquire
+__device__ inline bool last_workgroup_acquire(unsigned* ticket) {
+    __shared__ int last_acq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned xcd = blockIdx.x & 7, per = (gridDim.x - xcd + 7) / 8;
+        int l = 0;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (__hip_atomic_fetch_add(ticket + 16 * xcd, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == per - 1) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            ticket[16 * xcd] = 0u;
+            const unsigned nx = gridDim.x < 8 ? gridDim.x : 8;
+            l = __hip_atomic_fetch_add(ticket + 128, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nx - 1;
+            if (l) {
+                ticket[128] = 0u;
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
+        last_acq = l;
+    }
+    __syncthreads();
+    return last_acq != 0;
+}
+
+__device__ inline double sq64(float x) { return (double)x * (double)x; }
+
+__global__ __launch_bounds__(CLIP_THREADS) void grad_clip_kernel(const float* __restrict__ g, ClipVars cv, float clip,
+                                                                 float* __restrict__ norms, float* __restrict__ scales,
+                                                                 double* part, unsigned* ticket) {
+    __shared__ double red[CLIP_MAXCH];
+    __shared__ int cs[CLIP_MAXV + 1];
+    const int t = threadIdx.x, b = blockIdx.x;
+    int v = 0;
+    while (b >= cv.cstart[v + 1]) ++v;                       // uniform: this workgroup's variable
+    const int lo = (v ? cv.end[v - 1] : 0) + (b - cv.cstart[v]) * CLIP_CHUNK;
+    const int len = min(cv.end[v] - lo, CLIP_CHUNK);
+    const float* p = g + lo;
+    // 16-byte loads over the aligned body; a head of up to 3 elements and a tail, one element per thread
+    const int head = min((int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2), len);
+    const int nvec = (len - head) >> 2, tail0 = head + 4 * nvec;
+    double acc = 0.0;
+    if (t < head) acc = sq64(p[t]);
+    const float4* pv = reinterpret_cast<const float4*>(p + head);
+    for (int i = t; i < nvec; i += CLIP_THREADS) {
+        const float4 x = pv[i];
+        acc += sq64(x.x); acc += sq64(x.y); acc += sq64(x.z); acc += sq64(x.w);
+    }
+    if (t < len - tail0) acc += sq64(p[tail0 + t]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    if ((t & 63) == 0) red[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0) {
+        const double s = ((red[0] + red[1]) + red[2]) + red[3];
+        // an agent-scope (write-through) store: the partial is at the memory side before the ticket add
+        __hip_atomic_store(reinterpret_cast<uint64_t*>(part + b), __builtin_bit_cast(uint64_t, s), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!last_workgroup_acquire(ticket)) return;
+    // (the barriers inside last_workgroup_acquire separate red's two uses)
+    const int nch = cv.cstart[cv.nv];
+    for (int i = t; i < nch; i += CLIP_THREADS)
+        red[i] = __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<const uint64_t*>(part + i), __ATOMIC_RELAXED,
+                                                              __HIP_MEMORY_SCOPE_AGENT));
+    if (t == 0) {
+#pragma unroll
+        for (int k = 0; k <= CLIP_MAXV; ++k) cs[k] = cv.cstart[k];
+    }
+    __syncthreads();
+    if (t < cv.nv) {
+        double s = 0.0;
+        for (int c = cs[t]; c < cs[t + 1]; ++c) s += red[c];    // chunk order
+        const float nf = (float)sqrt(s);
+        if (norms) norms[t] = nf;
+        scales[t] = __fdiv_rn(clip, fmaxf(nf, clip));            // exactly 1 when nf <= clip (a zero tensor too)
+    }
+}
+
+static int make_clip_vars(const Dims& D, int nets, ClipVars& cv) {
+    const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD), FC = make_flat_offsets(D.SD, D.HC, 1, 0);
+    int64_t end[CLIP_MAXV];
+    cv = ClipVars{};
+    cv.nv = net_var_ends(FA, FC, nets, end);
+    DPPO_CHECK(end[cv.nv - 1] < ((int64_t)1 << 31), "dppo_grad_clip: range too large");
+    cv.cstart[0] = 0;
+    for (int v = 0; v < CLIP_MAXV; ++v) {
+        cv.end[v] = (int)end[v < cv.nv ? v : cv.nv - 1];
+        const int n = v < cv.nv ? (int)(end[v] - (v ? end[v - 1] : 0)) : 0;
+        cv.cstart[v + 1] = cv.cstart[v] + dppo_cdiv(n, CLIP_CHUNK);
+    }
+    DPPO_CHECK(cv.cstart[cv.nv] <= CLIP_MAXCH, "dppo_grad_clip: %d chunks exceed %d", cv.cstart[cv.nv], CLIP_MAXCH);
+    return DPPO_OK;
+}
+
+extern "C" size_t dppo_grad_clip_workspace_bytes(const dppo_dims* d, int nets) {
+    Dims D;
+    ClipVars cv;
+    if (dppo_check_dims(d, &D) || nets < 1 || nets > 3 || make_clip_vars(D, nets, cv)) return 0;
+    return (size_t)cv.cstart[cv.nv] * sizeof(double);
+}
+
+extern "C" int dppo_grad_clip_scales(const dppo_dims* d, int nets, const float* grads, float clip_norm, float* norms,
+                                     float* scales, void* workspace, void* stream) {
+    Dims D;
+    int rc = dppo_check_dims(d, &D);
+    if (rc) return rc;
+    DPPO_CHECK(nets >= 1 && nets <= 3, "dppo_grad_clip_scales: nets %d outside 1..3", nets);
+    DPPO_CHECK(clip_norm > 0.f && clip_norm <= 3.0e38f, "dppo_grad_clip_scales: clip_norm must be > 0 and finite");
+    DPPO_CHECK(grads && scales, "dppo_grad_clip_scales: grads or scales is NULL");
+    DPPO_CHECK(workspace && ((uintptr_t)workspace & 7) == 0, "dppo_grad_clip_scales: workspace must be 8-B aligned");
+    DPPO_CHECK(((uintptr_t)grads & 3) == 0, "dppo_grad_clip_scales: grads must be 4-B aligned");
+    ClipVars cv;
+    rc = make_clip_vars(D, nets, cv);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned* ticket = nullptr;
+    rc = step_ticket(s, &ticket);
+    if (rc) return rc;
+    DppoKtScope kt(KT_GRAD_CLIP, s);
+    hipLaunchKernelGGL(grad_clip_kernel, dim3((unsigned)cv.cstart[cv.nv]), dim3(CLIP_THREADS), 0, s, grads, cv, clip_norm,
+                       norms, scales, (double*)workspace, ticket);
+    DPPO_HIP(hipGetLastError());
+    return DPPO_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -145,25 +145,103 @@ def pack_all(d: ModelDims, precision, actor_params=None, packed_actor=None, crit
 
 def optimizer_step(d: ModelDims, precision, params, grads, m, v, step, lr, weight_decay, beta1, beta2, eps, mode,
                    actor_params=None, packed_actor=None, critic_params=None, packed_critic=None, metrics=None,
-                   metrics_out=None, n_metrics=0, metrics_tag=0, defer_sampler_tables=False):
+                   metrics_out=None, n_metrics=0, metrics_tag=0, defer_sampler_tables=False, clip_scales=None):
     """AdamW over params/grads/m/v (equal-length flat ranges), the metric sums copied to
     metrics_out (a device tensor or a dppo_host_alloc address), then the given images re-derived:
     two launches on the current stream (dppo_optimizer_step). A nonzero metrics_tag is stored as
     metrics_out[n_metrics] after the sums (the host polls it instead of an event).
     defer_sampler_tables: the actor image's split-sampler tables are left stale and re-derived by
-    the next sampler launch on it (DPPO_STEP_DEFER_SAMPLER_TABLES; the PPO kernels never read them)."""
+    the next sampler launch on it (DPPO_STEP_DEFER_SAMPLER_TABLES; the PPO kernels never read them).
+    clip_scales: the per-variable clip scales of the range (grad_clip_scales), applied as the step reads
+    each gradient (dppo_optimizer_step_clip; the range must be the actor, the critic or both)."""
     n = params.numel()
     for t, nm in ((grads, "grads"), (m, "m"), (v, "v")):
         if t.numel() != n:
             raise ValueError(f"{nm}: expected {n} elements")
     p = _prec(precision)
     mo = metrics_out if isinstance(metrics_out, int) else (metrics_out.data_ptr() if metrics_out is not None else None)
-    _lib.call("dppo_optimizer_step", ctypes.byref(_dims_c(d)), p, ptr(params), ptr(grads), ptr(m), ptr(v), int(n),
-              int(step), float(lr), float(weight_decay), float(beta1), float(beta2), float(eps),
-              (_lib.DPPO_ADAMW_KERAS if mode == "keras" else _lib.DPPO_ADAMW_TORCH) |
-              (_lib.DPPO_STEP_DEFER_SAMPLER_TABLES if defer_sampler_tables else 0), ptr(actor_params), ptr(packed_actor),
-              ptr(critic_params), ptr(packed_critic), ptr(metrics), ctypes.c_void_p(mo) if mo else None,
-              int(n_metrics), ctypes.c_uint64(int(metrics_tag)), stream_handle(params.device))
+    args = (ctypes.byref(_dims_c(d)), p, ptr(params), ptr(grads), ptr(m), ptr(v), int(n),
+            int(step), float(lr), float(weight_decay), float(beta1), float(beta2), float(eps),
+            (_lib.DPPO_ADAMW_KERAS if mode == "keras" else _lib.DPPO_ADAMW_TORCH) |
+            (_lib.DPPO_STEP_DEFER_SAMPLER_TABLES if defer_sampler_tables else 0), ptr(actor_params), ptr(packed_actor),
+            ptr(critic_params), ptr(packed_critic), ptr(metrics), ctypes.c_void_p(mo) if mo else None,
+            int(n_metrics), ctypes.c_uint64(int(metrics_tag)))
+    if clip_scales is None:
+        _lib.call("dppo_optimizer_step", *args, stream_handle(params.device))
+    else:
+        _lib.call("dppo_optimizer_step_clip", *args, None, None, 0, stream_handle(params.device), ptr(clip_scales),
+                  _clip_nets(d, n, clip_scales))
+
+
+_NET_VARS = {_lib.DPPO_NET_ACTOR: 12, _lib.DPPO_NET_CRITIC: 8, _lib.DPPO_NET_ACTOR | _lib.DPPO_NET_CRITIC: 20}
+_NET_NAMES = {"actor": _lib.DPPO_NET_ACTOR, "critic": _lib.DPPO_NET_CRITIC, "both": 3}
+
+
+def _clip_nets(d, n, clip_scales):
+    """The DPPO_NET_* value of a clipped step from its scale table's length (12 actor, 8 critic, 20
+    both); the library checks the range against it."""
+    _check(clip_scales, (clip_scales.numel(),), torch.float32, "clip_scales")
+    for nets, nv in _NET_VARS.items():
+        if clip_scales.numel() == nv:
+            return nets
+    raise ValueError(f"clip_scales: expected 12 (actor), 8 (critic) or 20 (both) entries, got {clip_scales.numel()}")
+
+
+def grad_clip_workspace_bytes(d: ModelDims, nets):
+    return int(_lib.query("dppo_grad_clip_workspace_bytes", ctypes.byref(_dims_c(d)), int(_NET_NAMES.get(nets, nets))))
+
+
+class BoundGradClip:
+    """grad_clip_scales over fixed buffers, validated and marshalled once: a call enqueues the one norm
+    launch on `stream` (a raw handle; default: the current stream). nets: "actor", "critic", "both" or
+    the DPPO_NET_* value; grads: the flat fp32 range of those networks. The norm, scale and workspace
+    buffers are allocated here unless given (norms=False: no norm table)."""
+
+    def __init__(self, d: ModelDims, nets, grads, clip_norm, norms=None, scales=None, workspace=None):
+        nets = int(_NET_NAMES.get(nets, nets))
+        if nets not in _NET_VARS:
+            raise ValueError(f"nets: expected 1 (actor), 2 (critic) or 3 (both), got {nets}")
+        na, nc = _n_params(d)
+        n = (na if nets & 1 else 0) + (nc if nets & 2 else 0)
+        nv = _NET_VARS[nets]
+        _check(grads, (n,), torch.float32, "grads")
+        dev = grads.device
+        if norms is None:
+            norms = torch.zeros(nv, dtype=torch.float32, device=dev)
+        elif norms is False:
+            norms = None
+        _check(norms, (nv,), torch.float32, "norms")
+        if scales is None:
+            scales = torch.ones(nv, dtype=torch.float32, device=dev)
+        _check(scales, (nv,), torch.float32, "scales")
+        need = grad_clip_workspace_bytes(d, nets)
+        if workspace is None:
+            workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        if not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+            raise ValueError(f"workspace: needs {need} contiguous device bytes")
+        if not float(clip_norm) > 0:
+            raise ValueError("clip_norm must be > 0")
+        self.nets, self.norms, self.scales, self.workspace = nets, norms, scales, workspace
+        self._lib = _lib.load()
+        self._args = (ctypes.byref(_dims_c(d)), nets, ptr(grads), float(clip_norm), ptr(norms), ptr(scales), ptr(workspace))
+        self._dev = dev
+        self._keep = (grads,)
+
+    def __call__(self, stream=None):
+        rc = self._lib.dppo_grad_clip_scales(*self._args, stream_handle(self._dev) if stream is None else stream)
+        if rc != 0:
+            raise _lib.DppoError(f"dppo_grad_clip_scales failed ({rc}): {self._lib.dppo_last_error().decode()}")
+        return self.scales
+
+
+def grad_clip_scales(d: ModelDims, nets, grads, clip_norm, norms=None, scales=None, workspace=None, stream=None):
+    """tf.clip_by_norm per variable as a scale table (dppo_grad_clip_scales, one launch): norm[v] =
+    sqrt(sum g^2) in fp64, scale[v] = clip_norm / max(norm[v], clip_norm), one entry per variable of
+    `nets` ("actor": 12, "critic": 8, "both": 20) in layout order. Returns (norms, scales); buffers not
+    given are allocated. BoundGradClip is the per-minibatch form."""
+    b = BoundGradClip(d, nets, grads, clip_norm, norms=norms, scales=scales, workspace=workspace)
+    b(stream)
+    return b.norms, b.scales
 
 
 def refresh_sampler_tables(packed_actor):
@@ -889,10 +967,12 @@ class BoundOptimizerStep:
 
     def __init__(self, d: ModelDims, precision, params, grads, m, v, weight_decay, beta1, beta2, eps, mode,
                  actor_params=None, packed_actor=None, critic_params=None, packed_critic=None,
-                 defer_sampler_tables=False, l2_from_pl2=False, fused_pack=False, clear_grads=False):
+                 defer_sampler_tables=False, l2_from_pl2=False, fused_pack=False, clear_grads=False, clip_scales=None):
         """fused_pack (ABI 11, DPPO_STEP_FUSED_PACK): AdamW and the image in one launch where the
         library can (one network whose parameters are the range); clear_grads (DPPO_STEP_CLEAR_GRADS):
-        the step zeroes the range's gradients and the `clear` ranges of each call after reading them."""
+        the step zeroes the range's gradients and the `clear` ranges of each call after reading them.
+        clip_scales: the range's per-variable clip scales (grad_clip_scales; a device tensor the launch
+        reads at run time), applied as the step reads each gradient (dppo_optimizer_step_clip)."""
         n = params.numel()
         for t, nm in ((grads, "grads"), (m, "m"), (v, "v")):
             if t.numel() != n:
@@ -908,7 +988,12 @@ class BoundOptimizerStep:
         self._hp = (float(weight_decay), float(beta1), float(beta2), float(eps), mode_i, ptr(actor_params),
                     ptr(packed_actor), ptr(critic_params), ptr(packed_critic))
         self._dev = params.device
-        self._keep = (params, grads, m, v, actor_params, packed_actor, critic_params, packed_critic)
+        self._keep = (params, grads, m, v, actor_params, packed_actor, critic_params, packed_critic, clip_scales)
+        self._fn = self._lib.dppo_optimizer_step_ex
+        self._clip = ()
+        if clip_scales is not None:
+            self._fn = self._lib.dppo_optimizer_step_clip
+            self._clip = (ptr(clip_scales), _clip_nets(d, n, clip_scales))
 
     def __call__(self, step, lr, metrics=None, metrics_out=None, n_metrics=0, metrics_tag=0, stream=None, clear=None):
         """metrics_out: a device tensor or a dppo_host_alloc address (as optimizer_step); metrics: a
@@ -917,10 +1002,9 @@ class BoundOptimizerStep:
         mo = metrics_out if isinstance(metrics_out, int) else (metrics_out.data_ptr() if metrics_out is not None else None)
         mi = metrics if isinstance(metrics, int) else ptr(metrics)
         cp, cb, cn = (None, None, 0) if clear is None else clear.args
-        rc = self._lib.dppo_optimizer_step_ex(*self._head, int(step), float(lr), *self._hp, mi,
-                                              ctypes.c_void_p(mo) if mo else None, int(n_metrics),
-                                              ctypes.c_uint64(int(metrics_tag)), cp, cb, cn,
-                                              stream_handle(self._dev) if stream is None else stream)
+        rc = self._fn(*self._head, int(step), float(lr), *self._hp, mi, ctypes.c_void_p(mo) if mo else None,
+                      int(n_metrics), ctypes.c_uint64(int(metrics_tag)), cp, cb, cn,
+                      stream_handle(self._dev) if stream is None else stream, *self._clip)
         if rc != 0:
             raise _lib.DppoError(f"dppo_optimizer_step failed ({rc}): {self._lib.dppo_last_error().decode()}")
 

@@ -38,33 +38,35 @@ class AdamW:
         return lr
 
     def apply_range(self, grads, lo, hi, lr, dims=None, precision=None, packs=(), metrics=None, metrics_out=None,
-                    n_metrics=0, metrics_tag=0, defer_sampler_tables=False):
+                    n_metrics=0, metrics_tag=0, defer_sampler_tables=False, clip_scales=None):
         """The step begin_step() opened, over params[lo:hi], then the images in `packs`
         ((actor_params, packed_actor) and/or (critic_params, packed_critic), keyed "actor" /
         "critic") re-derived, with the minibatch's metric sums copied to metrics_out (followed by
         metrics_tag when nonzero): one dppo_optimizer_step call (two launches) on the current stream.
-        defer_sampler_tables: the actor's split-sampler tables wait for the next sampler launch."""
+        defer_sampler_tables: the actor's split-sampler tables wait for the next sampler launch.
+        clip_scales: the range's per-variable clip scales (ops.grad_clip_scales), applied by the step."""
         pk = dict(packs)
         ap, pa = pk.get("actor", (None, None))
         cp, pc = pk.get("critic", (None, None))
         ops.optimizer_step(dims, precision, self.params[lo:hi], grads[lo:hi], self.m[lo:hi], self.v[lo:hi],
                            self.iterations, lr, self.weight_decay, self.beta_1, self.beta_2, self.epsilon, self.mode,
                            ap, pa, cp, pc, metrics, metrics_out, n_metrics, metrics_tag,
-                           defer_sampler_tables=defer_sampler_tables)
+                           defer_sampler_tables=defer_sampler_tables, clip_scales=clip_scales)
 
     def bind_range(self, grads, lo, hi, dims, precision, packs=(), defer_sampler_tables=False, l2_from_pl2=False,
-                   fused_pack=False, clear_grads=False):
+                   fused_pack=False, clear_grads=False, clip_scales=None):
         """apply_range over a fixed range and fixed images, validated and marshalled once
         (ops.BoundOptimizerStep): returns f(lr, metrics=None, metrics_out=None, n_metrics=0,
         metrics_tag=0, stream=None, clear=None) for the step begin_step() opened. fused_pack /
-        clear_grads: ABI 11 (one launch; the gradients and the `clear` ranges zeroed after use)."""
+        clear_grads: ABI 11 (one launch; the gradients and the `clear` ranges zeroed after use).
+        clip_scales: the range's clip-scale table (ops.BoundGradClip), read by every step at run time."""
         pk = dict(packs)
         ap, pa = pk.get("actor", (None, None))
         cp, pc = pk.get("critic", (None, None))
         b = ops.BoundOptimizerStep(dims, precision, self.params[lo:hi], grads[lo:hi], self.m[lo:hi], self.v[lo:hi],
                                    self.weight_decay, self.beta_1, self.beta_2, self.epsilon, self.mode, ap, pa, cp,
                                    pc, defer_sampler_tables=defer_sampler_tables, l2_from_pl2=l2_from_pl2,
-                                   fused_pack=fused_pack, clear_grads=clear_grads)
+                                   fused_pack=fused_pack, clear_grads=clear_grads, clip_scales=clip_scales)
 
         def step(lr, metrics=None, metrics_out=None, n_metrics=0, metrics_tag=0, stream=None, clear=None):
             b(self.iterations, lr, metrics, metrics_out, n_metrics, metrics_tag, stream=stream, clear=clear)

@@ -180,7 +180,7 @@ DPPO_API int dppo_sampler_release_stream(void* stream);
 
 /* Kernel timer (ABI 10, measurement): while enabled, the library brackets the launches of its
  * timed kernels (the sampler, the row tiles, dW, l2_back, time_bwd, AdamW, pack, GAE, the reward
- * scaler's three kernels, ...; dppo_kernel_timing_name(id) names id, NULL past the last) with HIP
+ * scaler's three kernels, the gradient-clip norms, ...; dppo_kernel_timing_name(id) names id, NULL past the last) with HIP
  * events on the launch's own stream. dppo_kernel_timing(enable) switches it and clears the window;
  * dppo_kernel_timing_read(n, total_ms[n], launches[n]) waits for the window's launches, returns the
  * summed event time and launch count per id, and clears the window. Off by default: a disabled timer
@@ -481,6 +481,39 @@ DPPO_API int dppo_optimizer_step_ex(const dppo_dims* d, int precision, float* pa
                            double* metrics_out, int n_metrics, uint64_t metrics_tag, void* const* clear_ptrs,
                            const size_t* clear_bytes, int n_clear, void* stream);
 
+/* ---- a13, the clip branch: tf.clip_by_norm(grad, 1.0) per variable when train.max_grad_norm is set
+ * (agent/finetune/train_ppo_diffusion_agent.py:349-354), as two device-side pieces so a clipped update
+ * keeps the split, fused, pre-cleared schedule (additions within ABI 15).
+ * dppo_grad_clip_scales: the clip scale of every variable of a network in ONE launch on stream. nets
+ * ORs DPPO_NET_ACTOR (the 12 actor variables of the flat layout above) and DPPO_NET_CRITIC (the 8 critic
+ * variables); 3 = the flat [actor | critic] range. grads is that range (fp32); norms (may be NULL) and
+ * scales are device fp32, one entry per variable in layout order:
+ *   norm[v] = sqrt(sum g^2),  scale[v] = clip_norm / max(norm[v], clip_norm)
+ * so scale is exactly 1.0f where norm <= clip_norm (a zero tensor included) and grad * scale is
+ * tf.clip_by_norm(grad, clip_norm). Every square is formed and summed in fp64 (exact products of fp32
+ * inputs), in a fixed order without floating-point atomics: each variable is cut into chunks that never
+ * cross a variable boundary, each chunk's workgroup stores one partial sum into workspace
+ * (dppo_grad_clip_workspace_bytes(d, nets) bytes, 8-B aligned, contents don't matter), and the last
+ * workgroup to arrive adds each variable's partials in chunk order. Two launches on the same data give
+ * the same bits. clip_norm must be > 0. */
+enum { DPPO_NET_ACTOR = 1, DPPO_NET_CRITIC = 2 };
+DPPO_API size_t dppo_grad_clip_workspace_bytes(const dppo_dims* d, int nets);
+DPPO_API int dppo_grad_clip_scales(const dppo_dims* d, int nets, const float* grads, float clip_norm, float* norms,
+                                   float* scales, void* workspace, void* stream);
+/* dppo_optimizer_step_ex whose AdamW reads each gradient as the fp32 product g[i] * clip_scales[v]
+ * (rounded once, before any moment update: the step equals multiplying the gradients by the expanded
+ * scale table and running dppo_optimizer_step_ex, bit for bit). clip_scales is device fp32, one per
+ * variable of the range in layout order (dppo_grad_clip_scales' output; read by the launch, never by the
+ * host); the range must be exactly the actor, the critic or [actor | critic], as nets says. Every path
+ * (staged, DPPO_STEP_FUSED_PACK, DPPO_STEP_CLEAR_GRADS, the clear ranges, the metrics copy and its tag)
+ * behaves as in dppo_optimizer_step_ex. DPPO_STEP_L2_FROM_PL2 is refused (DPPO_EINVAL): the factored l2
+ * gradient has no norm before it is formed. */
+DPPO_API int dppo_optimizer_step_clip(const dppo_dims* d, int precision, float* params, float* grads, float* m,
+                           float* v, int64_t n, int64_t step, float lr, float weight_decay, float beta1,
+                           float beta2, float eps, int mode, const float* actor_params, void* packed_actor,
+                           const float* critic_params, void* packed_critic, const double* metrics,
+                           double* metrics_out, int n_metrics, uint64_t metrics_tag, void* const* clear_ptrs,
+                           const size_t* clear_bytes, int n_clear, void* stream, const float* clip_scales, int nets);
 
 /* ---- ABI 12, §8(e): the data-parallel gradient all-reduce as one kernel over IPC-mapped peer
  * buffers (the reference has no collective: it applies gradients on one device,

@@ -368,6 +368,13 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
                 a0[r * lda0 + XD + c] = P::cvt(temb[(t - 1) * TD + c]);
             }
         }
+        if constexpr (16 * 16 * NO >= ST) {   // XD = 32 on 8 waves: every thread finished a coordinate, none was spare
+            if (16 * XD >= ST && t > 0)
+                for (int e = tid; e < 16 * TD; e += ST) {
+                    const int r = e / TD, c = e % TD;
+                    a0[r * lda0 + XD + c] = P::cvt(temb[(t - 1) * TD + c]);
+                }
+        }
         lds_sync();
         SPHASE(6);
     }
@@ -378,12 +385,16 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
     }
 }
 
+// dry (every launcher below): run the instantiation's host checks only and launch nothing. sample_impl
+// and dppo_sample_step ask first, so a geometry without an instantiation is refused before anything is
+// enqueued (deferred tables, the observation's copy)
 template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, bool RES>
-static int launch_sample_q(const SampleArgs& a, hipStream_t s) {
+static int launch_sample_q(const SampleArgs& a, hipStream_t s, bool dry) {
     if (a.L.ks_h != ksh_for<P>(NT, SW) || a.L.ks_in != KSI || a.L.ks_h % SW != 0)
         return dppo_set_error(DPPO_EUNSUPPORTED, "sampler: hidden %d not supported at this precision", a.H);
     const size_t lds = stream_lds_total<P>(a, NO, SW);
     if (lds > 160 * 1024) return dppo_set_error(DPPO_EUNSUPPORTED, "sampler needs %zu B of LDS", lds);
+    if (dry) return DPPO_OK;
     auto k = sample_kernel<P, NT, NO, KSI, INJ, QD, SW, RK, RES>;
     { const int rc_ = dppo_func_lds((const void*)k, (size_t)lds); if (rc_) return rc_; }
     DppoKtScope kt(KT_SAMPLER, s);
@@ -405,24 +416,24 @@ static char sampler_cfg() {
 }
 
 template <class P, int NT16, int NO, int KSI, bool INJ>   // NT16: n-tiles per wave of a 16-wave layout
-static int launch_sample_k(const SampleArgs& a, hipStream_t s) {
+static int launch_sample_k(const SampleArgs& a, hipStream_t s, bool dry) {
     constexpr StreamGeom g = stream_geom(P::KG == 32, NT16 * 256);
-    return launch_sample_q<P, NT16 * 16 / g.SW, NO, KSI, INJ, g.QD, g.SW, g.RK, g.RES>(a, s);
+    return launch_sample_q<P, NT16 * 16 / g.SW, NO, KSI, INJ, g.QD, g.SW, g.RK, g.RES>(a, s, dry);
 }
 
 template <class P, int NT, int NO, int KSI>
-static int launch_sample(const SampleArgs& a, hipStream_t s) {
-    if (a.noise) return launch_sample_k<P, NT, NO, KSI, true>(a, s);
-    return launch_sample_k<P, NT, NO, KSI, false>(a, s);
+static int launch_sample(const SampleArgs& a, hipStream_t s, bool dry) {
+    if (a.noise) return launch_sample_k<P, NT, NO, KSI, true>(a, s, dry);
+    return launch_sample_k<P, NT, NO, KSI, false>(a, s, dry);
 }
 
 template <class P>
-static int dispatch_sample(const SampleArgs& a, hipStream_t s) {
+static int dispatch_sample(const SampleArgs& a, hipStream_t s, bool dry) {
     const int NT = a.H / (16 * 16);   // n-tiles per wave of the 16-wave layout
     const int NO = dppo_cdiv(a.XD, 16);
     const int KSI = a.L.ks_in;
 #define DPPO_SAMPLE_CASE(nt, no, ksi) \
-    if (NT == nt && NO == no && KSI == ksi) return launch_sample<P, nt, no, ksi>(a, s);
+    if (NT == nt && NO == no && KSI == ksi) return launch_sample<P, nt, no, ksi>(a, s, dry);
     if constexpr (P::KG == 32) {   // bf16: H = 512 (NT 2)
         DPPO_SAMPLE_CASE(2, 1, 2) DPPO_SAMPLE_CASE(2, 2, 2) DPPO_SAMPLE_CASE(2, 1, 4) DPPO_SAMPLE_CASE(2, 2, 4)
     } else {                       // fp32: H = 512 or 256
@@ -452,9 +463,27 @@ extern "C" int dppo_sampler_stream_bytes(const dppo_dims* d, int precision, int6
     return DPPO_OK;
 }
 
+static int dispatch_stream(const SampleArgs& a, int precision, hipStream_t s, bool dry) {
+    return precision == DPPO_BF16 ? dispatch_sample<PolicyBF16>(a, s, dry)
+         : precision == DPPO_F16  ? dispatch_sample<PolicyF16>(a, s, dry) : dispatch_sample<PolicyF32>(a, s, dry);
+}
+
+// a's dimension fields and layout from the checked dims
+static void sample_geometry(const Dims& D, int precision, SampleArgs& a) {
+    a.XD = D.XD; a.SD = D.SD; a.TD = D.TD; a.H = D.H; a.K = D.K; a.KF = D.KF; a.IN = D.IN;
+    a.L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
+}
+
+// Does a kernel take the shape (a: sample_geometry's fields and E)? The split kernel where its plan
+// does, else the streaming kernel's instantiation checks (dry); launches and enqueues nothing.
+static int sample_supported(const SampleArgs& a, int precision, bool* split) {
+    *split = sampler_cfg() == 'x' && split_plan(precision, a.H, a.XD, a.SD, a.E, a.K, a.KF).P > 0;
+    return *split ? DPPO_OK : dispatch_stream(a, precision, nullptr, true);
+}
+
 // The one launch path: `a` carries the caller's pointers and scalars (fields it does not use are
-// zero); the dimension fields and the layout are filled here, tables an optimizer step deferred are
-// refreshed, and the split kernel or the streaming kernel is chosen.
+// zero); the dimension fields and the layout are filled here, a shape no kernel takes is refused,
+// tables an optimizer step deferred are refreshed, and the split kernel or the streaming kernel runs.
 static int sample_impl(const dppo_dims* d, int precision, SampleArgs a, void* stream) {
     Dims D;
     int rc = dppo_check_dims(d, &D);
@@ -464,20 +493,21 @@ static int sample_impl(const dppo_dims* d, int precision, SampleArgs a, void* st
     if (a.E == 0) return DPPO_OK;
     DPPO_CHECK(a.packed_base && a.packed_ft && a.sched && (a.cond || a.cond_tagged) && a.actions,
                "dppo_sample: null pointer argument");
+    sample_geometry(D, precision, a);
+    bool split = false;
+    rc = sample_supported(a, precision, &split);
+    if (rc) return rc;
     // tables an optimizer step deferred (DPPO_STEP_DEFER_SAMPLER_TABLES) are re-derived first, on this stream
     rc = dppo_refresh_sampler_tables(a.packed_ft, stream);
     if (rc) return rc;
     rc = dppo_refresh_sampler_tables(a.packed_base, stream);
     if (rc) return rc;
-    a.XD = D.XD; a.SD = D.SD; a.TD = D.TD; a.H = D.H; a.K = D.K; a.KF = D.KF; a.IN = D.IN;
-    a.L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
     hipStream_t s = (hipStream_t)stream;
-    if (sampler_cfg() == 'x') {
+    if (split) {
         rc = launch_sample_split(a, precision, s);
         if (rc != DPPO_EUNSUPPORTED) return rc;
     }
-    return precision == DPPO_BF16 ? dispatch_sample<PolicyBF16>(a, s)
-         : precision == DPPO_F16  ? dispatch_sample<PolicyF16>(a, s) : dispatch_sample<PolicyF32>(a, s);
+    return dispatch_stream(a, precision, s, false);
 }
 
 // the three plan queries: dims checked and the split kernel's plan looked up once ({0, ...} under
@@ -566,6 +596,15 @@ extern "C" int dppo_sample_step(const dppo_dims* d, int precision, const void* p
                          stream);
         if (rc) return rc;
     } else {
+        // ask before the observation's copy is enqueued: a refused shape leaves cond as it was
+        DPPO_CHECK(n_envs > 0, "dppo_sample: n_envs < 0");
+        DPPO_CHECK(dppo_prec_ok(precision), "dppo_sample: bad precision %d", precision);
+        SampleArgs q = {};
+        q.E = n_envs;
+        sample_geometry(D, precision, q);
+        bool split = false;
+        rc = sample_supported(q, precision, &split);
+        if (rc) return rc;
         DPPO_HIP(hipMemcpyAsync(cond, cond_host, sizeof(float) * (size_t)n_envs * D.SD, hipMemcpyHostToDevice, s));
         rc = dppo_sample(d, precision, packed_base, packed_ft, sched, cond, n_envs, nullptr, nullptr, seed, call_id,
                          env_offset, deterministic, min_sampling_std, randn_clip, final_clip, actions, chains, stream);

@@ -142,7 +142,24 @@ DPPO_API int dppo_pack_critic(const dppo_dims* d, int precision, const float* pa
  *   env_offset: global row index of row 0 (Philox counter; multi-GPU shards stay distinct)
  *   final_clip <= 0 means None (cfg default)
  *   actions  [n_envs, Ta*Da]                 (Sample.trajectories)
- *   chains   [n_envs, K'+1, Ta*Da] or NULL   (Sample.chains)                                 */
+ *   chains   [n_envs, K'+1, Ta*Da] or NULL   (Sample.chains)
+ * Supported geometry (dppo_sample, dppo_sample_step, dppo_rollout_enqueue*). With XD =
+ * horizon_steps*action_dim, SD = cond_steps*obs_dim, in = XD + time_dim + SD, K = denoising_steps,
+ * the split register-resident kernel runs where all of its line hold, else the weight-streaming one:
+ *   split, bf16 / fp16:     actor_hidden 512; XD % 4 == 0; XD + SD <= 64; K <= 62; n_envs <= 512
+ *   split, fp32:            actor_hidden 512; XD == 12; XD + SD <= 32; K <= 62; n_envs <= 512 on 256
+ *                           CUs (whatever time_dim is: a 31-input hopper variant runs here)
+ *   both split lines:       the kernel's LDS <= 160 KiB (hopper's width stops at K = 60 in fp32 and
+ *                           K = 35 in bf16 / fp16; cond_steps 2 reaches K = 62 in bf16 / fp16)
+ *   streaming, bf16 / fp16: actor_hidden 512; in <= 128
+ *   streaming, fp32:        actor_hidden 256 or 512; 33 <= in <= 64
+ *   both streaming lines:   the kernel's LDS <= 160 KiB (K * XD: K = 100 at XD = 32 is over)
+ * Everything else the dimension check takes (actor_hidden 128 / 384, 256 in bf16 / fp16, other input
+ * widths) is refused with DPPO_EUNSUPPORTED and "sampler: hidden %d / action chunk %d / in-layer
+ * k-steps %d not instantiated", "sampler: hidden %d not supported at this precision" (fp32 384) or
+ * "sampler needs %zu B of LDS" before anything is enqueued: outputs, dppo_sample_step's device copy
+ * of cond and the stream stay as they were. time_dim > 32 has no image (dppo_pack_actor refuses it).
+ * tests/test_sampler_surface_gpu.py pins the table, geometry by geometry.                    */
 DPPO_API int dppo_sample(const dppo_dims* d, int precision, const void* packed_base, const void* packed_ft,
                 const float* sched, const float* cond, int n_envs, const float* x_T, const float* noise,
                 uint64_t seed, uint64_t call_id, int env_offset, int deterministic,

@@ -11,8 +11,9 @@ requires bit-equal outputs: a prefetch that reads one step too far, or a stale c
 there, against the oracle, or as NaN.
 
 (The non-dual single-set path that switches actors mid-launch is chosen by the plan from the device's
-CU count alone; nothing lets a test force it for 2-byte operands, so it is not covered here. fp32 at
-more than 16 groups takes it: tests/test_kernels_gpu.py.)
+CU count alone; nothing lets a test force it for 2-byte operands, so it is not covered here. fp32
+hopper takes it from 9 groups (129 envs) to 32 on 256 CUs: tests/test_sampler_surface_gpu.py,
+test_fp32_split_member_sets.)
 """
 import numpy as np
 import pytest

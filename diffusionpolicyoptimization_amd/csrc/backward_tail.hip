@@ -480,6 +480,15 @@ static size_t time_bwd_lds(const Dims& D, int nb, int* stage_g) {
     if (*stage_g) tsm += sizeof(float) * (size_t)nb * D.H;
     return tsm;
 }
+// At the update entries' accepted geometries (time_dim <= 32, actor_hidden <= 512, nb <= 64) the
+// workgroup needs at most 147,712 B (TD 32, H 512, nb 64; the bucket sums unstaged beyond the 56 KiB
+// cap), so nothing accepted is refused here; the check keeps the entries' rule for any wider geometry
+int time_bwd_check(const Dims& D, int nb) {
+    int stage_g = 0;
+    const size_t tsm = time_bwd_lds(D, nb, &stage_g);
+    if (tsm > 160 * 1024) return dppo_set_error(DPPO_EUNSUPPORTED, "time_bwd needs %zu B LDS", tsm);
+    return DPPO_OK;
+}
 // after the actor's dW: the time-MLP backward over nb buckets at t = q * TS (the bucket sums in gseg),
 // W_out's gradient (out_back) and, unless the l2 gradient stays factored, l2's from pl2, in one launch
 int launch_time_bwd(const Dims& D, int precision, const PpoWorkspace& ws, const void* packed_actor,

@@ -24,7 +24,9 @@ struct PpoWorkspace {
     //   dW_out = W_l2^T pl2 + W_in^T pa0 + (b_l2 + b_in) db_out,  pa0 = a0^T dy [IN][XD] (dW GEMM),
     // formed by the out_back groups after the dW (backward_tail.hip); zeroed with pl2 | pa0 | gseg
     float* pa0;
-    float* gseg;      // [64][H] per-t sums of dh1 (actor in-layer; 16 buckets in PPO, K in pretraining)
+    // [PPO_MAX_BUCKETS][H] per-t sums of dh1 (actor in-layer): K' <= 64 buckets in PPO (the dW's one-hot
+    // rows add into them, so the minibatch zeroes rows [0, ceil16(K')) first), K in pretraining
+    float* gseg;
     float* cpl2;
     double* stats;    // [4] adv {count, sum, sumsq}
     // the critic's distinct samples of a minibatch (sample-weighted value loss, ppo_minibatch_impl):
@@ -34,6 +36,8 @@ struct PpoWorkspace {
     int* crow_cnt;
     size_t total;
 };
+
+constexpr int PPO_MAX_BUCKETS = 64;   // rows of gseg: 16 per wave row of the dW's 256-row tile
 
 inline PpoWorkspace make_ppo_workspace(const Dims& D, int precision, int rows, uint8_t* base) {
     PpoWorkspace w;
@@ -53,7 +57,7 @@ inline PpoWorkspace make_ppo_workspace(const Dims& D, int precision, int rows, u
     w.seg = base ? (int8_t*)(base + o) : nullptr; o = dppo_align256(o + w.ldm);
     w.pl2 = base ? (float*)(base + o) : nullptr; o = dppo_align256(o + 4 * (size_t)D.H * D.XD);
     w.pa0 = base ? (float*)(base + o) : nullptr; o = dppo_align256(o + 4 * (size_t)D.IN * D.XD);
-    w.gseg = base ? (float*)(base + o) : nullptr; o = dppo_align256(o + 4 * 64 * (size_t)D.H);
+    w.gseg = base ? (float*)(base + o) : nullptr; o = dppo_align256(o + 4 * PPO_MAX_BUCKETS * (size_t)D.H);
     w.cpl2 = base ? (float*)(base + o) : nullptr; o = dppo_align256(o + 4 * (size_t)D.HC);
     w.stats = base ? (double*)(base + o) : nullptr; o += 8 * 4;
     w.crow_cnt = base ? (int*)(base + o) : nullptr; o = dppo_align256(o + 4);

@@ -6,12 +6,15 @@
 // ---- dw.hip: the grouped split-K weight-gradient GEMM -------------------------------------------
 enum { EXTRA_NONE = 0, EXTRA_ONES = 1, EXTRA_ONEHOT = 2 };
 // one problem of a grouped launch: G[Kx][N] += XT^T DT over the workspace rows, Gx its extra rows
+// (EXTRA_ONEHOT: nb bucket rows Gx[q][N], q < nb <= 64 on the actor's tile; buckets past nb are not
+// written)
 struct DWItem {
     const void* XT; int Kx;
     const void* DT; int N;
     float* G;
     int extra;
     float* Gx;
+    int nb;
 };
 // the output tile and LDS ring of a launch: the actor's 256-row tile on the full ring, or the critic's
 // 128-row tile on a 3-slot ring (it runs beside the actor's time-MLP backward, which needs LDS too)
@@ -33,6 +36,9 @@ DWPlan dw_plan(DWTile tile, const DWItem* items, int n_items, size_t ldm, int mi
 // l2_back the l2 gradient stays factored in its own region of ga (DPPO_PPO_L2_DEFERRED)
 int launch_time_bwd(const Dims& D, int precision, const PpoWorkspace& ws, const void* packed_actor,
                     const float* actor_params, float* ga, int nb, int TS, hipStream_t s, bool l2_back = true);
+// host check only: DPPO_EUNSUPPORTED ("time_bwd needs %zu B LDS") where launch_time_bwd's workgroup
+// over nb buckets would not fit a CU's 160 KiB; callers ask before their first launch
+int time_bwd_check(const Dims& D, int nb);
 // the critic's l2 weight gradient from ws.cpl2 (N = 1); with zcnt, the launch also zeroes the
 // minibatch's sample counts zcnt[ws.crow_n[r]], r < *ws.crow_cnt
 int launch_critic_l2_back(const Dims& D, int precision, const PpoWorkspace& ws, const void* packed_critic, float* gc,

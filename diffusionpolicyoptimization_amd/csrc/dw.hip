@@ -16,7 +16,9 @@
 // The k-tile-0 workgroups also produce the "extra" rows:
 //   ONES   -> bias gradient  sum_m DT[n][m]
 //   ONEHOT -> per-bucket sums sum_{m: seg[m]=q} DT[n][m]  (actor in-layer: in_b and d t_emb); the
-//             stage's 64 seg bytes travel in the same ring slot
+//             stage's 64 seg bytes travel in the same ring slot. Wave row wr forms buckets
+//             q = 16 wr .. 16 wr + 15 (nb <= 64 buckets on the 256-row tile's four wave rows; wave
+//             rows past the last bucket run the plain loop)
 // Partial tiles are added with fp32 atomics (one add per element per m-chunk).
 // ---------------------------------------------------------------------------------------------
 #define DW_MAXP 8
@@ -49,6 +51,7 @@ template <int WK, int RC = 8> struct DWGeom {
 struct DWProb {
     const void* XT; const void* DT; float* G; float* Gx;
     int Kx, N, extra, ktiles, ntiles;
+    int nb;                   // ONEHOT: buckets q < nb (<= 16 per wave row of the tile)
 };
 struct DWArgs {
     DWProb p[DW_MAXP];
@@ -64,7 +67,8 @@ struct DWArgs {
 typedef __attribute__((address_space(3))) void lds_void_t;
 
 // extra A fragment: row q of [ones] or [one-hot(seg == q)] over EPL consecutive rows; the
-// chunk's seg bytes sit in LDS (staged before the glds pipeline starts)
+// chunk's seg bytes sit in LDS (staged before the glds pipeline starts). q >= 0, so a padding
+// row's seg of -1 matches no bucket
 template <class P>
 __device__ inline u32x4 extra_frag(int extra, int q, const int8_t* seg_lds) {
     using AT = typename P::AT;
@@ -100,7 +104,9 @@ __device__ inline void vm_wait() {
 // the main loop, with or without the extra (bias / bucket) rows: two straight copies, so the
 // register allocator sees one uniform accumulator set per loop (a data-dependent MFMA inside
 // one loop made hipcc shuttle the accumulators between AGPRs and VGPRs every k-step).
-// SEGLD: this wave also copies the stage's seg bytes (ONEHOT extra rows).
+// SEGLD: this wave also copies the stage's seg bytes (ONEHOT extra rows: wave row 0's waves; the
+// other wave rows with buckets read them after the stage's barrier like any staged operand, and
+// count only their own A and B copies in OPS).
 template <class P, int WK, int RC, bool EXTRA, bool SEGLD>
 __device__ __forceinline__ void dw_loop(uint8_t* smem, const DWArgs& a, const DWProb& pr, int nst, size_t m_begin,
                                         int wave, int lane, const typename P::AT* const (&srcA)[DWGeom<WK, RC>::AI],
@@ -157,7 +163,7 @@ __device__ __forceinline__ void dw_loop(uint8_t* smem, const DWArgs& a, const DW
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[i][j] = P::mma(A[i], B[j], acc[i][j]);
             if constexpr (EXTRA) {
-                const u32x4 AE = extra_frag<P>(pr.extra, fr, seg_lds + ks * P::KG + cq * P::EPL);
+                const u32x4 AE = extra_frag<P>(pr.extra, 16 * wr + fr, seg_lds + ks * P::KG + cq * P::EPL);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acce[j] = P::mma(AE, B[j], acce[j]);
             }
@@ -215,8 +221,10 @@ __global__ __launch_bounds__(WK / 32 * 64) void dw_kernel(DWArgs a) {   // DWGeo
     const AT* XT = (const AT*)pr.XT;
     const AT* DT = (const AT*)pr.DT;
     const bool wg_extra = pr.extra != EXTRA_NONE && kt == 0;      // uniform over the workgroup
-    const bool do_extra = wg_extra && wr == 0;
-    const bool seg_ld = do_extra && pr.extra == EXTRA_ONEHOT;
+    // extra rows of this wave row: ONES has one (row 0), ONEHOT buckets 16 wr .. < nb
+    const int xrows = pr.extra == EXTRA_ONEHOT ? pr.nb : 1;
+    const bool do_extra = wg_extra && 16 * wr < xrows;
+    const bool seg_ld = wg_extra && wr == 0 && pr.extra == EXTRA_ONEHOT;
 
     // per-lane glds sources of this wave's A and B wave-instructions (features ins*8 + lane/8)
     const AT* srcA[G::AI];
@@ -264,10 +272,10 @@ __global__ __launch_bounds__(WK / 32 * 64) void dw_kernel(DWArgs a) {   // DWGeo
             if (n >= pr.N) continue;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int q = crow(lane, r);
+                const int q = 16 * wr + crow(lane, r);
                 if (pr.extra == EXTRA_ONES) {
                     if (q == 0) atomicAdd(pr.Gx + n, acce[j][r] * a.out_scale);
-                } else {
+                } else if (q < pr.nb) {
                     atomicAdd(pr.Gx + (size_t)q * pr.N + n, acce[j][r] * a.out_scale);
                 }
             }
@@ -308,11 +316,14 @@ int launch_dw(DWTile tile, int precision, const DWItem* items, int n_items, cons
               const int* rows_dev, int min_chunk_rows, hipStream_t s) {
     DPPO_CHECK(n_items >= 1 && n_items <= DW_MAXP, "dW: %d problems in one launch", n_items);
     const int tk = tile == DWTile::ACTOR ? 256 : 128;
+    for (int i = 0; i < n_items; ++i)   // one 16-bucket one-hot tile per wave row of the output tile
+        DPPO_CHECK(items[i].extra != EXTRA_ONEHOT || (items[i].nb >= 1 && items[i].nb <= tk / 4),
+                   "dW: %d one-hot buckets on a %d-row tile", items[i].nb, tk);
     DWArgs w = {};
     for (int i = 0; i < n_items; ++i) {
         const DWItem& it = items[i];
         DWProb& p = w.p[i];
-        p.XT = it.XT; p.DT = it.DT; p.G = it.G; p.Gx = it.Gx; p.Kx = it.Kx; p.N = it.N; p.extra = it.extra;
+        p.XT = it.XT; p.DT = it.DT; p.G = it.G; p.Gx = it.Gx; p.Kx = it.Kx; p.N = it.N; p.extra = it.extra; p.nb = it.nb;
         p.ktiles = dppo_cdiv(it.Kx, tk); p.ntiles = dppo_cdiv(it.N, DW_TN);
         w.tile_start[i + 1] = w.tile_start[i] + dw_item_tiles(tile, it);
     }

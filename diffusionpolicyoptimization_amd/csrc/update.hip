@@ -280,7 +280,8 @@ static ZeroArgs minibatch_zero_args(const Dims& D, const PpoWorkspace& ws, float
     const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
     const FlatOffsets FC = make_flat_offsets(D.SD, D.HC, 1, 0);
     ZeroArgs z = {};
-    const size_t actor_acc = (size_t)((const uint8_t*)(ws.gseg + 16 * D.H) - (const uint8_t*)ws.pl2);   // pl2 | pa0 | gseg
+    // pl2 | pa0 | gseg: the bucket rows the dW adds into, whole wave rows of 16 (K' <= 64)
+    const size_t actor_acc = (size_t)((const uint8_t*)(ws.gseg + (size_t)dppo_cdiv(D.KF, 16) * 16 * D.H) - (const uint8_t*)ws.pl2);
     const size_t critic_acc = (size_t)((const uint8_t*)(ws.crow_cnt + 1) - (const uint8_t*)ws.cpl2);
     if (part == MB_WHOLE) {
         z.p[0] = grads; z.n[0] = (FA.count + FC.count) * sizeof(float);
@@ -308,6 +309,7 @@ extern "C" int dppo_ppo_clear_ranges(const dppo_dims* d, int precision, int batc
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
     DPPO_CHECK(workspace && metrics && ptrs && bytes && count && batch_rows > 0, "dppo_ppo_clear_ranges: bad arguments");
     DPPO_CHECK(part == 1 || part == 2 || part == 3 || part == 4, "dppo_ppo_clear_ranges: part must be 1, 2, 3 or 4");
+    DPPO_CHECK(D.KF <= PPO_MAX_BUCKETS, "dppo_ppo_clear_ranges: ft_denoising_steps %d > %d", D.KF, PPO_MAX_BUCKETS);
     const PpoWorkspace ws = make_ppo_workspace(D, precision, batch_rows, (uint8_t*)workspace);
     const ZeroArgs z = minibatch_zero_args(D, ws, nullptr, metrics, (MbPart)part);
     int n = 0;
@@ -332,7 +334,7 @@ static float* grad_at(float* g, size_t off) { return g ? g + off : nullptr; }
 static void actor_dw_items(const Dims& D, const PpoWorkspace& ws, float* ga, bool pretrain, bool l2_def, DWItem (&it)[4]) {
     const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
     it[0] = pretrain ? DWItem{ws.a0T, D.IN, ws.dh1T, D.H, grad_at(ga, FA.in_w), EXTRA_NONE, nullptr}
-                     : DWItem{ws.a0T, D.IN, ws.dh1T, D.H, grad_at(ga, FA.in_w), EXTRA_ONEHOT, ws.gseg};
+                     : DWItem{ws.a0T, D.IN, ws.dh1T, D.H, grad_at(ga, FA.in_w), EXTRA_ONEHOT, ws.gseg, D.KF};
     it[1] = DWItem{ws.u1T, D.H, ws.dh2T, D.H, grad_at(ga, FA.l1_w), EXTRA_ONES, grad_at(ga, FA.l1_b)};
     it[2] = DWItem{ws.u2T, D.H, ws.dyT, D.XD, l2_def ? grad_at(ga, FA.l2_w) : ws.pl2, EXTRA_NONE, nullptr};   // l2 through the out layer
     it[3] = DWItem{ws.a0T, D.IN, ws.dyT, D.XD, ws.pa0, EXTRA_ONES, grad_at(ga, FA.out_b)};   // out through the fold (out_back)
@@ -405,7 +407,10 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     DPPO_CHECK(m.total > 0 && m.total % D.KF == 0, "dppo_ppo_minibatch: total must be a positive multiple of K'");
     DPPO_CHECK(rows > 0 && m.start >= 0, "dppo_ppo_minibatch: bad rows/start");
     DPPO_CHECK(hp->global_rows > 0, "dppo_ppo_minibatch: global_rows must be > 0");
-    DPPO_CHECK(D.KF <= 16, "dppo_ppo_minibatch: ft_denoising_steps > 16 unsupported (bucket sums)");
+    // the dW forms the per-t bucket sums 16 to a wave row of its 256-row tile, and gseg holds 64 rows
+    if (D.KF > PPO_MAX_BUCKETS)
+        return dppo_set_error(DPPO_EUNSUPPORTED, "dppo_ppo_minibatch: ft_denoising_steps %d > %d unsupported (bucket sums)",
+                              D.KF, PPO_MAX_BUCKETS);
     hipStream_t s = (hipStream_t)m.stream;
     const PpoWorkspace ws = make_ppo_workspace(D, precision, rows, (uint8_t*)m.workspace);
     DPPO_CHECK(ws.total < ((size_t)1 << 31), "dppo_ppo_minibatch: workspace for %d rows exceeds 2 GiB", rows);
@@ -458,6 +463,10 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     }
     if (part == MB_CRITIC || part == MB_WHOLE) {
         rc = launch_critic_rowtile(ca, precision, s, true);
+        if (rc) return rc;
+    }
+    if (part != MB_CRITIC && part != MB_ACTOR_TILES) {   // the parts that end in the time-MLP backward
+        rc = time_bwd_check(D, D.KF);
         if (rc) return rc;
     }
     // one launch zeroes the atomically accumulated outputs of the half (or whole) being run

@@ -98,10 +98,21 @@ typedef struct dppo_dims {
  *   actor, bf16 / fp16:  actor_hidden 512, or 256 with horizon_steps*action_dim <= 16; in <= 128
  *   critic, fp32:        critic_hidden 256;       cond_steps*obs_dim <= 32
  *   critic, bf16 / fp16: critic_hidden 256;       cond_steps*obs_dim <= 64
- *   all: horizon_steps*action_dim <= 32, time_dim <= 32 (the image's fold), ft_denoising_steps <= 16
- *   in dppo_ppo_minibatch (bucket sums), denoising_steps <= 64 in dppo_pretrain_minibatch.
+ *   all: horizon_steps*action_dim <= 32, time_dim <= 32 (the image's fold), ft_denoising_steps <= 64
+ *   in dppo_ppo_minibatch{,_part} (bucket sums: 16 per wave row of the dW's 256-row tile; above it
+ *   "ft_denoising_steps %d > 64 unsupported (bucket sums)"), denoising_steps <= 64 in
+ *   dppo_pretrain_minibatch.
+ *   LDS that grows with K' (K in pretraining): the 64-row actor tile (bf16 / fp16, actor_hidden 512,
+ *   horizon_steps*action_dim <= 16, minibatches of at least 64 x CU-count rows) keeps K' rows of time
+ *   embeddings and schedule (K' (4 time_dim + 32) bytes) beside its activation tiles: hopper's
+ *   geometry needs 161,616 + 96 K' bytes, so K' <= 23 fits the CU's 160 KiB there and K' >= 24 is
+ *   refused with "actor row tile needs %zu B LDS" (the 32-row tile of smaller minibatches and of fp32
+ *   takes every K' <= 64). The time-MLP backward's workgroup needs at most 147,712 B at the accepted
+ *   geometries (time_dim 32, actor_hidden 512, K' 64), so it refuses none of them ("time_bwd needs
+ *   %zu B LDS" otherwise, also before the first launch).
  * An actor rejection fails dppo_logprob, dppo_pretrain_minibatch and dppo_ppo_minibatch; a critic
- * rejection dppo_critic_forward and dppo_ppo_minibatch. tests/test_update_surface_gpu.py pins the table. */
+ * rejection dppo_critic_forward and dppo_ppo_minibatch. tests/test_update_surface_gpu.py pins the
+ * table, tests/test_update_ft_steps_gpu.py its K' lines. */
 
 /* Schedule table, one fp32 row per sampling row r (r = t for DDPM; the DDIM sub-sequence index for
  * DDIM): {c0, c1, c2, c3, logvar, eval_floor, eval_zero, 0} with

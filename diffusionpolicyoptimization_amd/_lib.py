@@ -25,6 +25,8 @@ DPPO_PPO_PRECLEARED = 4                  # (ABI 11) the part's accumulators are 
 DPPO_NET_ACTOR, DPPO_NET_CRITIC = 1, 2   # dppo_grad_clip_scales / dppo_optimizer_step_clip: OR'd, 3 = [actor | critic]
 SCHED_COLS = 8
 PRECISION = {"fp32": DPPO_F32, "f32": DPPO_F32, "bf16": DPPO_BF16, "fp16": DPPO_F16, "f16": DPPO_F16}
+# the actor's activation_type (DPPO_ACT_*): an attribute of a packed actor image (dppo_pack_actor_act)
+ACTIVATION = {"ReLU": 0, "Mish": 1}
 
 
 class DppoDims(ctypes.Structure):
@@ -60,6 +62,7 @@ _SIGNATURES = {
     "dppo_critic_packed_bytes": (_SZ, [_DIMS, _I]),
     "dppo_pack_actor": (_I, [_DIMS, _I, _P, _P, _P]),
     "dppo_pack_critic": (_I, [_DIMS, _I, _P, _P, _P]),
+    "dppo_pack_actor_act": (_I, [_DIMS, _I, _I, _P, _P, _P]),
     "dppo_sample": (_I, [_DIMS, _I, _P, _P, _P, _P, _I, _P, _P, _U64, _U64, _I, _I, _F, _F, _F, _P, _P, _P]),
     "dppo_sample_step": (_I, [_DIMS, _I, _P, _P, _P, _P, _P, _I, _U64, _U64, _I, _I, _F, _F, _F, _P, _P, _P, _I, _P]),
     "dppo_host_alloc": (_I, [_SZ, ctypes.POINTER(ctypes.c_void_p)]),
@@ -88,6 +91,7 @@ _SIGNATURES = {
     "dppo_gae": (_I, [_P, _P, _P, _P, _I, _I, _D, _D, _D, _P, _P, _P]),
     "dppo_ppo_workspace_bytes": (_SZ, [_DIMS, _I, _I]),
     "dppo_ppo_plan": (_I, [_DIMS, _I, _I, _I, ctypes.POINTER(ctypes.c_int)]),
+    "dppo_ppo_plan_act": (_I, [_DIMS, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)]),
     "dppo_ppo_adv_stats": (_I, [_P, _I64, _I, _U64, _I, _I64, _I, _P, _P, _P]),
     "dppo_ppo_adv_stats_all": (_I, [_P, _I64, _I, _U64, _I, _I, _I64, _I, _P, _P]),
     "dppo_ppo_minibatch": (_I, [_DIMS, _I, ctypes.POINTER(DppoPpoHparams), _P, _P, _P, _P, _P, _P, _P, _P, _P,

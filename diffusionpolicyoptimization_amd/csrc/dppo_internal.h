@@ -43,6 +43,11 @@ int dppo_pack_rt_fold(int in_dim, int hidden, int out_dim, int time_dim, int pre
                       void* packed_actor, int temb_steps, int time_stride, hipStream_t s);
 // temb: the TEMB table is stale too (the fused actor step), not only the split-sampler tables
 int dppo_mark_tables_stale(const Dims& D, int precision, const float* actor_params, const void* packed_actor, bool temb);
+// the activation (DPPO_ACT_*) recorded for the actor image at `packed` (dppo_pack_actor_act; pack.hip):
+// ReLU for an address no such pack recorded. Host table keyed by the address, as the stale-table list
+int dppo_actor_image_act(const void* packed);
+void dppo_actor_image_set_act(const void* packed, int activation);
+inline bool dppo_act_ok(int a) { return a == DPPO_ACT_RELU || a == DPPO_ACT_MISH; }
 // device address of mapped pinned host memory (dppo_host_alloc), cached; null if not mapped (host_staging.hip)
 void* mapped_ptr(const void* host);
 

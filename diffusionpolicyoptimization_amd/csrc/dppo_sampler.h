@@ -207,4 +207,5 @@ struct SplitPlan { int P; bool dual; int blocks; int cus; };
 SplitPlan split_plan(int precision, int H, int XD, int SD, int E, int K, int KF);
 // returns DPPO_OK after launching, DPPO_EUNSUPPORTED (without touching the error message) when
 // split_plan does not take the shape, or another error code
-int launch_sample_split(const SampleArgs& a, int precision, hipStream_t s);
+// act: the images' activation (DPPO_ACT_*), one instantiation each
+int launch_sample_split(const SampleArgs& a, int precision, int act, hipStream_t s);

@@ -1,6 +1,7 @@
 // pack.hip — flat fp32 Keras parameters -> packed MFMA fragment images (dppo_layout.h).
 // Replaces the Keras variable storage of model/common/mlp.py:95-206 (kernels are [in,out]).
 #include <mutex>
+#include <vector>
 #include "dppo_common.cuh"
 #include "dppo_internal.h"
 
@@ -618,6 +619,28 @@ int mark_stale(const Dims& D, int precision, const float* params, const void* pa
     return DPPO_OK;
 }
 }  // namespace
+
+// The activation of an actor image (include/dppo.h, dppo_pack_actor_act): only Mish images are listed
+// (ReLU, the default of an unlisted address, erases the entry), keyed by the image's address like g_stale.
+namespace {
+std::mutex g_act_mu;
+std::vector<const void*> g_mish;
+}  // namespace
+int dppo_actor_image_act(const void* packed) {
+    std::lock_guard<std::mutex> lk(g_act_mu);
+    for (const void* p : g_mish)
+        if (p == packed) return DPPO_ACT_MISH;
+    return DPPO_ACT_RELU;
+}
+void dppo_actor_image_set_act(const void* packed, int activation) {
+    std::lock_guard<std::mutex> lk(g_act_mu);
+    for (size_t i = 0; i < g_mish.size(); ++i)
+        if (g_mish[i] == packed) {
+            if (activation != DPPO_ACT_MISH) { g_mish[i] = g_mish.back(); g_mish.pop_back(); }
+            return;
+        }
+    if (activation == DPPO_ACT_MISH) g_mish.push_back(packed);
+}
 
 // the fused step leaves the actor image's split-sampler tables stale like a PACK_UPDATE pack
 int dppo_mark_tables_stale(const Dims& D, int precision, const float* actor_params, const void* packed_actor, bool temb) {

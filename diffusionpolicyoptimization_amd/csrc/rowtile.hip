@@ -77,9 +77,15 @@ struct ActorSmem {
     }
 };
 
-template <class P, int MT, int NT, int NO, int KSI, bool TRAIN, int WAVES>
+// ACT (DPPO_ACT_RELU / DPPO_ACT_MISH): the image's activation at the block's two sites, u1 = act(h1) and
+// a = act(h2) (mlp.py:192-193, 202-203). relu' is read off the activation's sign (one bit per element);
+// mish is not monotone, so a Mish TRAIN tile keeps h1 and h2 themselves in registers until the
+// backward, as the critic tile does (8 MT NT VGPRs: the 8-wave tiles have them, the 16-wave ones do not)
+template <class P, int MT, int NT, int NO, int KSI, bool TRAIN, int WAVES, int ACT>
 __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
     using AT = typename P::AT;
+    constexpr bool MISH = ACT == DPPO_ACT_MISH;
+    constexpr bool CARRY = MISH && TRAIN;
     constexpr int THREADS = 64 * WAVES;
     constexpr int ROWS = 16 * MT;
     static_assert(ROWS <= 64, "the epilogue maps one row per lane of wave 0");
@@ -231,6 +237,7 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
     using MaskT = typename std::conditional<(MT * NT * 4 > 32), uint64_t, uint32_t>::type;
     static_assert(MT * NT * 4 <= 64, "relu masks are at most 64-bit");
     MaskT mask1 = 0, mask2 = 0;
+    f32x4 hk1[CARRY ? MT : 1][CARRY ? NT : 1], hk2[CARRY ? MT : 1][CARRY ? NT : 1];   // Mish TRAIN: h1, h2
     // The weight stream is one QD-deep queue per wave through every layer of the kernel:
     //   in -> l1 -> [train] out^T -> M^T -> l1^T. The l2 layer never runs as a GEMM: the residual block
     //   is linear from the l2 product to the out-Dense (mlp.py:186-206), so
@@ -251,11 +258,16 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if (acc[m][n][r] > 0.f) mask1 |= MaskT(1) << ((m * NT + n) * 4 + r);
-                acc[m][n][r] = fmaxf(acc[m][n][r], 0.f);
+                if constexpr (MISH) {
+                    if constexpr (CARRY) hk1[m][n][r] = acc[m][n][r];
+                    acc[m][n][r] = mishf(acc[m][n][r]);
+                } else {
+                    if (acc[m][n][r] > 0.f) mask1 |= MaskT(1) << ((m * NT + n) * 4 + r);
+                    acc[m][n][r] = fmaxf(acc[m][n][r], 0.f);
+                }
             }
     // materialise the mask now (otherwise hipcc keeps the 8*MT*NT floats alive until the backward)
-    asm volatile("" : "+v"(mask1));
+    if constexpr (!MISH) asm volatile("" : "+v"(mask1));
     store_acc_lds<P, MT, NT>(tA, ldh, ntile0, lane, acc);
     if constexpr (train) store_accT<P, MT, NT>(wsr, ws_off(a.ws, a.ws.u1T), ldm32, ntile0, grow32, lane, acc);
     lds_sync();
@@ -264,7 +276,7 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
         if (tid < ROWS) { radv[tid] = pre_adv; rlpo[tid] = pre_lpo; }
         else if (tid == ROWS) { nrm[0] = pre_m; nrm[1] = pre_s; }
     }
-    // ---- L2: h2 = relu(h1) W_l1 + b ----
+    // ---- L2: h2 = act(h1) W_l1 + b ----
     if constexpr (train)
         gemm_queue<P, MT, NT, KSH, QD>(tA, ldh, W(SEG_W_L1), ntile0, acc, lane, R,
                                        NextLayers{W(SEG_T_OUT), KSO, W(SEG_RT_TFOLD), KSO});
@@ -277,10 +289,15 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if (acc[m][n][r] > 0.f) mask2 |= MaskT(1) << ((m * NT + n) * 4 + r);
-                acc[m][n][r] = fmaxf(acc[m][n][r], 0.f);
+                if constexpr (MISH) {
+                    if constexpr (CARRY) hk2[m][n][r] = acc[m][n][r];
+                    acc[m][n][r] = mishf(acc[m][n][r]);
+                } else {
+                    if (acc[m][n][r] > 0.f) mask2 |= MaskT(1) << ((m * NT + n) * 4 + r);
+                    acc[m][n][r] = fmaxf(acc[m][n][r], 0.f);
+                }
             }
-    asm volatile("" : "+v"(mask2));
+    if constexpr (!MISH) asm volatile("" : "+v"(mask2));
     store_acc_lds<P, MT, NT>(tB, ldh, ntile0, lane, acc);
     if constexpr (train) store_accT<P, MT, NT>(wsr, ws_off(a.ws, a.ws.u2T), ldm32, ntile0, grow32, lane, acc);
     // the folded out-Dense's fragments: fetched after the l1 result's stores (held
@@ -509,8 +526,10 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (!((mask2 >> ((m * NT + n) * 4 + r)) & 1u)) acc[m][n][r] = 0.f;
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (CARRY) acc[m][n][r] *= mish_gradf(hk2[m][n][r]);
+                else if (!((mask2 >> ((m * NT + n) * 4 + r)) & 1u)) acc[m][n][r] = 0.f;
+            }
     store_acc_lds<P, MT, NT>(tA, ldh, ntile0, lane, acc);
     store_accT<P, MT, NT>(wsr, ws_off(a.ws, a.ws.dh2T), ldm32, ntile0, grow32, lane, acc);
     lds_sync();
@@ -524,9 +543,13 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const bool on = (mask1 >> ((m * NT + n) * 4 + r)) & 1u;
                 const float dh3 = P::tof(tB[(m * 16 + crow(lane, r)) * ldh + (ntile0 + n) * 16 + ccol(lane)]);
-                acc[m][n][r] = dh3 + (on ? acc[m][n][r] : 0.f);
+                if constexpr (CARRY) {
+                    acc[m][n][r] = dh3 + acc[m][n][r] * mish_gradf(hk1[m][n][r]);
+                } else {
+                    const bool on = (mask1 >> ((m * NT + n) * 4 + r)) & 1u;
+                    acc[m][n][r] = dh3 + (on ? acc[m][n][r] : 0.f);
+                }
             }
     store_accT<P, MT, NT>(wsr, ws_off(a.ws, a.ws.dh1T), ldm32, ntile0, grow32, lane, acc);
     PHASE(10);
@@ -746,13 +769,13 @@ __device__ __forceinline__ void critic_rowtile_body(const CriticArgs& a) {
 
 // Kernel entry points. The *_o4 forms cap registers at 128 (4 waves per SIMD: two 8-wave row
 // tiles per CU) at the price of a few spills; which form runs is chosen per launch (row_tile_cfg).
-template <class P, int MT, int NT, int NO, int KSI, bool TRAIN, int WAVES>
+template <class P, int MT, int NT, int NO, int KSI, bool TRAIN, int WAVES, int ACT>
 __global__ __launch_bounds__(64 * WAVES) void actor_rowtile_kernel(ActorArgs a) {
-    actor_rowtile_body<P, MT, NT, NO, KSI, TRAIN, WAVES>(a);
+    actor_rowtile_body<P, MT, NT, NO, KSI, TRAIN, WAVES, ACT>(a);
 }
-template <class P, int MT, int NT, int NO, int KSI, bool TRAIN, int WAVES>
+template <class P, int MT, int NT, int NO, int KSI, bool TRAIN, int WAVES, int ACT>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4))) void actor_rowtile_kernel_o4(ActorArgs a) {
-    actor_rowtile_body<P, MT, NT, NO, KSI, TRAIN, WAVES>(a);
+    actor_rowtile_body<P, MT, NT, NO, KSI, TRAIN, WAVES, ACT>(a);
 }
 template <class P, int MT, int NT, bool TRAIN, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void critic_rowtile_kernel(CriticArgs a) {
@@ -776,7 +799,7 @@ static RowTileCfg row_tile_cfg() { return RowTileCfg{0, 1}; }
 // dry (every launcher below): run the instantiation's host checks only and launch nothing. The
 // entries of several launches (dppo_ppo_minibatch, dppo_pretrain_minibatch) ask first, so a geometry
 // without an instantiation is rejected before their outputs are zeroed
-template <class P, int MT, int NT, int NO, int KSI, bool TRAIN, int WAVES, bool O4>
+template <class P, int MT, int NT, int NO, int KSI, bool TRAIN, int WAVES, bool O4, int ACT>
 static int launch_actor_t(const ActorArgs& a, hipStream_t s, bool dry) {
     if (a.L.ks_in != KSI || a.L.ks_h != ksh_for<P>(NT, WAVES) || a.L.ks_out_t != 2 || a.L.ks_h != WAVES * nok_for<P>(NT))
         return dppo_set_error(DPPO_EUNSUPPORTED, "actor row tile: layout does not match the instantiation");
@@ -787,7 +810,9 @@ static int launch_actor_t(const ActorArgs& a, hipStream_t s, bool dry) {
     if (part_bytes > tb_bytes) return dppo_set_error(DPPO_EUNSUPPORTED, "actor: partial buffer does not fit");
     if (S.total > 160 * 1024) return dppo_set_error(DPPO_EUNSUPPORTED, "actor row tile needs %zu B LDS", S.total);
     if (dry) return DPPO_OK;
-    auto k = O4 ? actor_rowtile_kernel_o4<P, MT, NT, NO, KSI, TRAIN, WAVES> : actor_rowtile_kernel<P, MT, NT, NO, KSI, TRAIN, WAVES>;
+    void (*k)(ActorArgs);   // only the form the launch asks for is instantiated
+    if constexpr (O4) k = actor_rowtile_kernel_o4<P, MT, NT, NO, KSI, TRAIN, WAVES, ACT>;
+    else k = actor_rowtile_kernel<P, MT, NT, NO, KSI, TRAIN, WAVES, ACT>;
     { const int rc_ = dppo_func_lds((const void*)k, (size_t)S.total); if (rc_) return rc_; }
     // TRAIN mode covers every row of the 64-padded feature-major images (padding rows get
     // finite activations and zero gradients), so the dW kernel never reads unwritten memory
@@ -801,24 +826,26 @@ static int launch_actor_t(const ActorArgs& a, hipStream_t s, bool dry) {
     return DPPO_OK;
 }
 
-template <class P, int MT, int NT, int NO, int KSI, int WAVES, bool O4>
+template <class P, int MT, int NT, int NO, int KSI, int WAVES, bool O4, int ACT>
 static int launch_actor_m(const ActorArgs& a, hipStream_t s, bool dry) {
-    return (a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN) ? launch_actor_t<P, MT, NT, NO, KSI, true, WAVES, O4>(a, s, dry)
-                                : launch_actor_t<P, MT, NT, NO, KSI, false, WAVES, O4>(a, s, dry);
+    return (a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN) ? launch_actor_t<P, MT, NT, NO, KSI, true, WAVES, O4, ACT>(a, s, dry)
+                                : launch_actor_t<P, MT, NT, NO, KSI, false, WAVES, O4, ACT>(a, s, dry);
 }
 
 // bf16: 64-row tiles, 16 waves (half the weight stream per row of 32-row tiles; LDS-limited);
-// fp32: 32-row tiles, 16 waves
-template <class P, int MT, int WAVES, bool O4 = false>
+// fp32: 32-row tiles, 16 waves (a Mish actor: 8 waves, whose 256 registers hold h1 and h2; the same widths)
+template <class P, int MT, int WAVES, bool O4 = false, int ACT = DPPO_ACT_RELU>
 static int dispatch_actor(const ActorArgs& a, hipStream_t s, bool dry) {
     const int NT = a.H / (16 * WAVES), NO = dppo_cdiv(a.XD, 16), KSI = a.L.ks_in;
 #define DPPO_ACTOR_CASE(nt, no, ksi) \
-    if (NT == nt && NO == no && KSI == ksi) return launch_actor_m<P, MT, nt, no, ksi, WAVES, O4>(a, s, dry);
+    if (NT == nt && NO == no && KSI == ksi) return launch_actor_m<P, MT, nt, no, ksi, WAVES, O4, ACT>(a, s, dry);
     if constexpr (P::KG == 32 && WAVES == 16) {   // bf16, H = 512 on 16 waves
         DPPO_ACTOR_CASE(2, 1, 2) DPPO_ACTOR_CASE(2, 2, 2) DPPO_ACTOR_CASE(2, 1, 4) DPPO_ACTOR_CASE(2, 2, 4)
     } else if constexpr (P::KG == 32) {           // bf16, 8 waves: the in-layer is 2 k-steps up to 64 inputs, 4 up to 128
         DPPO_ACTOR_CASE(4, 1, 2) DPPO_ACTOR_CASE(4, 2, 2) DPPO_ACTOR_CASE(4, 1, 4) DPPO_ACTOR_CASE(4, 2, 4)
         DPPO_ACTOR_CASE(2, 1, 2) DPPO_ACTOR_CASE(2, 2, 2) DPPO_ACTOR_CASE(2, 1, 4) DPPO_ACTOR_CASE(2, 2, 4)
+    } else if constexpr (WAVES == 8) {   // fp32 Mish, H = 512 on 8 waves
+        DPPO_ACTOR_CASE(4, 1, 4) DPPO_ACTOR_CASE(4, 2, 4)
     } else {                       // fp32: 33..64 inputs -> 4 k-steps
         DPPO_ACTOR_CASE(4, 1, 4) DPPO_ACTOR_CASE(4, 2, 4) DPPO_ACTOR_CASE(2, 1, 4) DPPO_ACTOR_CASE(2, 2, 4)
     }
@@ -839,7 +866,11 @@ static int64_t actor_device_cus() {
 
 // The tile decision, host arithmetic only: launch_actor_rowtile and the plan query (dppo_ppo_plan)
 // both take it from here. The 2-byte operand policies (bf16, fp16) share the tile configurations
-ActorTilePlan actor_tile_plan(int precision, int H, int XD, int64_t rows) {
+ActorTilePlan actor_tile_plan(int precision, int H, int XD, int64_t rows, int act) {
+    // Mish: the TRAIN tile carries h1 and h2 (8 MT NT registers) from the forward to the backward. The
+    // 16-wave tiles (128 registers per lane: the 64-row 2-byte tile already spills a little, the fp32 tile
+    // sits at 108) have no room for them, so a Mish actor runs 32 rows on 8 waves whatever the row count
+    if (act == DPPO_ACT_MISH) return ActorTilePlan{2, 8};
     // fp32: 32-row tiles on 16 waves (four per SIMD behind the 16x16x4 MFMA chains): update 41.5 ->
     // 40.5 ms per iteration against 8 waves (profiles/r06zz_f32_tile_16wave_ab.txt)
     if (!dppo_prec_2b(precision)) return ActorTilePlan{2, 16};
@@ -866,19 +897,22 @@ ActorTilePlan actor_tile_plan(int precision, int H, int XD, int64_t rows) {
 }
 
 template <class P2>
-static int launch_actor_2b(const ActorArgs& a, const ActorTilePlan& p, hipStream_t s, bool dry) {
-    if (p.mt == 4 && p.waves == 16) return dispatch_actor<P2, 4, 16>(a, s, dry);
-    if (p.mt == 2 && p.waves == 8) return dispatch_actor<P2, 2, 8>(a, s, dry);
+static int launch_actor_2b(const ActorArgs& a, const ActorTilePlan& p, int act, hipStream_t s, bool dry) {
+    if (act == DPPO_ACT_MISH && p.mt == 2 && p.waves == 8) return dispatch_actor<P2, 2, 8, false, DPPO_ACT_MISH>(a, s, dry);
+    if (act == DPPO_ACT_RELU && p.mt == 4 && p.waves == 16) return dispatch_actor<P2, 4, 16>(a, s, dry);
+    if (act == DPPO_ACT_RELU && p.mt == 2 && p.waves == 8) return dispatch_actor<P2, 2, 8>(a, s, dry);
     return dppo_set_error(DPPO_EUNSUPPORTED, "actor: no %d-row tile on %d waves", 16 * p.mt, p.waves);
 }
 
 int launch_actor_rowtile(const ActorArgs& a, int precision, hipStream_t s, bool dry) {
     // TRAIN modes cover the 64-padded images (launch_actor_t), the others the rows given
     const int64_t rows = (a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN) ? (int64_t)a.ws.ldm : a.nrows;
-    const ActorTilePlan p = actor_tile_plan(precision, a.H, a.XD, rows);
-    if (precision == DPPO_BF16) return launch_actor_2b<PolicyBF16>(a, p, s, dry);
-    if (precision == DPPO_F16) return launch_actor_2b<PolicyF16>(a, p, s, dry);
-    if (p.mt != 2 || p.waves != 16)
+    const int act = dppo_actor_image_act(a.packed);   // the image's activation picks the instantiation
+    const ActorTilePlan p = actor_tile_plan(precision, a.H, a.XD, rows, act);
+    if (precision == DPPO_BF16) return launch_actor_2b<PolicyBF16>(a, p, act, s, dry);
+    if (precision == DPPO_F16) return launch_actor_2b<PolicyF16>(a, p, act, s, dry);
+    if (act == DPPO_ACT_MISH && p.mt == 2 && p.waves == 8) return dispatch_actor<PolicyF32, 2, 8, false, DPPO_ACT_MISH>(a, s, dry);
+    if (act != DPPO_ACT_RELU || p.mt != 2 || p.waves != 16)
         return dppo_set_error(DPPO_EUNSUPPORTED, "actor: no fp32 %d-row tile on %d waves", 16 * p.mt, p.waves);
     return dispatch_actor<PolicyF32, 2, 16>(a, s, dry);
 }

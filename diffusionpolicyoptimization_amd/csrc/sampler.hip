@@ -133,7 +133,15 @@ static size_t stream_lds_total(const SampleArgs& a, int NO, int SW) {
     return o;
 }
 
-template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, bool RES>
+// the block's activation (ACT: DPPO_ACT_RELU or DPPO_ACT_MISH, the images' attribute) in fp32, rounded by
+// the caller where relu's result is rounded
+template <int ACT>
+__device__ inline float stream_act(float x) {
+    if constexpr (ACT == DPPO_ACT_MISH) return mishf(x);
+    else return fmaxf(x, 0.f);
+}
+
+template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, bool RES, int ACT>
 __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
     SPHASE_START;
     using AT = typename P::AT;
@@ -296,12 +304,12 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 h1[0][n][r] += bv;
-                tA[crow(lane, r) * ldh + col] = P::cvt(fmaxf(h1[0][n][r], 0.f));
+                tA[crow(lane, r) * ldh + col] = P::cvt(stream_act<ACT>(h1[0][n][r]));
             }
         }
         lds_sync();
         SPHASE(2);
-        // c) l1: relu(h1) W_l1 + b -> relu -> tB   (pre-activation block, mlp.py:192-193,202-203)
+        // c) l1: act(h1) W_l1 + b -> act -> tB   (pre-activation block, mlp.py:192-193,202-203)
         gemm_res<P, NT, KSH, RK, QD>(tA, ldh, s_l1(PK).W, r_l1, ntile0, acc, lane, R,
                                      RES ? SNext{s_l2(PK), s_l1(PKn)} : SNext{s_l2(PK), s_in(PKn)});
 #pragma unroll
@@ -309,11 +317,11 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
             const int col = (ntile0 + n) * 16 + ccol(lane);
             const float bv = bb[H + col];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) tB[crow(lane, r) * ldh + col] = P::cvt(fmaxf(acc[0][n][r] + bv, 0.f));
+            for (int r = 0; r < 4; ++r) tB[crow(lane, r) * ldh + col] = P::cvt(stream_act<ACT>(acc[0][n][r] + bv));
         }
         lds_sync();
         SPHASE(3);
-        // d) l2: relu(h2) W_l2 + b + h1 (residual, mlp.py:206) -> tA; the stream moves on to the
+        // d) l2: act(h2) W_l2 + b + h1 (residual, mlp.py:206) -> tA; the stream moves on to the
         //    next denoising step (possibly the other actor)
         gemm_res<P, NT, KSH, RK, QD>(tB, ldh, s_l2(PK).W, r_l2, ntile0, acc, lane, R,
                                      RES ? SNext{s_l1(PKn), s_l2(PKn)} : SNext{s_in(PKn), s_l1(PKn)});
@@ -388,14 +396,14 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
 // dry (every launcher below): run the instantiation's host checks only and launch nothing. sample_impl
 // and dppo_sample_step ask first, so a geometry without an instantiation is refused before anything is
 // enqueued (deferred tables, the observation's copy)
-template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, bool RES>
+template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, bool RES, int ACT>
 static int launch_sample_q(const SampleArgs& a, hipStream_t s, bool dry) {
     if (a.L.ks_h != ksh_for<P>(NT, SW) || a.L.ks_in != KSI || a.L.ks_h % SW != 0)
         return dppo_set_error(DPPO_EUNSUPPORTED, "sampler: hidden %d not supported at this precision", a.H);
     const size_t lds = stream_lds_total<P>(a, NO, SW);
     if (lds > 160 * 1024) return dppo_set_error(DPPO_EUNSUPPORTED, "sampler needs %zu B of LDS", lds);
     if (dry) return DPPO_OK;
-    auto k = sample_kernel<P, NT, NO, KSI, INJ, QD, SW, RK, RES>;
+    auto k = sample_kernel<P, NT, NO, KSI, INJ, QD, SW, RK, RES, ACT>;
     { const int rc_ = dppo_func_lds((const void*)k, (size_t)lds); if (rc_) return rc_; }
     DppoKtScope kt(KT_SAMPLER, s);
     hipLaunchKernelGGL(k, dim3(dppo_cdiv(a.E, 16)), dim3(SW * 64), lds, s, a);
@@ -415,25 +423,25 @@ static char sampler_cfg() {
     return c;
 }
 
-template <class P, int NT16, int NO, int KSI, bool INJ>   // NT16: n-tiles per wave of a 16-wave layout
+template <class P, int NT16, int NO, int KSI, bool INJ, int ACT>   // NT16: n-tiles per wave of a 16-wave layout
 static int launch_sample_k(const SampleArgs& a, hipStream_t s, bool dry) {
     constexpr StreamGeom g = stream_geom(P::KG == 32, NT16 * 256);
-    return launch_sample_q<P, NT16 * 16 / g.SW, NO, KSI, INJ, g.QD, g.SW, g.RK, g.RES>(a, s, dry);
+    return launch_sample_q<P, NT16 * 16 / g.SW, NO, KSI, INJ, g.QD, g.SW, g.RK, g.RES, ACT>(a, s, dry);
 }
 
-template <class P, int NT, int NO, int KSI>
+template <class P, int NT, int NO, int KSI, int ACT>
 static int launch_sample(const SampleArgs& a, hipStream_t s, bool dry) {
-    if (a.noise) return launch_sample_k<P, NT, NO, KSI, true>(a, s, dry);
-    return launch_sample_k<P, NT, NO, KSI, false>(a, s, dry);
+    if (a.noise) return launch_sample_k<P, NT, NO, KSI, true, ACT>(a, s, dry);
+    return launch_sample_k<P, NT, NO, KSI, false, ACT>(a, s, dry);
 }
 
-template <class P>
+template <class P, int ACT>
 static int dispatch_sample(const SampleArgs& a, hipStream_t s, bool dry) {
     const int NT = a.H / (16 * 16);   // n-tiles per wave of the 16-wave layout
     const int NO = dppo_cdiv(a.XD, 16);
     const int KSI = a.L.ks_in;
 #define DPPO_SAMPLE_CASE(nt, no, ksi) \
-    if (NT == nt && NO == no && KSI == ksi) return launch_sample<P, nt, no, ksi>(a, s, dry);
+    if (NT == nt && NO == no && KSI == ksi) return launch_sample<P, nt, no, ksi, ACT>(a, s, dry);
     if constexpr (P::KG == 32) {   // bf16: H = 512 (NT 2)
         DPPO_SAMPLE_CASE(2, 1, 2) DPPO_SAMPLE_CASE(2, 2, 2) DPPO_SAMPLE_CASE(2, 1, 4) DPPO_SAMPLE_CASE(2, 2, 4)
     } else {                       // fp32: H = 512 or 256
@@ -463,9 +471,23 @@ extern "C" int dppo_sampler_stream_bytes(const dppo_dims* d, int precision, int6
     return DPPO_OK;
 }
 
-static int dispatch_stream(const SampleArgs& a, int precision, hipStream_t s, bool dry) {
-    return precision == DPPO_BF16 ? dispatch_sample<PolicyBF16>(a, s, dry)
-         : precision == DPPO_F16  ? dispatch_sample<PolicyF16>(a, s, dry) : dispatch_sample<PolicyF32>(a, s, dry);
+template <int ACT>
+static int dispatch_stream_a(const SampleArgs& a, int precision, hipStream_t s, bool dry) {
+    return precision == DPPO_BF16 ? dispatch_sample<PolicyBF16, ACT>(a, s, dry)
+         : precision == DPPO_F16  ? dispatch_sample<PolicyF16, ACT>(a, s, dry) : dispatch_sample<PolicyF32, ACT>(a, s, dry);
+}
+static int dispatch_stream(const SampleArgs& a, int precision, int act, hipStream_t s, bool dry) {
+    return act == DPPO_ACT_MISH ? dispatch_stream_a<DPPO_ACT_MISH>(a, precision, s, dry)
+                                : dispatch_stream_a<DPPO_ACT_RELU>(a, precision, s, dry);
+}
+
+// The activation of a sampler launch: its two images' (ReLU where none was recorded), which must agree:
+// one instantiation runs both actors' steps
+static int sample_act(const void* packed_base, const void* packed_ft, int* act) {
+    *act = dppo_actor_image_act(packed_ft);
+    DPPO_CHECK(dppo_actor_image_act(packed_base) == *act,
+               "dppo_sample: the base and the fine-tuned actor images carry different activations");
+    return DPPO_OK;
 }
 
 // a's dimension fields and layout from the checked dims
@@ -476,9 +498,9 @@ static void sample_geometry(const Dims& D, int precision, SampleArgs& a) {
 
 // Does a kernel take the shape (a: sample_geometry's fields and E)? The split kernel where its plan
 // does, else the streaming kernel's instantiation checks (dry); launches and enqueues nothing.
-static int sample_supported(const SampleArgs& a, int precision, bool* split) {
+static int sample_supported(const SampleArgs& a, int precision, int act, bool* split) {
     *split = sampler_cfg() == 'x' && split_plan(precision, a.H, a.XD, a.SD, a.E, a.K, a.KF).P > 0;
-    return *split ? DPPO_OK : dispatch_stream(a, precision, nullptr, true);
+    return *split ? DPPO_OK : dispatch_stream(a, precision, act, nullptr, true);
 }
 
 // The one launch path: `a` carries the caller's pointers and scalars (fields it does not use are
@@ -494,8 +516,11 @@ static int sample_impl(const dppo_dims* d, int precision, SampleArgs a, void* st
     DPPO_CHECK(a.packed_base && a.packed_ft && a.sched && (a.cond || a.cond_tagged) && a.actions,
                "dppo_sample: null pointer argument");
     sample_geometry(D, precision, a);
+    int act = DPPO_ACT_RELU;
+    rc = sample_act(a.packed_base, a.packed_ft, &act);
+    if (rc) return rc;
     bool split = false;
-    rc = sample_supported(a, precision, &split);
+    rc = sample_supported(a, precision, act, &split);
     if (rc) return rc;
     // tables an optimizer step deferred (DPPO_STEP_DEFER_SAMPLER_TABLES) are re-derived first, on this stream
     rc = dppo_refresh_sampler_tables(a.packed_ft, stream);
@@ -504,10 +529,10 @@ static int sample_impl(const dppo_dims* d, int precision, SampleArgs a, void* st
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (split) {
-        rc = launch_sample_split(a, precision, s);
+        rc = launch_sample_split(a, precision, act, s);
         if (rc != DPPO_EUNSUPPORTED) return rc;
     }
-    return dispatch_stream(a, precision, s, false);
+    return dispatch_stream(a, precision, act, s, false);
 }
 
 // the three plan queries: dims checked and the split kernel's plan looked up once ({0, ...} under
@@ -602,8 +627,11 @@ extern "C" int dppo_sample_step(const dppo_dims* d, int precision, const void* p
         SampleArgs q = {};
         q.E = n_envs;
         sample_geometry(D, precision, q);
+        int act = DPPO_ACT_RELU;
+        rc = sample_act(packed_base, packed_ft, &act);
+        if (rc) return rc;
         bool split = false;
-        rc = sample_supported(q, precision, &split);
+        rc = sample_supported(q, precision, act, &split);
         if (rc) return rc;
         DPPO_HIP(hipMemcpyAsync(cond, cond_host, sizeof(float) * (size_t)n_envs * D.SD, hipMemcpyHostToDevice, s));
         rc = dppo_sample(d, precision, packed_base, packed_ft, sched, cond, n_envs, nullptr, nullptr, seed, call_id,

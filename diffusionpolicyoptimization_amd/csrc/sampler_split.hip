@@ -131,6 +131,13 @@ constexpr int S4_L1D = 1;
 // relu as one v_max_i32 on the bits (fmaxf(x, 0) canonicalises its MFMA-produced input first: two
 // VALU ops per element); negative values and -0 map to +0, as fmaxf(x, 0) does up to the sign of 0
 __device__ inline float relu_f(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
+// the block's activation at its two sites (ACT: DPPO_ACT_RELU or DPPO_ACT_MISH, the images' attribute),
+// in fp32; the caller rounds it where relu's result is rounded
+template <int ACT>
+__device__ inline float act_f(float x) {
+    if constexpr (ACT == DPPO_ACT_MISH) return mishf(x);
+    else return relu_f(x);
+}
 // LDS_READY(...): an empty asm statement that "uses" its operands: every one of them is loaded
 // before it, so their loads issue together and pay one LDS round trip (left alone, hipcc sank each
 // read next to its use)
@@ -168,7 +175,7 @@ __device__ inline float dpp_f32(float v) {
 // PM = members per group: 2 (the 2-byte default, S4_P: 1/2 of l1 per member, 2 l1 n-tiles per wave,
 // a 2-member exchange; possible once l2 is folded away), 4, or 8 (fp32 with SWV = 4: one wave per
 // SIMD, one l1 n-tile each; the member sum adds a third DPP level)
-template <class Pol, int XQ, int KX, bool INJ, int SWV, int PM = 4>
+template <class Pol, int XQ, int KX, bool INJ, int SWV, int PM, int ACT>
 __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
     constexpr int P = PM;
     static_assert(P == 2 || P == 4 || P == 8, "members per group");
@@ -559,11 +566,11 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
                 const int f = 16 * (NTI * wave + n) + 4 * jq;
                 if constexpr (TWO) {
                     u32x2 pk;
-                    pk[0] = pack_bf16x2(relu_f(h1[n][0]), relu_f(h1[n][1]));
-                    pk[1] = pack_bf16x2(relu_f(h1[n][2]), relu_f(h1[n][3]));
+                    pk[0] = pack_bf16x2(act_f<ACT>(h1[n][0]), act_f<ACT>(h1[n][1]));
+                    pk[1] = pack_bf16x2(act_f<ACT>(h1[n][2]), act_f<ACT>(h1[n][3]));
                     *(u32x2*)(u1 + env * ldh + f) = pk;
                 } else {
-                    *(f32x4*)(u1 + env * ldh + f) = f32x4{relu_f(h1[n][0]), relu_f(h1[n][1]), relu_f(h1[n][2]), relu_f(h1[n][3])};
+                    *(f32x4*)(u1 + env * ldh + f) = f32x4{act_f<ACT>(h1[n][0]), act_f<ACT>(h1[n][1]), act_f<ACT>(h1[n][2]), act_f<ACT>(h1[n][3])};
                 }
             }
         }
@@ -623,13 +630,13 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
             for (int tt = 0; tt < NL1; ++tt) {
                 u32x4 ba;
                 if constexpr (TWO) {
-                    ba[0] = pack_bf16x2(relu_f(acc[tt][0]), relu_f(acc[tt][1]));
-                    ba[1] = pack_bf16x2(relu_f(acc[tt][2]), relu_f(acc[tt][3]));
+                    ba[0] = pack_bf16x2(act_f<ACT>(acc[tt][0]), act_f<ACT>(acc[tt][1]));
+                    ba[1] = pack_bf16x2(act_f<ACT>(acc[tt][2]), act_f<ACT>(acc[tt][3]));
                     ba[2] = ba[0];
                     ba[3] = ba[1];
                 } else {
-                    ba = __builtin_bit_cast(u32x4, f32x4{relu_f(acc[tt][0]), relu_f(acc[tt][1]), relu_f(acc[tt][2]),
-                                                         relu_f(acc[tt][3])});
+                    ba = __builtin_bit_cast(u32x4, f32x4{act_f<ACT>(acc[tt][0]), act_f<ACT>(acc[tt][1]), act_f<ACT>(acc[tt][2]),
+                                                         act_f<ACT>(acc[tt][3])});
                 }
 #pragma unroll
                 for (int n = 0; n < NO; ++n) po[n] = Pol::mma(rfold[tt][n], ba, po[n]);
@@ -892,13 +899,13 @@ int device_cus() {
 // profiles/r05d_sampler_xreg_w4_ab.txt)
 constexpr int S4_WAVES = 8;
 
-template <class Pol, int XQ, int KX, bool INJ, int SWV, int PM>
+template <class Pol, int XQ, int KX, bool INJ, int SWV, int PM, int ACT>
 int launch_split4_kw(const SplitArgs& sa, hipStream_t s) {
     // the finishing lanes are the members' lanes: a wave's 16 x XD / SWV coordinates in (64 / PM)
     // slots at most PM deep
     constexpr int NVW = 16 * 4 * XQ / SWV, KW = (NVW + 64 / PM - 1) / (64 / PM);
     static_assert(KW <= PM, "the waves of a member do not cover XD");
-    auto k = sample_split4_kernel<Pol, XQ, KX, INJ, SWV, PM>;
+    auto k = sample_split4_kernel<Pol, XQ, KX, INJ, SWV, PM, ACT>;
     const SampleArgs& a = sa.a;
     const size_t lds = split_lds_total(sizeof(typename Pol::AT), KX, a.XD, a.SD, a.K, SWV);
     if (lds > 160 * 1024) return dppo_set_error(DPPO_EUNSUPPORTED, "split sampler needs %zu B of LDS", lds);
@@ -917,9 +924,9 @@ constexpr int S4_P = 2;
 // so halving each SIMD's l1 share pays for the 8-member exchange; P = 4 of 8 waves was the alternative)
 constexpr int F32_P = 8, F32_WAVES = 4;
 
-template <class Pol, int XQ, int KX, bool INJ>
+template <class Pol, int XQ, int KX, bool INJ, int ACT>
 int launch_split4_k(const SplitArgs& sa, hipStream_t s) {
-    return launch_split4_kw<Pol, XQ, KX, INJ, S4_WAVES, S4_P>(sa, s);
+    return launch_split4_kw<Pol, XQ, KX, INJ, S4_WAVES, S4_P, ACT>(sa, s);
 }
 
 }  // namespace
@@ -949,7 +956,9 @@ SplitPlan split_plan(int precision, int H, int XD, int SD, int E, int K, int KF)
     return {P, dual, 8 * P * ((G + 7) / 8) * (dual ? 2 : 1), cus};
 }
 
-int launch_sample_split(const SampleArgs& a, int precision, hipStream_t s) {
+namespace {
+template <int ACT>
+int launch_sample_split_a(const SampleArgs& a, int precision, hipStream_t s) {
     const SplitPlan plan = split_plan(precision, a.H, a.XD, a.SD, a.E, a.K, a.KF);
     const int P = plan.P;
     if (!P) return DPPO_EUNSUPPORTED;
@@ -964,24 +973,30 @@ int launch_sample_split(const SampleArgs& a, int precision, hipStream_t s) {
     if (precision == DPPO_F32) {   // split_plan took XD = 12 only
         if (a.XD != 12 || P != F32_P) return DPPO_EUNSUPPORTED;
         if (a.XD + a.SD > 16)
-            return inj ? launch_split4_kw<PolicyF32, 3, 2, true, F32_WAVES, F32_P>(sa, s)
-                       : launch_split4_kw<PolicyF32, 3, 2, false, F32_WAVES, F32_P>(sa, s);
-        return inj ? launch_split4_kw<PolicyF32, 3, 1, true, F32_WAVES, F32_P>(sa, s)
-                   : launch_split4_kw<PolicyF32, 3, 1, false, F32_WAVES, F32_P>(sa, s);
+            return inj ? launch_split4_kw<PolicyF32, 3, 2, true, F32_WAVES, F32_P, ACT>(sa, s)
+                       : launch_split4_kw<PolicyF32, 3, 2, false, F32_WAVES, F32_P, ACT>(sa, s);
+        return inj ? launch_split4_kw<PolicyF32, 3, 1, true, F32_WAVES, F32_P, ACT>(sa, s)
+                   : launch_split4_kw<PolicyF32, 3, 1, false, F32_WAVES, F32_P, ACT>(sa, s);
     }
     const bool kx2 = a.XD + a.SD > 32;
     switch (a.XD / 4) {
 #define DPPO_SPLIT4_CASE(xq)                                                                                 \
     case xq:                                                                                                 \
         if (kx2) {                                                                                           \
-            if (f16) return inj ? launch_split4_k<PolicyF16, xq, 2, true>(sa, s) : launch_split4_k<PolicyF16, xq, 2, false>(sa, s); \
-            return inj ? launch_split4_k<PolicyBF16, xq, 2, true>(sa, s) : launch_split4_k<PolicyBF16, xq, 2, false>(sa, s); \
+            if (f16) return inj ? launch_split4_k<PolicyF16, xq, 2, true, ACT>(sa, s) : launch_split4_k<PolicyF16, xq, 2, false, ACT>(sa, s); \
+            return inj ? launch_split4_k<PolicyBF16, xq, 2, true, ACT>(sa, s) : launch_split4_k<PolicyBF16, xq, 2, false, ACT>(sa, s); \
         }                                                                                                    \
-        if (f16) return inj ? launch_split4_k<PolicyF16, xq, 1, true>(sa, s) : launch_split4_k<PolicyF16, xq, 1, false>(sa, s); \
-        return inj ? launch_split4_k<PolicyBF16, xq, 1, true>(sa, s) : launch_split4_k<PolicyBF16, xq, 1, false>(sa, s);
+        if (f16) return inj ? launch_split4_k<PolicyF16, xq, 1, true, ACT>(sa, s) : launch_split4_k<PolicyF16, xq, 1, false, ACT>(sa, s); \
+        return inj ? launch_split4_k<PolicyBF16, xq, 1, true, ACT>(sa, s) : launch_split4_k<PolicyBF16, xq, 1, false, ACT>(sa, s);
         DPPO_SPLIT4_CASE(1) DPPO_SPLIT4_CASE(2) DPPO_SPLIT4_CASE(3) DPPO_SPLIT4_CASE(4)
         DPPO_SPLIT4_CASE(5) DPPO_SPLIT4_CASE(6) DPPO_SPLIT4_CASE(7) DPPO_SPLIT4_CASE(8)
 #undef DPPO_SPLIT4_CASE
         default: return DPPO_EUNSUPPORTED;
     }
+}
+}  // namespace
+
+int launch_sample_split(const SampleArgs& a, int precision, int act, hipStream_t s) {
+    return act == DPPO_ACT_MISH ? launch_sample_split_a<DPPO_ACT_MISH>(a, precision, s)
+                                : launch_sample_split_a<DPPO_ACT_RELU>(a, precision, s);
 }

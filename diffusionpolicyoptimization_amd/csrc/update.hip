@@ -214,7 +214,9 @@ extern "C" int dppo_pack_all(const dppo_dims* d, int precision, const float* act
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
     DPPO_CHECK(!packed_actor == !actor_params && !packed_critic == !critic_params,
                "dppo_pack_all: a packed image needs its parameters");
-    return dppo_pack_models(D, precision, actor_params, packed_actor, critic_params, packed_critic, (hipStream_t)stream);
+    rc = dppo_pack_models(D, precision, actor_params, packed_actor, critic_params, packed_critic, (hipStream_t)stream);
+    if (rc == DPPO_OK && packed_actor) dppo_actor_image_set_act(packed_actor, DPPO_ACT_RELU);   // = dppo_pack_actor
+    return rc;
 }
 
 extern "C" int dppo_feistel_permute(int64_t first, int64_t count, int64_t n, uint64_t seed, int epoch, int64_t* out,
@@ -348,16 +350,22 @@ static void critic_dw_items(const Dims& D, const PpoWorkspace& ws, float* gc, DW
 }
 
 extern "C" int dppo_ppo_plan(const dppo_dims* d, int precision, int rows, int mode, int* out) {
+    return dppo_ppo_plan_act(d, precision, DPPO_ACT_RELU, rows, mode, out);
+}
+
+extern "C" int dppo_ppo_plan_act(const dppo_dims* d, int precision, int activation, int rows, int mode, int* out) {
     Dims D;
     int rc = dppo_check_dims(d, &D);
     if (rc) return rc;
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
+    DPPO_CHECK(dppo_act_ok(activation), "dppo_ppo_plan_act: bad activation %d", activation);
     DPPO_CHECK(out && rows > 0, "dppo_ppo_plan: bad arguments");
     DPPO_CHECK(mode == DPPO_PLAN_TRAIN || mode == DPPO_PLAN_PRETRAIN || mode == DPPO_PLAN_LOGPROB,
                "dppo_ppo_plan: mode must be 0 (train), 1 (pretrain) or 2 (logprob)");
     const PpoWorkspace ws = make_ppo_workspace(D, precision, rows, nullptr);
     // the row counts launch_actor_rowtile sees: the 64-padded images, or the log-prob pass's rows as given
-    const ActorTilePlan t = actor_tile_plan(precision, D.H, D.XD, mode == DPPO_PLAN_LOGPROB ? (int64_t)rows : (int64_t)ws.ldm);
+    const ActorTilePlan t = actor_tile_plan(precision, D.H, D.XD, mode == DPPO_PLAN_LOGPROB ? (int64_t)rows : (int64_t)ws.ldm,
+                                            activation);
     out[0] = 16 * t.mt;
     out[1] = t.waves;
     out[2] = out[3] = out[4] = out[5] = 0;

@@ -80,7 +80,8 @@ class DiffusionModel:
         self.pre_dims = ops.ModelDims(obs_dim=self.obs_dim, action_dim=self.action_dim,
                                       horizon_steps=self.horizon_steps, cond_steps=net.cond_dim // self.obs_dim,
                                       time_dim=net.time_dim, actor_hidden=net.hidden,
-                                      denoising_steps=self.denoising_steps, ft_denoising_steps=1, time_stride=1)
+                                      denoising_steps=self.denoising_steps, ft_denoising_steps=1, time_stride=1,
+                                      activation=net.activation_type)
         self.pre_spec = ops.actor_param_spec(self.pre_dims)
         path = self.network_path
         if path is not None and not os.path.exists(str(path)):

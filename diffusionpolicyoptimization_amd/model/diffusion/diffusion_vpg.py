@@ -54,7 +54,7 @@ class VPGDiffusion(DiffusionModel):
                                   horizon_steps=self.horizon_steps, cond_steps=cond_steps, time_dim=actor.time_dim,
                                   actor_hidden=actor.hidden, critic_hidden=critic.hidden,
                                   denoising_steps=self.sampling_steps, ft_denoising_steps=self.ft_denoising_steps,
-                                  time_stride=self.time_stride)
+                                  time_stride=self.time_stride, activation=actor.activation_type)
         self.actor_spec = ops.actor_param_spec(self.dims)
         self.critic_spec = ops.critic_param_spec(self.dims)
         self.n_actor = ops.spec_count(self.actor_spec)

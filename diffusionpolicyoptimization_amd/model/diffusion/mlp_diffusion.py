@@ -16,8 +16,8 @@ class DiffusionMLP:
             raise NotImplementedError("cond_mlp_dims (obs encoder) is not used by the gym fine-tune cfgs")
         if not residual_style:
             raise NotImplementedError("DiffusionMLP(residual_style=False) is not implemented on MI355X")
-        if activation_type != "ReLU":
-            raise NotImplementedError("the actor kernels implement the cfg's ReLU activation")
+        if activation_type not in ("ReLU", "Mish"):
+            raise NotImplementedError(f"activation_type {activation_type!r}: the actor kernels implement ReLU and Mish")
         self.action_dim, self.horizon_steps, self.cond_dim, self.time_dim = action_dim, horizon_steps, cond_dim, time_dim
         self.mlp_dims = list(mlp_dims)
         self.activation_type = activation_type

@@ -30,6 +30,13 @@ class ModelDims:
     denoising_steps: int = 20       # sampling steps (DDIM: ddim_steps)
     ft_denoising_steps: int = 10
     time_stride: int = 1            # diffusion time of sampling row r is r * time_stride (DDIM: K / S)
+    # the actor's activation_type, "ReLU" or "Mish". Python-only: it is no field of dppo_dims; pack_actor
+    # records it with the packed image (dppo_pack_actor_act) and every kernel launch follows the image
+    activation: str = "ReLU"
+
+    def __post_init__(self):
+        if self.activation not in _lib.ACTIVATION:
+            raise ValueError(f"activation must be one of {sorted(_lib.ACTIVATION)}, got {self.activation!r}")
 
     @property
     def xd(self):
@@ -139,6 +146,12 @@ def pack_all(d: ModelDims, precision, actor_params=None, packed_actor=None, crit
     _check(critic_params, (nc,), torch.float32, "critic params")
     _check(packed_critic, (cb,), torch.uint8, "packed critic")
     t = actor_params if actor_params is not None else critic_params
+    if actor_params is not None and d.activation != "ReLU":
+        # dppo_pack_all records ReLU for the actor image (= dppo_pack_actor): a Mish actor packs on its own
+        pack_actor(d, actor_params, precision, out=packed_actor)
+        if critic_params is not None:
+            pack_critic(d, critic_params, precision, out=packed_critic)
+        return
     _lib.call("dppo_pack_all", ctypes.byref(_dims_c(d)), p, ptr(actor_params), ptr(packed_actor), ptr(critic_params),
               ptr(packed_critic), stream_handle(t.device))
 
@@ -361,14 +374,16 @@ def critic_packed_bytes(d: ModelDims, precision):
 
 
 def pack_actor(d: ModelDims, params_flat, precision, out=None):
+    """The packed image of an actor; d.activation is recorded with it (dppo_pack_actor_act) and decides
+    which kernels every later launch on the image runs."""
     p = _prec(precision)
     _check(params_flat, (_n_params(d)[0],), torch.float32, "actor params")
     if out is None:
         out = torch.empty(_packed_bytes(d, p)[0], dtype=torch.uint8, device=params_flat.device)
     else:
         _check(out, (_packed_bytes(d, p)[0],), torch.uint8, "packed actor")
-    _lib.call("dppo_pack_actor", ctypes.byref(_dims_c(d)), p, ptr(params_flat), ptr(out),
-              stream_handle(params_flat.device))
+    _lib.call("dppo_pack_actor_act", ctypes.byref(_dims_c(d)), p, _lib.ACTIVATION[d.activation], ptr(params_flat),
+              ptr(out), stream_handle(params_flat.device))
     return out
 
 
@@ -807,9 +822,11 @@ def ppo_plan(d: ModelDims, precision, rows, mode="train"):
     functions the launchers themselves call): dict(actor_tile_rows (32 or 64), actor_waves,
     dw_chunks_actor, dw_chunk_rows_actor, dw_chunks_critic, dw_chunk_rows_critic). mode: "train"
     (ppo_minibatch), "pretrain" (pretrain_minibatch) or "logprob" (rows = samples x K'); the dW fields
-    are 0 where the mode has no such launch."""
+    are 0 where the mode has no such launch. The plan is d.activation's (dppo_ppo_plan_act): a Mish actor
+    runs the 32-row tile on 8 waves at every row count."""
     out = (ctypes.c_int * 6)()
-    _lib.call("dppo_ppo_plan", ctypes.byref(d.c()), _prec(precision), int(rows), _PLAN_MODES[mode], out)
+    _lib.call("dppo_ppo_plan_act", ctypes.byref(d.c()), _prec(precision), _lib.ACTIVATION[d.activation], int(rows),
+              _PLAN_MODES[mode], out)
     return dict(actor_tile_rows=out[0], actor_waves=out[1], dw_chunks_actor=out[2], dw_chunk_rows_actor=out[3],
                 dw_chunks_critic=out[4], dw_chunk_rows_critic=out[5])
 

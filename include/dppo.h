@@ -112,7 +112,14 @@ typedef struct dppo_dims {
  *   %zu B LDS" otherwise, also before the first launch).
  * An actor rejection fails dppo_logprob, dppo_pretrain_minibatch and dppo_ppo_minibatch; a critic
  * rejection dppo_critic_forward and dppo_ppo_minibatch. tests/test_update_surface_gpu.py pins the
- * table, tests/test_update_ft_steps_gpu.py its K' lines. */
+ * table, tests/test_update_ft_steps_gpu.py its K' lines.
+ * A Mish actor image (dppo_pack_actor_act) is accepted and refused on the same lines, with the same
+ * messages. Its row tile keeps the pre-activations h1, h2 in registers from the forward to the backward
+ * (mish' cannot be read off the stored activation as relu' is), so it runs the 32-row tile on 8 waves at
+ * every row count and precision: the 64-row tile of large 2-byte minibatches and the fp32 16-wave tile
+ * (4 waves per SIMD, 128 registers) have no room for them and are not instantiated for Mish, and neither
+ * is their K' <= 23 LDS line (a Mish actor takes every K' <= 64 at every row count). dppo_ppo_plan_act
+ * reports the tile. tests/test_actor_mish_gpu.py pins this. */
 
 /* Schedule table, one fp32 row per sampling row r (r = t for DDPM; the DDIM sub-sequence index for
  * DDIM): {c0, c1, c2, c3, logvar, eval_floor, eval_zero, 0} with
@@ -143,6 +150,21 @@ DPPO_API size_t dppo_critic_packed_bytes(const dppo_dims* d, int precision);
 /* params: flat fp32 (layout above) -> packed image (forward + transposed fragments) */
 DPPO_API int dppo_pack_actor(const dppo_dims* d, int precision, const float* params, void* packed, void* stream);
 DPPO_API int dppo_pack_critic(const dppo_dims* d, int precision, const float* params, void* packed, void* stream);
+/* The actor's activation (DiffusionMLP activation_type, model/diffusion/mlp_diffusion.py:21; ResidualMLP
+ * applies it at both sites of the residual block, model/common/mlp.py:95-206: u1 = act(h1), a = act(h2)).
+ * It is an attribute of the packed IMAGE, not of dppo_dims (an addition within ABI 15):
+ * dppo_pack_actor_act packs like dppo_pack_actor and records `activation` for the image at `packed` in a
+ * host table keyed by that address; dppo_pack_actor and dppo_pack_all record DPPO_ACT_RELU, so re-packing
+ * a buffer resets the attribute. The optimizer steps (staged or DPPO_STEP_FUSED_PACK), the fold launch
+ * and dppo_refresh_sampler_tables rewrite an image that was packed before and leave its attribute alone.
+ * Every launcher that takes a packed actor image (dppo_sample, dppo_sample_step, dppo_rollout_enqueue*,
+ * dppo_logprob, dppo_ppo_minibatch{,_part}, dppo_pretrain_minibatch) looks the image up (ReLU when it was
+ * never packed through these entries) and runs that activation's kernels. An activation outside the
+ * enum is refused with DPPO_EINVAL; so is a sampler launch whose base and fine-tuned images carry
+ * different activations, before anything is enqueued. The critic is Mish always (critic.py:40-54). */
+enum { DPPO_ACT_RELU = 0, DPPO_ACT_MISH = 1 };
+DPPO_API int dppo_pack_actor_act(const dppo_dims* d, int precision, int activation, const float* params, void* packed,
+                                 void* stream);
 
 /* ---- a9: diffusion-policy action sampler, VPGDiffusion.call (model/diffusion/diffusion_vpg.py:250-339) ----
  * All K DDPM steps for n_envs rows in ONE launch: DiffusionMLP forward on MFMA + fused DDPM
@@ -170,7 +192,11 @@ DPPO_API int dppo_pack_critic(const dppo_dims* d, int precision, const float* pa
  * k-steps %d not instantiated", "sampler: hidden %d not supported at this precision" (fp32 384) or
  * "sampler needs %zu B of LDS" before anything is enqueued: outputs, dppo_sample_step's device copy
  * of cond and the stream stay as they were. time_dim > 32 has no image (dppo_pack_actor refuses it).
- * tests/test_sampler_surface_gpu.py pins the table, geometry by geometry.                    */
+ * tests/test_sampler_surface_gpu.py pins the table, geometry by geometry.
+ * Mish actor images (dppo_pack_actor_act; both images of a launch carry the same activation, else
+ * DPPO_EINVAL) run on every line above, on the same kernel (dppo_sampler_plan does not depend on the
+ * activation), and are refused where ReLU images are, with the same messages
+ * (tests/test_actor_mish_gpu.py).                                                             */
 DPPO_API int dppo_sample(const dppo_dims* d, int precision, const void* packed_base, const void* packed_ft,
                 const float* sched, const float* cond, int n_envs, const float* x_T, const float* noise,
                 uint64_t seed, uint64_t call_id, int env_offset, int deterministic,
@@ -409,6 +435,9 @@ DPPO_API size_t dppo_ppo_workspace_bytes(const dppo_dims* d, int precision, int 
  * the critic's). */
 enum { DPPO_PLAN_TRAIN = 0, DPPO_PLAN_PRETRAIN = 1, DPPO_PLAN_LOGPROB = 2 };
 DPPO_API int dppo_ppo_plan(const dppo_dims* d, int precision, int rows, int mode, int* out);
+/* the same for an actor image of the given activation (DPPO_ACT_*; dppo_ppo_plan is the ReLU plan): a
+ * Mish actor runs the 32-row tile on 8 waves at every row count (the table above) */
+DPPO_API int dppo_ppo_plan_act(const dppo_dims* d, int precision, int activation, int rows, int mode, int* out);
 DPPO_API int dppo_ppo_adv_stats(const float* advantages, int64_t total, int K_ft, uint64_t perm_seed, int epoch,
                        int64_t start, int rows, const int64_t* row_index, double* adv_stats, void* stream);
 /* The adv_stats of every minibatch of an update phase in one launch: minibatch m = e * n_batch + b

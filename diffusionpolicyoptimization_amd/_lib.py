@@ -157,12 +157,15 @@ def load(path=LIB_PATH):
     return lib
 
 
-def call(name, *args):
-    lib = load()
-    rc = getattr(lib, name)(*args)
+def check(rc, name):
+    """The status of a C entry point: nonzero raises with the library's message (dppo_last_error)."""
     if rc != 0:
-        raise DppoError(f"{name} failed ({rc}): {lib.dppo_last_error().decode()}")
+        raise DppoError(f"{name} failed ({rc}): {load().dppo_last_error().decode()}")
     return rc
+
+
+def call(name, *args):
+    return check(getattr(load(), name)(*args), name)
 
 
 def query(name, *args):

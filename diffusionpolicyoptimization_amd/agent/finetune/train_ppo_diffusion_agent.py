@@ -70,6 +70,107 @@ def episode_stats_from_sums(sums):
                 success_rate=succ / n_ep)
 
 
+def minibatch_geometry(total_local, batch_size, world, dp_scale_batch):
+    """(num_batch, rows_local_full): the minibatches of an epoch (:288) and this rank's rows of a full
+    one, for total_local rows per rank at data-parallel width `world`.
+
+    Data parallel: by default the global minibatch is the reference's batch_size rows,
+    batch_size / world drawn by each rank from its own shard (each rank's keyed permutation of its
+    rows), so the update is the reference's PPO over the union of the shards (world x more minibatches
+    than one rank over its own envs). With train.dp_scale_batch = true every rank runs a full
+    batch_size minibatch of its own and the gradients are averaged: the reference run with
+    batch_size x world."""
+    eff_batch = batch_size * (world if dp_scale_batch else 1)
+    return max(1, total_local * world // eff_batch), eff_batch // world
+
+
+def _pack_metric_sums(ext, ng, met):
+    """Data parallel: a minibatch's metric sums ride behind the gradients in grads_ext (5 loss sums,
+    then learn_eta's d loss / d eta, metric 8), so the gradients' all-reduce sums them as well."""
+    ext[ng:ng + 5].copy_(met[:5])
+    ext[ng + 5:ng + 6].copy_(met[8:9])
+
+
+def _unpack_metric_sums(ext, ng, met):
+    met[:5].copy_(ext[ng:ng + 5])
+    met[8:9].copy_(ext[ng + 5:ng + 6])
+
+
+class _PendingMetrics:
+    """A minibatch's metric sums on their way to the host, and the verdict they carry.
+
+    The target_kl check (:366-370) reads each minibatch's approx_kl on the host. It runs one
+    minibatch behind: minibatch i's gradients are enqueued before the host waits for i-1's
+    metrics (an event right after i-1's kernels, the metrics copied to pinned memory), so the
+    GPU never idles on that read. Only the AdamW step of i waits for the verdict. In the
+    reference the minibatch that exceeds target_kl IS applied and its `break` leaves only the
+    batch loop of that epoch (`if flag_break: break` sits inside the batch loop and is never
+    reached; flag_break is reset per epoch, :284-286,366-370), so the next epoch still runs.
+    Here: a stop by minibatch i-1 of the SAME epoch drops i's gradients (the reference never
+    computes them, so the update's last minibatch is i-1: last_mb = prev_mb) and ends the epoch; a
+    stop by the previous epoch's last minibatch ended an epoch that was over anyway, so i (the new
+    epoch's first) is applied.
+    Each minibatch's metric sums land in mapped host memory, copied by its optimiser-step
+    launch (dppo_optimizer_step) or, before the critic warm-up ends, by a plain copy; one event
+    per slot marks them readable.
+    With the optimiser step applied (after the critic warm-up) the launch stores a tag after the
+    sums and the host polls it (ABI 5): no event record or cross-stream wait on the minibatch
+    chain. In the split update the critic's step copies its own v_loss (metric 1) with the
+    same tag, so the main stream never waits for the side stream inside the epochs."""
+
+    def __init__(self):
+        self._met_map = [ops.MappedDoubles(8) for _ in range(2)]
+        self._cmet_map = [ops.MappedDoubles(8) for _ in range(2)]
+        self._ev_m = [torch.cuda.Event() for _ in range(2)]
+        self._mb_tag = 0      # counts on over the agent's life: a slot never sees the same tag twice
+        self.waiting = False
+        self.out_actor = [mm.address for mm in self._met_map]     # metrics_out of the steps, per slot
+        self.out_critic = [mm.address for mm in self._cmet_map]
+
+    def begin(self, agent, eta_now, critic_tags):
+        """A new update of `agent`. eta_now: c_loss's eta metric (diffusion_ppo.py:131) as of its start;
+        critic_tags: the split update, whose critic step delivers v_loss under the same tag."""
+        self.timing, self.vf_coef, self.target_kl = agent.timing, agent.vf_coef, agent.target_kl
+        self.eta, self.critic_tags, self.clipfracs, self.waiting = eta_now, critic_tags, [], False
+
+    def next_tag(self):
+        self._mb_tag += 1
+        return self._mb_tag
+
+    def copy_in(self, slot, met):
+        """No optimizer step delivers this minibatch's sums (critic warm-up): a plain copy."""
+        torch.from_numpy(self._met_map[slot].array[:5]).copy_(met[:5])
+
+    def push(self, slot, global_rows, epoch, tag, stream):
+        """The minibatch just enqueued: its sums arrive in `slot` under `tag`, or, untagged (0),
+        behind the slot's event recorded here on `stream`."""
+        if not tag:
+            self._ev_m[slot].record(stream)
+        self.slot, self.rows, self.epoch, self.tag, self.waiting = slot, global_rows, epoch, tag, True
+
+    def finish(self):
+        """Wait for the pending minibatch's sums: (its info dict, whether it exceeds target_kl)."""
+        slot, tag = self.slot, self.tag
+        self.waiting = False
+        if tag:
+            self._met_map[slot].wait_tag(5, tag)
+            met = self._met_map[slot].array[:5].copy()
+            if self.critic_tags:
+                self._cmet_map[slot].wait_tag(1, tag)
+                met[1] = self._cmet_map[slot].array[0]
+            met /= self.rows
+        else:
+            self._ev_m[slot].synchronize()
+            met = self._met_map[slot].array[:5] / self.rows
+        self.timing["n_updates"] += 1
+        eta = self.eta
+        inf = dict(pg_loss=float(met[0]), v_loss=float(met[1]), approx_kl=float(met[2]),
+                   clipfrac=float(met[3]), ratio=float(met[4]), bc_loss=0.0, eta=eta,
+                   entropy_loss=-eta, loss=float(met[0] + self.vf_coef * met[1]))
+        self.clipfracs.append(inf["clipfrac"])
+        return inf, self.target_kl is not None and inf["approx_kl"] > self.target_kl
+
+
 class TrainPPODiffusionAgent(TrainPPOAgent):
     def __init__(self, cfg):
         super().__init__(cfg)
@@ -94,6 +195,19 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         self.update_events = None
         self.host_profile = None      # optional dict: host seconds per update-loop phase (tools)
         self._passes_enqueued = False
+        # what rollouts and updates keep from one iteration to the next, created where first needed
+        # (rollout(), _update_resources(), _ipc_setup()); not in _alloc_buffers, which annealing re-runs
+        self._pass_stream = self._launch_evs = None          # the old-log-prob passes during a rollout
+        self._ep_local, self._ep_dev_valid = None, False     # this rollout's episode sums
+        self._ipc_groups = None                              # train.allreduce = ipc: one group per bucket
+        self._ev_map = None          # explained-variance moments, mapped host memory
+        self._metrics = None         # _PendingMetrics: mapped metric slots, their events, the tag counter
+        self._adv_all = None         # every minibatch's advantage moments, fp64 [n_mb, 3]
+        self._side = None            # the split update's side stream (tools/cu_mask_probe.py swaps it)
+        self._met_dev = self._ev_rows = self._ev_met = None   # ... its two metric buffers and events
+        self._clip_buf = None        # device clip: (norms, scales, actor workspace, critic workspace)
+        self._torch_norms = None     # torch clip: the last call's per-variable norms
+        self._bound_key = self._bound = None                 # the marshalled calls, see _bind_update()
         # test hook: called as minibatch_hook(epoch, batch, start, rows) after a minibatch's
         # gradients (all-reduced under data parallelism) are in self.model.grads
         self.minibatch_hook = None
@@ -191,7 +305,7 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         ops.critic_forward(m.dims, m.precision, m.packed_critic, self.obs_traj.view(N, -1), values=self.values)
         if from_step < S:
             self._logprob_range(from_step, S)
-        if getattr(self, "_pass_stream", None) is not None:
+        if self._pass_stream is not None:
             torch.cuda.current_stream(self.device).wait_stream(self._pass_stream)
         self._passes_enqueued = True
 
@@ -203,7 +317,7 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         the default) or, with train.allreduce = ipc (env DPPO_ALLREDUCE), dppo_ipc_allreduce over
         IPC-mapped peer regions (util/ipc.py; one group per bucket, since the two buckets run on two
         streams), on the current stream."""
-        groups = getattr(self, "_ipc_groups", None)
+        groups = self._ipc_groups
         if groups is None:
             return self._allreduce(t)
         return groups[name](t)
@@ -211,7 +325,7 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
     def _ipc_setup(self, split):
         """Collective (every rank, same point of the update): the IPC groups of the gradient buckets."""
         mode = os.environ.get("DPPO_ALLREDUCE") or str(self.cfg.train.get("allreduce", "rccl"))
-        if mode != "ipc" or self.world_size == 1 or getattr(self, "_ipc_groups", None) is not None:
+        if mode != "ipc" or self.world_size == 1 or self._ipc_groups is not None:
             return
         from ...util.ipc import IpcAllReduce
         m = self.model
@@ -227,7 +341,7 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
     def close_collectives(self):
         """Collective (every rank): unmap and free the IPC groups (run() calls it after the last
         iteration)."""
-        for g in (getattr(self, "_ipc_groups", None) or {}).values():
+        for g in (self._ipc_groups or {}).values():
             g.close()
         self._ipc_groups = None
 
@@ -275,12 +389,12 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
             # chunks (G x E x K' rows) goes to a pass stream behind the events of the two latest
             # launches, onto the idle CUs (DPPO_PASS_CHUNK = G; 0 = after the rollout).
             G = int(os.environ.get("DPPO_PASS_CHUNK", "10")) if early else 0
-            if G > 0 and getattr(self, "_pass_stream", None) is None:
+            if G > 0 and self._pass_stream is None:
                 self._pass_stream = torch.cuda.Stream(device=self.device)
             done_lp = 0
             # completion events of the launches, a ring re-recorded per step (only the two latest
             # launches <= last are ever waited on); created once per agent
-            if G > 0 and getattr(self, "_launch_evs", None) is None:
+            if G > 0 and self._launch_evs is None:
                 self._launch_evs = [torch.cuda.Event() for _ in range(4)]
             evs = self._launch_evs if G > 0 else None
 
@@ -362,8 +476,8 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
     def _episode_sums_local(self):
         """This rank's episode sums: the update's dppo_episode_sums rows summed in env order (the
         reference's visit order), or the host restatement when no update ran on this rollout."""
-        if getattr(self, "_ep_local", None) is None:
-            if getattr(self, "_ep_dev_valid", False):
+        if self._ep_local is None:
+            if self._ep_dev_valid:
                 rows = self.episode_dev.cpu().numpy()
                 acc = [0.0, 0.0, 0.0, 0.0]
                 for r in rows.tolist():
@@ -385,12 +499,36 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         return episode_stats_from_sums(sums)
 
     # ------------------------------------------------------------------ update (agent :186-377)
-    def update(self):
+    def _update_resources(self, split, clip_dev, n_mb):
+        """What an update keeps across iterations (declared in __init__), allocated when missing."""
+        dev = self.device
+        if self._ev_map is None:
+            self._ev_map = ops.MappedDoubles(5)
+            self._metrics = _PendingMetrics()
+        if self._adv_all is None or self._adv_all.shape[0] != n_mb:
+            self._adv_all = torch.zeros(n_mb, 3, dtype=torch.float64, device=dev)
+        if split and self._side is None:
+            self._side = torch.cuda.Stream(device=dev)
+        if split and self._met_dev is None:
+            self._met_dev = [torch.zeros(16, dtype=torch.float64, device=dev) for _ in range(2)]
+            self._ev_rows = torch.cuda.Event()
+            self._ev_met = torch.cuda.Event()
+        # the clip's norm table (12 actor + 8 critic variables), scale table and partial-sum workspaces:
+        # allocated once, captured by the bound norm launches and optimizer steps
+        if clip_dev and self._clip_buf is None:
+            ws = [torch.empty(ops.grad_clip_workspace_bytes(self.model.dims, net) // 8, dtype=torch.float64, device=dev)
+                  for net in ("actor", "critic")]
+            self._clip_buf = (torch.zeros(20, dtype=torch.float32, device=dev),
+                              torch.ones(20, dtype=torch.float32, device=dev), *ws)
+
+    def _prepare_update(self):
+        """The rollout's hand-off to the epochs: rewards and flags to the device, episode sums, reward
+        scaling, bootstrap values, GAE and the value moments. Returns the flat views the minibatches
+        gather from: (obs [N,SD], chains [N,K'+1,XD], advantages [N], returns [N])."""
         S, E, m = self.n_steps, self.n_envs, self.model
-        kf = m.ft_denoising_steps
         N = S * E
         obs_flat = self.obs_traj.view(N, -1)
-        chains_flat = self.chains_traj.view(N, kf + 1, -1)
+        chains_flat = self.chains_traj.view(N, m.ft_denoising_steps + 1, -1)
         if not self._passes_enqueued:
             self._enqueue_passes()
         self._passes_enqueued = False
@@ -418,341 +556,305 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         adv_flat, ret_flat = self.adv.view(-1), self.ret.view(-1)
         # explained-variance moments of the pre-update values and returns (:373-377), read after the
         # epochs from host-mapped memory (no torch reductions or host syncs at the end of the update)
-        if getattr(self, "_ev_map", None) is None:
-            self._ev_map = ops.MappedDoubles(5)
         ops.value_moments(self.values, ret_flat, self._ev_map.address)
+        return obs_flat, chains_flat, adv_flat, ret_flat
 
-        total_local = N * kf
+    def _bind_update(self, obs_flat, chains_flat, adv_flat, ret_flat, rows_local_full, split, fuse, clip_c):
+        """self._bound: the per-update arguments of the minibatch, norm and optimizer calls, validated
+        and marshalled once (host enqueue time per minibatch: an 8-GPU rank runs 255 small ones per
+        iteration). The bound calls are reused across updates while every buffer they captured is the
+        same (~0.2 ms of host marshalling per update, with the device idle behind it).
+        Both halves' optimizer steps are ONE launch each (ABI 11, DPPO_STEP_FUSED_PACK): AdamW, the
+        weight image (the actor's: actor_tile_step_kernel, then its row tiles' fold launch) and the
+        zeroing of what the next minibatch's half would zero first (DPPO_STEP_CLEAR_GRADS +
+        ops.ClearRanges; the next half runs DPPO_PPO_PRECLEARED). The actor's time-MLP backward and
+        W_out / l2 gradients stay one launch in the minibatch (time_l2_bwd). Measured slower and
+        removed: the actor's whole tail in one launch (r06, profiles/r06de_actor_tail_ab.txt; r05g
+        workgroup-0 form, profiles/r05g_step_ab.txt), the l2 gradient left factored for the step
+        (profiles/r05r_l2_defer_ab.txt), the critic's half held behind the actor's step, and the
+        AdamW + pack launch pair. Not with a test hook reading the gradients (zero after the step):
+        `fuse` is off then.
+        The actor's image skips the split sampler's tables (fold, TIN, W_XS, B_OUT2), which no PPO
+        kernel reads: the next rollout's first sampler launch re-derives them once
+        (DPPO_STEP_DEFER_SAMPLER_TABLES)."""
+        m, opt = self.model, self.actor_optimizer
+        na, ng = m.n_actor, m.grads.numel()
+        clip_dev = split and clip_c is not None
+        ptrs = lambda *ts: tuple((t.data_ptr(), tuple(t.shape)) for t in ts)
+        # self.values: bind_minibatch captures it for the clipped value loss
+        bkey = (ptrs(obs_flat, chains_flat, self.lp_old, adv_flat, ret_flat, self.values, m.grads, m.train_params,
+                     m.packed_ft, m.packed_critic, m.sched, m.workspace(rows_local_full), opt.m, opt.v),
+                self.perm_seed, rows_local_full, self.reward_horizon, split,
+                self.max_grad_norm is None, m.dims.ft_denoising_steps, m.precision, fuse,
+                (ptrs(*self._clip_buf), clip_c) if clip_dev else None)
+        if self._bound_key == bkey:
+            return self._bound
+        bound = {"run_mb": m.bind_minibatch(obs_flat, chains_flat, self.lp_old, adv_flat, ret_flat,
+                                            self.perm_seed, rows_local_full, reward_horizon=self.reward_horizon,
+                                            old_values=self.values)}   # the clipped v_loss's (:110-116)
+        actor_pack = {"actor": (m.actor_ft_params, m.packed_ft)}
+        critic_pack = {"critic": (m.critic_params, m.packed_critic)}
+        if split:
+            sc_a = sc_c = None
+            if clip_dev:
+                norms, scales, ws_a, ws_c = self._clip_buf
+                sc_a, sc_c = scales[:12], scales[12:]
+                bound["clip_actor"] = ops.BoundGradClip(m.dims, "actor", m.grads[:na], clip_c, norms[:12], sc_a, ws_a)
+                bound["clip_critic"] = ops.BoundGradClip(m.dims, "critic", m.grads[na:ng], clip_c, norms[12:], sc_c, ws_c)
+            bound["actor"] = opt.bind_range(m.grads, 0, na, m.dims, m.precision, packs=actor_pack,
+                                            defer_sampler_tables=True, fused_pack=fuse, clear_grads=fuse,
+                                            clip_scales=sc_a)
+            bound["critic"] = opt.bind_range(m.grads, na, ng, m.dims, m.precision, packs=critic_pack,
+                                             fused_pack=fuse, clear_grads=fuse, clip_scales=sc_c)
+            if fuse:   # what each half of a full minibatch zeroes, per metrics buffer
+                ws_full = m.workspace(rows_local_full)
+                bound["clear"] = [(ops.ClearRanges(m.dims, m.precision, rows_local_full, ws_full, t, 1),
+                                   ops.ClearRanges(m.dims, m.precision, rows_local_full, ws_full, t, 2))
+                                  for t in self._met_dev]
+        elif self.max_grad_norm is None:
+            bound["all"] = opt.bind_range(m.grads, 0, ng, m.dims, m.precision, packs={**actor_pack, **critic_pack},
+                                          defer_sampler_tables=True)
+        self._bound_key, self._bound = bkey, bound
+        return bound
+
+    # One minibatch's gradients: enqueue(mb, global_rows, stats, pre, slot) with mb = (epoch key,
+    # start, rows), stats the device address of its advantage moments (fp64[3]), pre whether the
+    # previous optimizer step already zeroed its accumulators, slot the metrics buffer it sums into.
+    # Raw device addresses and stream handles are computed once per update: per minibatch the host
+    # passes ints instead of slicing tensors and entering stream contexts (~tens of us per minibatch,
+    # which an 8-GPU rank's 255 small minibatches per iteration wait on).
+    def _enqueue_split(self, run_mb, stream, side, tagged):
+        """Split update: the critic's half of each minibatch (row tiles, dW, its AdamW range,
+        repack) runs on a side stream and the actor's on the main stream, so the critic of
+        minibatch i+1 fills the CUs the actor leaves idle in its dW / small-kernel tail of i.
+        Metrics alternate between two device buffers. Inside the critic warm-up (not tagged) the
+        main stream joins the critic's half before the plain copy of the minibatch's metrics."""
+        st_main, st_side = stream.cuda_stream, side.cuda_stream
+        met_ptrs = [t.data_ptr() for t in self._met_dev]
+
+        def enqueue(mb, global_rows, stats, pre, slot):
+            met_p = met_ptrs[slot]
+            run_mb(*mb, global_rows=global_rows, adv_stats=stats, part=2, metrics=met_p, stream=st_side, precleared=pre)
+            if not tagged:
+                ev_c = torch.cuda.Event()
+                ev_c.record(side)
+            run_mb(*mb, global_rows=global_rows, adv_stats=stats, part=1, metrics=met_p, stream=st_main, precleared=pre)
+            if not tagged:
+                stream.wait_event(ev_c)
+        return enqueue
+
+    def _enqueue_split_dp(self, run_mb, stream, side):
+        """Split update under data parallelism: the gradients go out in two buckets, each as soon as
+        it is final: the critic's gradients + the minibatch's metric sums on the side stream once the
+        actor's row tiles have produced their loss metrics (overlapping the actor's dW), then the
+        actor's gradients on the main stream (overlapping the critic's optimiser step and repack).
+        The main stream joins the critic's bucket before the step reads the metrics."""
+        m = self.model
+        na, ng, ext = m.n_actor, m.grads.numel(), m.grads_ext
+        st_side = side.cuda_stream
+        mets, met_ptrs = self._met_dev, [t.data_ptr() for t in self._met_dev]
+        ev_rows, ev_met, allreduce = self._ev_rows, self._ev_met, self._bucket_allreduce
+
+        def enqueue(mb, global_rows, stats, pre, slot):
+            met = mets[slot]
+            run_mb(*mb, global_rows=global_rows, adv_stats=stats, part=2, metrics=met_ptrs[slot], stream=st_side,
+                   precleared=pre)
+            run_mb(*mb, global_rows=global_rows, adv_stats=stats, part=4, metrics=met, precleared=pre)  # actor row tiles
+            ev_rows.record(stream)
+            with torch.cuda.stream(side):          # bucket 1: critic gradients + metrics
+                side.wait_event(ev_rows)
+                _pack_metric_sums(ext, ng, met)
+                allreduce("critic", ext[na:])
+                _unpack_metric_sums(ext, ng, met)
+                ev_met.record(side)
+            run_mb(*mb, global_rows=global_rows, adv_stats=stats, part=5, metrics=met)   # actor dW + time MLP
+            allreduce("actor", ext[:na])           # bucket 2: actor gradients
+            stream.wait_event(ev_met)
+        return enqueue
+
+    def _enqueue_unsplit(self, run_mb, dp):
+        """DPPO_SPLIT_UPDATE=0: one launch sequence on the main stream into model.metrics and, under
+        data parallelism, one collective: gradients + metric sums."""
+        m = self.model
+        ng, ext, met, allreduce = m.grads.numel(), m.grads_ext, m.metrics, self._bucket_allreduce
+
+        def enqueue(mb, global_rows, stats, pre, slot):
+            run_mb(*mb, global_rows=global_rows, adv_stats=stats)
+            if dp:
+                _pack_metric_sums(ext, ng, met)
+                allreduce("all", ext)
+                _unpack_metric_sums(ext, ng, met)
+        return enqueue
+
+    # The optimiser step (agent :346) of one minibatch: step(lr, slot, tag) applies AdamW, sends the
+    # metric sums of buffer `slot` to the host under `tag` and re-derives the weight images.
+    def _step_split(self, bound, stream, side):
+        """One dppo_optimizer_step per half, each on its stream; with the device clip, one norm launch
+        per half (dppo_grad_clip_scales) right before its step, which applies the scales as it reads
+        the gradients (under data parallelism after that half's bucket all-reduce: the reference clips
+        the whole batch's gradient). The critic's step sends its own v_loss (metric 1)."""
+        step_actor, step_critic = bound["actor"], bound["critic"]
+        clip_actor, clip_critic = bound.get("clip_actor"), bound.get("clip_critic")
+        clear_next = bound.get("clear") or [(None, None)] * 2   # fused: what the NEXT minibatch's halves zero first
+        st_main, st_side = stream.cuda_stream, side.cuda_stream
+        met_ptrs = [t.data_ptr() for t in self._met_dev]
+        out_a, out_c = self._metrics.out_actor, self._metrics.out_critic
+
+        def step(lr, slot, tag):
+            ca, cc = clear_next[1 - slot]
+            met_p = met_ptrs[slot]
+            step_actor(lr, metrics=met_p, metrics_out=out_a[slot], n_metrics=5, metrics_tag=tag, stream=st_main, clear=ca)
+            step_critic(lr, metrics=met_p + 8, metrics_out=out_c[slot], n_metrics=1, metrics_tag=tag, stream=st_side,
+                        clear=cc)
+        if clip_actor is None:
+            return step
+
+        def clipped_step(lr, slot, tag):   # the norms of what each stream's step is about to read
+            clip_actor(stream=st_main)
+            clip_critic(stream=st_side)
+            step(lr, slot, tag)
+        return clipped_step
+
+    def _step_unsplit(self, bound, clip_c):
+        """One dppo_optimizer_step call over [actor | critic] on the main stream: the bound one, or,
+        with train.max_grad_norm, the per-variable torch clip and an unbound step, the independent
+        statement the device clip is tested against."""
+        m, opt, out = self.model, self.actor_optimizer, self._metrics.out_actor
+        met, ng = m.metrics, m.grads.numel()
+        if clip_c is None:
+            step_all = bound["all"]
+            return lambda lr, slot, tag: step_all(lr, metrics=met, metrics_out=out[slot], n_metrics=5, metrics_tag=tag)
+        packs = {"actor": (m.actor_ft_params, m.packed_ft), "critic": (m.critic_params, m.packed_critic)}
+
+        def clipped_step(lr, slot, tag):
+            self._clip_by_norm_per_tensor(clip_c)
+            opt.apply_range(m.grads, 0, ng, lr, m.dims, m.precision, packs=packs, metrics=met, metrics_out=out[slot],
+                            n_metrics=5, metrics_tag=tag, defer_sampler_tables=True)
+        return clipped_step
+
+    def update(self):
+        m, opt = self.model, self.actor_optimizer
+        kf = m.ft_denoising_steps
+        total_local = self.n_steps * self.n_envs * kf
         # W: the data-parallel width the minibatch arithmetic follows. train.emulate_world = W' > 1
         # on ONE process is a measurement mode (bench.py --emulate-ranks): this rank runs exactly one
         # rank's share of the W'-rank update (W' x the minibatches, batch_size / W' rows each, the
         # gradient scaled by 1 / batch_size) with every collective skipped
-        W = self.world_size if self.world_size > 1 else self.emulate_world
-        total_global = total_local * W
-        # Data parallel: by default the global minibatch is the reference's
-        # batch_size rows, batch_size / world drawn by each rank from its own shard (each rank's
-        # keyed permutation of its rows), so the update is the reference's PPO over the union of
-        # the shards (world x more minibatches than one rank over its own envs). With
-        # train.dp_scale_batch = true every rank runs a full batch_size minibatch of its own and
-        # the gradients are averaged: the reference run with batch_size x world.
-        eff_batch = self.batch_size * (W if self.dp_scale_batch else 1)
-        num_batch = max(1, total_global // eff_batch)                                     # :288
-        rows_local_full = eff_batch // W
-        clipfracs, info = [], {}
-        caller = torch.cuda.current_stream(self.device)
+        dp = self.world_size > 1
+        W = self.world_size if dp else self.emulate_world
+        num_batch, rows_local_full = minibatch_geometry(total_local, self.batch_size, W, self.dp_scale_batch)
+        split = os.environ.get("DPPO_SPLIT_UPDATE", "1") != "0"
+        # train.max_grad_norm (agent :349-354: tf.clip_by_norm(grad, 1.0) per variable) keeps the split
+        # update (the device clip, _step_split); the unsplit path keeps the torch clip (_step_unsplit)
+        clip_c = None
+        if self.max_grad_norm is not None:
+            clip_c = 1.0 if self.grad_clip_norm is None else float(self.grad_clip_norm)
+        clip_dev = split and clip_c is not None
+        fuse = split and self.minibatch_hook is None      # one-launch steps that pre-clear: _bind_update
+        tagged = self.itr >= self.n_critic_warmup_itr      # the optimizer steps are applied (:348)
+        self._update_resources(split, clip_dev, self.update_epochs * num_batch)
+        obs_flat, chains_flat, adv_flat, ret_flat = self._prepare_update()
+        pend = self._metrics
+        pend.begin(self, m.current_eta(), split)
+        if dp:
+            self._ipc_setup(split)
+        # every minibatch's advantage moments (norm_adv, diffusion_ppo.py:74-75) in one launch, and
+        # on several GPUs one all-reduce of the whole table instead of one per minibatch
+        ops.ppo_adv_stats_all(adv_flat, total_local, kf, self.perm_seed, 1000 * self.itr, self.update_epochs,
+                              rows_local_full, num_batch, self._adv_all)
+        if dp:
+            self._allreduce(self._adv_all)
         # the epochs run on the caller's stream (a high-priority stream for the actor's half, r03, was
         # measured slower: update 15.0 vs 14.8 ms per iteration, tools/ab_env.sh)
-        with torch.cuda.stream(caller):
-            stream = torch.cuda.current_stream(self.device)
-            # The target_kl check (:366-370) reads each minibatch's approx_kl on the host. It runs one
-            # minibatch behind: minibatch i's gradients are enqueued before the host waits for i-1's
-            # metrics (an event right after i-1's kernels, the metrics copied to pinned memory), so the
-            # GPU never idles on that read. Only the AdamW step of i waits for the verdict. In the
-            # reference the minibatch that exceeds target_kl IS applied and its `break` leaves only the
-            # batch loop of that epoch (`if flag_break: break` sits inside the batch loop and is never
-            # reached; flag_break is reset per epoch, :284-286,366-370), so the next epoch still runs.
-            # Here: a stop by minibatch i-1 of the SAME epoch drops i's gradients (the reference never
-            # computes them) and ends the epoch; a stop by the previous epoch's last minibatch ended an
-            # epoch that was over anyway, so i (the new epoch's first) is applied.
-            # Each minibatch's metric sums land in mapped host memory, copied by its optimiser-step
-            # launch (dppo_optimizer_step) or, before the critic warm-up ends, by a plain copy; one event
-            # per slot marks them readable.
-            # With the optimiser step applied (after the critic warm-up) the launch stores a tag after the
-            # sums and the host polls it (ABI 5): no event record or cross-stream wait on the minibatch
-            # chain. In the split update the critic's step copies its own v_loss (metric 1) with the
-            # same tag, so the main stream never waits for the side stream inside the epochs.
-            if not hasattr(self, "_met_map"):
-                self._met_map = [ops.MappedDoubles(8) for _ in range(2)]
-                self._cmet_map = [ops.MappedDoubles(8) for _ in range(2)]
-                self._ev_m = [torch.cuda.Event() for _ in range(2)]
-                self._mb_tag = 0
-            pending = None
-            last_mb = None   # (epoch key, start, rows) of the last minibatch run (the bc_loss report)
-            eta_now = m.current_eta()   # c_loss's eta metric (diffusion_ppo.py:131), as of the update's start
-
-            def finish(p):
-                slot, ev, grows, _, tag, ctag = p
-                if tag:
-                    self._met_map[slot].wait_tag(5, tag)
-                    met = self._met_map[slot].array[:5].copy()
-                    if ctag:
-                        self._cmet_map[slot].wait_tag(1, ctag)
-                        met[1] = self._cmet_map[slot].array[0]
-                    met /= grows
-                else:
-                    ev.synchronize()
-                    met = self._met_map[slot].array[:5] / grows
-                self.timing["n_updates"] += 1
-                inf = dict(pg_loss=float(met[0]), v_loss=float(met[1]), approx_kl=float(met[2]),
-                           clipfrac=float(met[3]), ratio=float(met[4]), bc_loss=0.0, eta=eta_now,
-                           entropy_loss=-eta_now, loss=float(met[0] + self.vf_coef * met[1]))
-                clipfracs.append(inf["clipfrac"])
-                return inf, self.target_kl is not None and inf["approx_kl"] > self.target_kl
-
-            dp = self.world_size > 1
-            split = os.environ.get("DPPO_SPLIT_UPDATE", "1") != "0"
-            # train.max_grad_norm (agent :349-354: tf.clip_by_norm(grad, 1.0) per variable) keeps the split
-            # update: each half enqueues ONE norm launch (dppo_grad_clip_scales) right before its
-            # optimizer step (under data parallelism after that half's bucket all-reduce: the reference
-            # clips the whole batch's gradient), and the step applies the scales as it reads the gradients.
-            # The unsplit path (DPPO_SPLIT_UPDATE=0) keeps the per-variable torch clip as the independent
-            # statement the device path is tested against.
-            clip_c = None
-            if self.max_grad_norm is not None:
-                clip_c = 1.0 if self.grad_clip_norm is None else float(self.grad_clip_norm)
-            clip_ran = False
-            if dp:
-                self._ipc_setup(split)
-            # every minibatch's advantage moments (norm_adv, diffusion_ppo.py:74-75) in one launch, and
-            # on several GPUs one all-reduce of the whole table instead of one per minibatch
-            n_mb = self.update_epochs * num_batch
-            if getattr(self, "_adv_all", None) is None or self._adv_all.shape[0] != n_mb:
-                self._adv_all = torch.zeros(n_mb, 3, dtype=torch.float64, device=self.device)
-            ops.ppo_adv_stats_all(adv_flat, total_local, kf, self.perm_seed, 1000 * self.itr, self.update_epochs,
-                                  rows_local_full, num_batch, self._adv_all)
-            if dp:
-                self._allreduce(self._adv_all)
-            # Split update: the critic's half of each minibatch (row tiles, dW, its AdamW range,
-            # repack) runs on a side stream and the actor's on the main stream, so the critic of
-            # minibatch i+1 fills the CUs the actor leaves idle in its dW / small-kernel tail of i.
-            # Metrics alternate between two device buffers; the main stream joins the critic's half
-            # before copying a minibatch's metrics.
-            # Under data parallelism the gradients go out in two buckets, each as soon as it is final:
-            # the critic's gradients + the minibatch's metric sums on the side stream once the actor's
-            # row tiles have produced their loss metrics (overlapping the actor's dW), then the actor's
-            # gradients on the main stream (overlapping the critic's optimiser step and repack).
-            if split:
-                if getattr(self, "_side", None) is None:
-                    self._side = torch.cuda.Stream(device=self.device)
-                    self._met_dev = [torch.zeros(16, dtype=torch.float64, device=self.device) for _ in range(2)]
-                    self._ev_rows = torch.cuda.Event()
-                    self._ev_met = torch.cuda.Event()
-                side = self._side
-                side.wait_stream(stream)
-                na = m.n_actor
-            # the per-update arguments of the minibatch and optimizer calls, validated and marshalled
-            # once (host enqueue time per minibatch: an 8-GPU rank runs 255 small ones per iteration)
-            # Both halves' optimizer steps are ONE launch each (ABI 11, DPPO_STEP_FUSED_PACK): AdamW, the
-            # weight image (the actor's: actor_tile_step_kernel, then its row tiles' fold launch) and the
-            # zeroing of what the next minibatch's half would zero first (DPPO_STEP_CLEAR_GRADS +
-            # ops.ClearRanges; the next half runs DPPO_PPO_PRECLEARED). The actor's time-MLP backward and
-            # W_out / l2 gradients stay one launch in the minibatch (time_l2_bwd). Measured slower and
-            # removed: the actor's whole tail in one launch (r06, profiles/r06de_actor_tail_ab.txt; r05g
-            # workgroup-0 form, profiles/r05g_step_ab.txt), the l2 gradient left factored for the step
-            # (profiles/r05r_l2_defer_ab.txt), the critic's half held behind the actor's step, and the
-            # AdamW + pack launch pair. Not with a test hook reading the gradients (zero after the step).
-            fuse = split and self.minibatch_hook is None
-            # the actor's image skips the split sampler's tables (fold, TIN, W_XS, B_OUT2), which no PPO
-            # kernel reads: the next rollout's first sampler launch re-derives them once
-            defer = True
-            opt = self.actor_optimizer
-            ng_all = m.grads.numel()
-            # the bound calls are reused across updates while every buffer they captured is the same
-            # (~0.2 ms of host marshalling per update, with the device idle behind it)
-            ptrs = lambda *ts: tuple((t.data_ptr(), tuple(t.shape)) for t in ts)
-            # the clip's norm table (12 actor + 8 critic variables), scale table and partial-sum workspaces:
-            # allocated once, captured by the bound norm launches and optimizer steps
-            clip_dev = split and clip_c is not None
-            if clip_dev and getattr(self, "_clip_buf", None) is None:
-                f32 = dict(dtype=torch.float32, device=self.device)
-                self._clip_buf = (torch.zeros(20, **f32), torch.ones(20, **f32),
-                                  torch.empty(ops.grad_clip_workspace_bytes(m.dims, "actor") // 8, dtype=torch.float64,
-                                              device=self.device),
-                                  torch.empty(ops.grad_clip_workspace_bytes(m.dims, "critic") // 8, dtype=torch.float64,
-                                              device=self.device))
-            bkey = (ptrs(obs_flat, chains_flat, self.lp_old, adv_flat, ret_flat, m.grads, m.train_params,
-                         m.packed_ft, m.packed_critic, m.sched, m.workspace(rows_local_full), opt.m, opt.v),
-                    self.perm_seed, rows_local_full, self.reward_horizon, split,
-                    self.max_grad_norm is None, m.dims.ft_denoising_steps, m.precision, fuse,
-                    (ptrs(*self._clip_buf), clip_c) if clip_dev else None)
-            if getattr(self, "_bound_key", None) != bkey:
-                bound = {"run_mb": m.bind_minibatch(obs_flat, chains_flat, self.lp_old, adv_flat, ret_flat,
-                                                    self.perm_seed, rows_local_full, reward_horizon=self.reward_horizon,
-                                                    old_values=self.values)}   # the clipped v_loss's (:110-116)
-                if split:
-                    sc_a = sc_c = None
-                    if clip_dev:
-                        norms, scales, ws_a, ws_c = self._clip_buf
-                        sc_a, sc_c = scales[:12], scales[12:]
-                        bound["clip_actor"] = ops.BoundGradClip(m.dims, "actor", m.grads[:na], clip_c, norms[:12], sc_a, ws_a)
-                        bound["clip_critic"] = ops.BoundGradClip(m.dims, "critic", m.grads[na:ng_all], clip_c, norms[12:],
-                                                                 sc_c, ws_c)
-                    bound["actor"] = opt.bind_range(m.grads, 0, na, m.dims, m.precision,
-                                                    packs={"actor": (m.actor_ft_params, m.packed_ft)},
-                                                    defer_sampler_tables=defer, fused_pack=fuse, clear_grads=fuse,
-                                                    clip_scales=sc_a)
-                    bound["critic"] = opt.bind_range(m.grads, na, ng_all, m.dims, m.precision,
-                                                     packs={"critic": (m.critic_params, m.packed_critic)},
-                                                     fused_pack=fuse, clear_grads=fuse, clip_scales=sc_c)
-                    if fuse:   # what each half of a full minibatch zeroes, per metrics buffer
-                        ws_full = m.workspace(rows_local_full)
-                        bound["clear"] = [(ops.ClearRanges(m.dims, m.precision, rows_local_full, ws_full, t, 1),
-                                           ops.ClearRanges(m.dims, m.precision, rows_local_full, ws_full, t, 2))
-                                          for t in self._met_dev] if fuse else None
-                elif self.max_grad_norm is None:
-                    bound["all"] = opt.bind_range(m.grads, 0, ng_all, m.dims, m.precision,
-                                                  packs={"actor": (m.actor_ft_params, m.packed_ft),
-                                                         "critic": (m.critic_params, m.packed_critic)},
-                                                  defer_sampler_tables=defer)
-                self._bound_key, self._bound = bkey, bound
-            run_mb = self._bound["run_mb"]
-            step_actor, step_critic = self._bound.get("actor"), self._bound.get("critic")
-            step_all = self._bound.get("all")
-            clear_next = self._bound.get("clear")
-            clip_actor, clip_critic = self._bound.get("clip_actor"), self._bound.get("clip_critic")
-            cleared = False   # the previous optimizer step zeroed this minibatch's accumulators
-            # raw device addresses and stream handles, computed once: per minibatch the host passes
-            # ints instead of slicing tensors and entering stream contexts (~tens of us per minibatch,
-            # which an 8-GPU rank's 255 small minibatches per iteration wait on)
-            adv_base = self._adv_all.data_ptr()
-            st_main = stream.cuda_stream
-            st_side = side.cuda_stream if split else None
-            met_ptrs = [t.data_ptr() for t in self._met_dev] if split else None
-            k = 0
-            for update_epoch in range(self.update_epochs):
-                for batch in range(num_batch):
-                    start = batch * rows_local_full
-                    rows = min(rows_local_full, total_local - start)
-                    if rows <= 0:
-                        break
-                    global_rows = rows * W
-                    stats = adv_base + 24 * (update_epoch * num_batch + batch)   # fp64[3] row
-                    hp_ = self.host_profile
-                    if hp_ is not None:
-                        t_h0 = time.perf_counter()
-                    if self.update_events is not None:
-                        ev0 = torch.cuda.Event(enable_timing=True)
-                        ev0.record(stream)
-                    mb_args = (update_epoch + 1000 * self.itr, start, rows)
-                    prev_mb, last_mb = last_mb, mb_args
-                    pre = cleared and rows == rows_local_full
-                    mb_kw = dict(global_rows=global_rows, adv_stats=stats)
-                    met = m.metrics
-                    tagged = self.itr >= self.n_critic_warmup_itr
+        stream = torch.cuda.current_stream(self.device)
+        side = self._side if split else None
+        if split:
+            side.wait_stream(stream)
+        bound = self._bind_update(obs_flat, chains_flat, adv_flat, ret_flat, rows_local_full, split, fuse, clip_c)
+        run_mb = bound["run_mb"]
+        if split:
+            enqueue = (self._enqueue_split_dp(run_mb, stream, side) if dp else
+                       self._enqueue_split(run_mb, stream, side, tagged))
+            step, mets = self._step_split(bound, stream, side), self._met_dev
+        else:
+            enqueue = self._enqueue_unsplit(run_mb, dp)
+            step, mets = self._step_unsplit(bound, clip_c), (m.metrics, m.metrics)
+        hp_, events, hook, learn_eta = self.host_profile, self.update_events, self.minibatch_hook, self.learn_eta
+        adv_base, epoch0, steps0 = self._adv_all.data_ptr(), 1000 * self.itr, opt.iterations
+        info = {}
+        last_mb = None    # (epoch key, start, rows) of the last minibatch run (the bc_loss report)
+        cleared = False   # the previous optimizer step zeroed this minibatch's accumulators
+        k = 0
+        for update_epoch in range(self.update_epochs):
+            for batch in range(num_batch):
+                start = batch * rows_local_full
+                rows = min(rows_local_full, total_local - start)
+                if rows <= 0:
+                    break
+                global_rows = rows * W
+                if hp_ is not None:
+                    t_h0 = time.perf_counter()
+                if events is not None:
+                    ev0 = torch.cuda.Event(enable_timing=True)
+                    ev0.record(stream)
+                mb = (update_epoch + epoch0, start, rows)
+                prev_mb, last_mb = last_mb, mb
+                slot = k % 2
+                enqueue(mb, global_rows, adv_base + 24 * (update_epoch * num_batch + batch),   # its fp64[3] row
+                        cleared and rows == rows_local_full, slot)
+                if hook is not None:
                     if split:
-                        met = self._met_dev[k % 2]
-                        met_p = met_ptrs[k % 2]
-                        run_mb(*mb_args, **mb_kw, part=2, metrics=met_p, stream=st_side, precleared=pre)
-                        if not tagged and not dp:
-                            ev_c = torch.cuda.Event()
-                            ev_c.record(side)
-                        if dp:
-                            ng = m.grads.numel()
-                            run_mb(*mb_args, **mb_kw, part=4, metrics=met,   # actor row tiles
-                                   precleared=pre)
-                            self._ev_rows.record(stream)
-                            with torch.cuda.stream(side):          # bucket 1: critic gradients + metrics
-                                side.wait_event(self._ev_rows)
-                                m.grads_ext[ng:ng + 5].copy_(met[:5])
-                                m.grads_ext[ng + 5:ng + 6].copy_(met[8:9])   # learn_eta: d loss / d eta
-                                self._bucket_allreduce("critic", m.grads_ext[na:])
-                                met[:5].copy_(m.grads_ext[ng:ng + 5])
-                                met[8:9].copy_(m.grads_ext[ng + 5:ng + 6])
-                                self._ev_met.record(side)
-                            run_mb(*mb_args, **mb_kw, part=5, metrics=met)   # actor dW + time MLP
-                            self._bucket_allreduce("actor", m.grads_ext[:na])      # bucket 2: actor gradients
-                            stream.wait_event(self._ev_met)
-                        else:
-                            run_mb(*mb_args, **mb_kw, part=1, metrics=met_p, stream=st_main, precleared=pre)
-                            if not tagged:
-                                stream.wait_event(ev_c)
-                    else:
-                        run_mb(*mb_args, **mb_kw)
-                        if dp:                             # one collective: gradients + metric sums
-                            ng = m.grads.numel()
-                            m.grads_ext[ng:ng + 5].copy_(m.metrics[:5])
-                            m.grads_ext[ng + 5:ng + 6].copy_(m.metrics[8:9])
-                            self._bucket_allreduce("all", m.grads_ext)
-                            m.metrics[:5].copy_(m.grads_ext[ng:ng + 5])
-                            m.metrics[8:9].copy_(m.grads_ext[ng + 5:ng + 6])
-                    if self.minibatch_hook is not None:
-                        if split:
-                            stream.wait_stream(side)
-                            m.metrics[:5].copy_(met[:5])   # the hook reads model.metrics
-                        self.minibatch_hook(update_epoch, batch, start, rows)
-                    if hp_ is not None:
-                        t_h1 = time.perf_counter()
-                    slot = k % 2
-                    if pending is not None:
-                        info, stop = finish(pending)
-                        same_epoch = pending[3] == update_epoch
-                        pending = None
-                        if stop and same_epoch:                                    # :366-368
-                            cleared = False   # this minibatch's sums stay; no step clears them
-                            last_mb = prev_mb   # the reference never computes this one
-                            break
-                    # the optimiser step (agent :346): AdamW, the metric sums to the host and the weight
-                    # images re-derived, one dppo_optimizer_step per stream (two launches each). The actor
-                    # image skips the split sampler's tables (fold, TIN, W_XS, B_OUT2), which no PPO kernel
-                    # reads: the next rollout's first sampler launch re-derives them once
-                    # (DPPO_STEP_DEFER_SAMPLER_TABLES)
-                    if hp_ is not None:
-                        t_h2 = time.perf_counter()
-                    ng = m.grads.numel()
-                    met_out = self._met_map[slot]
-                    tag = ctag = 0
-                    if tagged:
-                        lr = opt.begin_step()
-                        self._mb_tag += 1
-                        tag = self._mb_tag
-                        if split:
-                            ctag = tag
-                            ca, cc = clear_next[(k + 1) % 2] if fuse else (None, None)
-                            if clip_actor is not None:   # the norms of what each stream's step is about to read
-                                clip_actor(stream=st_main)
-                                clip_critic(stream=st_side)
-                                clip_ran = True
-                            step_actor(lr, metrics=met_p, metrics_out=met_out.address, n_metrics=5, metrics_tag=tag,
-                                       stream=st_main, clear=ca)
-                            step_critic(lr, metrics=met_p + 8, metrics_out=self._cmet_map[slot].address,   # met[1]
-                                        n_metrics=1, metrics_tag=ctag, stream=st_side, clear=cc)
-                            cleared = fuse
-                        elif self.max_grad_norm is not None:
-                            self._clip_by_norm_per_tensor(clip_c)
-                            clip_ran = True
-                            opt.apply_range(m.grads, 0, ng, lr, m.dims, m.precision,
-                                            packs={"actor": (m.actor_ft_params, m.packed_ft),
-                                                   "critic": (m.critic_params, m.packed_critic)},
-                                            metrics=met, metrics_out=met_out.address, n_metrics=5, metrics_tag=tag,
-                                            defer_sampler_tables=defer)
-                        else:
-                            step_all(lr, metrics=met, metrics_out=met_out.address, n_metrics=5, metrics_tag=tag)
-                        if self.learn_eta and batch % self.eta_update_interval == 0:   # :358-359
-                            m.eta_optimizer_step(met, self.eta_lr_scheduler(m.eta_step_count), self.eta_weight_decay)
-                    else:
-                        torch.from_numpy(met_out.array[:5]).copy_(met[:5])
-                        cleared = False
-                    if self.update_events is not None:
-                        ev1 = torch.cuda.Event(enable_timing=True)
-                        ev1.record(stream)
-                        self.update_events.append((ev0, ev1))
-                    ev_m = None
-                    if not tag:
-                        ev_m = self._ev_m[slot]
-                        ev_m.record(stream)
-                    pending = (slot, ev_m, global_rows, update_epoch, tag, ctag)
-                    k += 1
-                    if hp_ is not None:   # host seconds: enqueue grads, wait for the previous metrics, enqueue step
-                        t_h3 = time.perf_counter()
-                        for key, dt in (("enqueue_grads", t_h1 - t_h0), ("wait_metrics", t_h2 - t_h1),
-                                        ("enqueue_step", t_h3 - t_h2)):
-                            hp_[key] = hp_.get(key, 0.0) + dt
-                        hp_["minibatches"] = hp_.get("minibatches", 0) + 1
-            if pending is not None:
-                info, _ = finish(pending)
-            if split:
-                stream.wait_stream(side)
-        stream = caller
-        # explained variance (:373-377) from the moments value_moments stored before the epochs
+                        stream.wait_stream(side)
+                        m.metrics[:5].copy_(mets[slot][:5])   # the hook reads model.metrics
+                    hook(update_epoch, batch, start, rows)
+                if hp_ is not None:
+                    t_h1 = time.perf_counter()
+                if pend.waiting:           # the previous minibatch's verdict (_PendingMetrics)
+                    same_epoch = pend.epoch == update_epoch
+                    info, stop = pend.finish()
+                    if stop and same_epoch:                                    # :366-368
+                        cleared = False   # this minibatch's sums stay; no step clears them
+                        last_mb = prev_mb   # the reference never computes this one
+                        break
+                if hp_ is not None:
+                    t_h2 = time.perf_counter()
+                if tagged:
+                    tag = pend.next_tag()
+                    step(opt.begin_step(), slot, tag)
+                    cleared = fuse
+                    if learn_eta and batch % self.eta_update_interval == 0:   # :358-359
+                        m.eta_optimizer_step(mets[slot], self.eta_lr_scheduler(m.eta_step_count), self.eta_weight_decay)
+                else:
+                    tag = 0
+                    pend.copy_in(slot, mets[slot])
+                    cleared = False
+                if events is not None:
+                    ev1 = torch.cuda.Event(enable_timing=True)
+                    ev1.record(stream)
+                    events.append((ev0, ev1))
+                pend.push(slot, global_rows, update_epoch, tag, stream)
+                k += 1
+                if hp_ is not None:   # host seconds: enqueue grads, wait for the previous metrics, enqueue step
+                    t_h3 = time.perf_counter()
+                    for key, dt in (("enqueue_grads", t_h1 - t_h0), ("wait_metrics", t_h2 - t_h1),
+                                    ("enqueue_step", t_h3 - t_h2)):
+                        hp_[key] = hp_.get(key, 0.0) + dt
+                    hp_["minibatches"] = hp_.get("minibatches", 0) + 1
+        if pend.waiting:
+            info, _ = pend.finish()
+        if split:
+            stream.wait_stream(side)
         stream.synchronize()
-        for g in (getattr(self, "_ipc_groups", None) or {}).values():
+        for g in (self._ipc_groups or {}).values():
             g.check()   # a barrier timeout in any bucket all-reduce of this update
         if self.use_bc_loss and last_mb is not None:
             info["bc_loss"] = self._bc_loss_report(last_mb, obs_flat, total_local, kf)
+        # explained variance (:373-377) from the moments value_moments stored before the epochs
         info["explained_var"] = explained_variance_from_moments(
             self._ev_map.array.copy(), self.device, group=dist.group.WORLD if self.world_size > 1 else None)
-        info["clipfrac"] = float(np.mean(clipfracs)) if clipfracs else 0.0
-        if clip_ran:   # the last applied minibatch's per-variable norms: one small copy per iteration
+        info["clipfrac"] = float(np.mean(pend.clipfracs)) if pend.clipfracs else 0.0
+        if clip_c is not None and opt.iterations > steps0:   # a clipped step ran: the last applied
+            # minibatch's per-variable norms, one small copy per iteration
             nrm = (self._clip_buf[0] if clip_dev else self._torch_norms).cpu().numpy()
             info["grad_norm_max"] = float(nrm.max())
             info["grad_clipped"] = int((nrm > np.float32(clip_c)).sum())

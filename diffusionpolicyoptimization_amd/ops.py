@@ -133,7 +133,27 @@ def _prec(precision):
 # packing
 # ------------------------------------------------------------------------------------------------
 def actor_packed_bytes(d: ModelDims, precision):
-    return int(_lib.query("dppo_actor_packed_bytes", ctypes.byref(d.c()), _prec(precision)))
+    return _packed_bytes(d, _prec(precision))[0]
+
+
+def critic_packed_bytes(d: ModelDims, precision):
+    return _packed_bytes(d, _prec(precision))[1]
+
+
+def _step_mode(mode, defer_sampler_tables=False, l2_from_pl2=False, fused_pack=False, clear_grads=False):
+    """The mode word of dppo_optimizer_step*: the AdamW flavour OR'd with the DPPO_STEP_* flags."""
+    return ((_lib.DPPO_ADAMW_KERAS if mode == "keras" else _lib.DPPO_ADAMW_TORCH) |
+            (_lib.DPPO_STEP_DEFER_SAMPLER_TABLES if defer_sampler_tables else 0) |
+            (_lib.DPPO_STEP_L2_FROM_PL2 if l2_from_pl2 else 0) |
+            (_lib.DPPO_STEP_FUSED_PACK if fused_pack else 0) |
+            (_lib.DPPO_STEP_CLEAR_GRADS if clear_grads else 0))
+
+
+def _address(x):
+    """A void* argument given as a raw address (a dppo_host_alloc block or a precomputed device
+    address), a tensor or None (NULL, as is address 0)."""
+    a = x if isinstance(x, int) or x is None else x.data_ptr()
+    return ctypes.c_void_p(a) if a else None
 
 
 def pack_all(d: ModelDims, precision, actor_params=None, packed_actor=None, critic_params=None, packed_critic=None):
@@ -172,12 +192,10 @@ def optimizer_step(d: ModelDims, precision, params, grads, m, v, step, lr, weigh
         if t.numel() != n:
             raise ValueError(f"{nm}: expected {n} elements")
     p = _prec(precision)
-    mo = metrics_out if isinstance(metrics_out, int) else (metrics_out.data_ptr() if metrics_out is not None else None)
     args = (ctypes.byref(_dims_c(d)), p, ptr(params), ptr(grads), ptr(m), ptr(v), int(n),
             int(step), float(lr), float(weight_decay), float(beta1), float(beta2), float(eps),
-            (_lib.DPPO_ADAMW_KERAS if mode == "keras" else _lib.DPPO_ADAMW_TORCH) |
-            (_lib.DPPO_STEP_DEFER_SAMPLER_TABLES if defer_sampler_tables else 0), ptr(actor_params), ptr(packed_actor),
-            ptr(critic_params), ptr(packed_critic), ptr(metrics), ctypes.c_void_p(mo) if mo else None,
+            _step_mode(mode, defer_sampler_tables), ptr(actor_params), ptr(packed_actor),
+            ptr(critic_params), ptr(packed_critic), ptr(metrics), _address(metrics_out),
             int(n_metrics), ctypes.c_uint64(int(metrics_tag)))
     if clip_scales is None:
         _lib.call("dppo_optimizer_step", *args, stream_handle(params.device))
@@ -241,9 +259,8 @@ class BoundGradClip:
         self._keep = (grads,)
 
     def __call__(self, stream=None):
-        rc = self._lib.dppo_grad_clip_scales(*self._args, stream_handle(self._dev) if stream is None else stream)
-        if rc != 0:
-            raise _lib.DppoError(f"dppo_grad_clip_scales failed ({rc}): {self._lib.dppo_last_error().decode()}")
+        _lib.check(self._lib.dppo_grad_clip_scales(*self._args, stream_handle(self._dev) if stream is None else stream),
+                   "dppo_grad_clip_scales")
         return self.scales
 
 
@@ -284,8 +301,7 @@ def value_moments(values, returns, out_address):
     n = values.numel()
     if returns.numel() != n:
         raise ValueError("values / returns: length mismatch")
-    out = out_address if isinstance(out_address, int) else out_address.data_ptr()
-    _lib.call("dppo_value_moments", ptr(values), ptr(returns), int(n), ctypes.c_void_p(out), stream_handle(values.device))
+    _lib.call("dppo_value_moments", ptr(values), ptr(returns), int(n), _address(out_address), stream_handle(values.device))
 
 
 class _HostBlock:
@@ -369,10 +385,6 @@ class MappedDoubles:
                 raise _lib.DppoError(f"mapped tag {tag} not seen within {timeout_s} s (found {a[index]})")
 
 
-def critic_packed_bytes(d: ModelDims, precision):
-    return int(_lib.query("dppo_critic_packed_bytes", ctypes.byref(d.c()), _prec(precision)))
-
-
 def pack_actor(d: ModelDims, params_flat, precision, out=None):
     """The packed image of an actor; d.activation is recorded with it (dppo_pack_actor_act) and decides
     which kernels every later launch on the image runs."""
@@ -419,7 +431,7 @@ def sample(d: ModelDims, precision, packed_base, packed_ft, sched, cond, x_T=Non
         chains = torch.empty(E, d.ft_denoising_steps + 1, d.xd, dtype=torch.float32, device=dev)
     _check(actions, (E, d.xd), torch.float32, "actions")
     _check(chains, (E, d.ft_denoising_steps + 1, d.xd), torch.float32, "chains")
-    _lib.call("dppo_sample", ctypes.byref(d.c()), _prec(precision), ptr(packed_base), ptr(packed_ft), ptr(sched),
+    _lib.call("dppo_sample", ctypes.byref(_dims_c(d)), _prec(precision), ptr(packed_base), ptr(packed_ft), ptr(sched),
               ptr(cond), E, ptr(x_T), ptr(noise), ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(call_id),
               int(env_offset), int(bool(deterministic)), float(min_sampling_std), float(randn_clip),
               float(final_clip) if final_clip is not None else 0.0, ptr(actions), ptr(chains), stream_handle(dev))
@@ -507,10 +519,9 @@ class SampleStepper:
         m = self.model
         cond_host, actions, actions_host = self._fixed
         common, scalars = _step_args(m, self._dims, deterministic)
-        rc = self._fn(*common, cond_host, ctypes.c_void_p(self._obs0 + i * self._obs_step), self.E, *scalars,
-                      actions, actions_host, ctypes.c_void_p(self._ch0 + i * self._ch_step), 1, self._stream)
-        if rc:
-            raise _lib.DppoError(f"dppo_sample_step failed ({rc}): {_lib.load().dppo_last_error().decode()}")
+        _lib.check(self._fn(*common, cond_host, ctypes.c_void_p(self._obs0 + i * self._obs_step), self.E, *scalars,
+                            actions, actions_host, ctypes.c_void_p(self._ch0 + i * self._ch_step), 1, self._stream),
+                   "dppo_sample_step")
         m._call_id += 1
 
 
@@ -582,8 +593,7 @@ class RolloutPipe:
         else:
             rc = self._fn(*common, p["obs"], obs_dev, *tail, p["go"], ctypes.c_uint32(self.enqueued), p["done"],
                           self._stream)
-        if rc:
-            raise _lib.DppoError(f"dppo_rollout_enqueue failed ({rc}): {self._lib.dppo_last_error().decode()}")
+        _lib.check(rc, "dppo_rollout_enqueue")
         m._call_id += 1
 
     def launch_event(self, ev=None):
@@ -636,7 +646,6 @@ class RolloutPipe:
         self.published += 1
 
     def wait(self, timeout_s=30.0):
-        import time
         self.finished += 1
         target = self.finished * self.nwg
         done = self._done
@@ -689,7 +698,7 @@ def logprob(d: ModelDims, precision, packed_ft, sched, cond, chains, min_logprob
     _check(lp_elem, (n * kf, d.xd), torch.float32, "lp_elem")
     _check(lp_mean, (n, kf), torch.float32, "lp_mean")
     rh = d.horizon_steps if reward_horizon is None else int(reward_horizon)
-    _lib.call("dppo_logprob", ctypes.byref(d.c()), _prec(precision), ptr(packed_ft), ptr(sched), ptr(cond),
+    _lib.call("dppo_logprob", ctypes.byref(_dims_c(d)), _prec(precision), ptr(packed_ft), ptr(sched), ptr(cond),
               ptr(chains), n, float(min_logprob_std), rh, ptr(lp_elem), ptr(lp_mean), stream_handle(dev))
     return lp_elem, lp_mean
 
@@ -701,7 +710,7 @@ def critic_forward(d: ModelDims, precision, packed_critic, cond, values=None):
     if values is None:
         values = torch.empty(n, dtype=torch.float32, device=cond.device)
     _check(values, (n,), torch.float32, "values")
-    _lib.call("dppo_critic_forward", ctypes.byref(d.c()), _prec(precision), ptr(packed_critic), ptr(cond), n,
+    _lib.call("dppo_critic_forward", ctypes.byref(_dims_c(d)), _prec(precision), ptr(packed_critic), ptr(cond), n,
               ptr(values), stream_handle(cond.device))
     return values
 
@@ -810,8 +819,7 @@ def feistel_permute(first, count, n, seed, epoch, device):
 
 
 def ppo_workspace(d: ModelDims, precision, rows, device):
-    nbytes = int(_lib.query("dppo_ppo_workspace_bytes", ctypes.byref(d.c()), _prec(precision), int(rows)))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return torch.empty(_workspace_bytes(d, _prec(precision), int(rows)), dtype=torch.uint8, device=device)
 
 
 _PLAN_MODES = {"train": 0, "pretrain": 1, "logprob": 2}
@@ -892,9 +900,10 @@ def materialize_l2(d: ModelDims, precision, packed_actor, grads, workspace, batc
               ptr(workspace), int(batch_rows), stream_handle(grads.device))
 
 
-def ppo_minibatch(d: ModelDims, precision, hp, packed_ft, packed_critic, actor_params, sched, obs, chains, lp_old_mean,
-                  advantages, returns, perm_seed, epoch, start, rows, workspace, grads, metrics, adv_stats=None,
-                  row_index=None, part=None):
+def _check_minibatch_buffers(d, precision, obs, chains, lp_old_mean, advantages, returns, actor_params, grads,
+                             workspace, rows):
+    """The buffers every PPO minibatch launch reads and writes, against the rollout's sample count n
+    (returned) and the workspace a launch of `rows` rows needs."""
     n = obs.shape[0]
     kf = d.ft_denoising_steps
     _check(obs, (n, d.sd), torch.float32, "obs")
@@ -905,14 +914,23 @@ def ppo_minibatch(d: ModelDims, precision, hp, packed_ft, packed_critic, actor_p
     na, nc = _n_params(d)
     _check(actor_params, (na,), torch.float32, "actor_params")
     _check(grads, (na + nc,), torch.float32, "grads")
+    need = _workspace_bytes(d, _prec(precision), int(rows))
+    if workspace.numel() < need:
+        raise ValueError(f"workspace too small: {workspace.numel()} < {need}")
+    return n
+
+
+def ppo_minibatch(d: ModelDims, precision, hp, packed_ft, packed_critic, actor_params, sched, obs, chains, lp_old_mean,
+                  advantages, returns, perm_seed, epoch, start, rows, workspace, grads, metrics, adv_stats=None,
+                  row_index=None, part=None):
+    n = _check_minibatch_buffers(d, precision, obs, chains, lp_old_mean, advantages, returns, actor_params, grads,
+                                 workspace, rows)
+    kf = d.ft_denoising_steps
     _check(metrics, (16,), torch.float64, "metrics")
     if row_index is not None:
         _check(row_index, (row_index.numel(),), torch.int64, "row_index")
         if row_index.numel() < start + rows:
             raise ValueError("row_index shorter than start + rows")
-    need = _workspace_bytes(d, _prec(precision), int(rows))
-    if workspace.numel() < need:
-        raise ValueError(f"workspace too small: {workspace.numel()} < {need}")
     args = (ctypes.byref(_dims_c(d)), _prec(precision), ctypes.byref(hp), ptr(packed_ft), ptr(packed_critic),
             ptr(actor_params), ptr(sched), ptr(obs), ptr(chains), ptr(lp_old_mean), ptr(advantages), ptr(returns),
             int(n * kf), ctypes.c_uint64(perm_seed), int(epoch), int(start), int(rows), ptr(row_index), ptr(adv_stats),
@@ -931,19 +949,9 @@ class BoundMinibatch:
 
     def __init__(self, d: ModelDims, precision, packed_ft, packed_critic, actor_params, sched, obs, chains,
                  lp_old_mean, advantages, returns, perm_seed, workspace, grads, max_rows):
-        n = obs.shape[0]
+        n = _check_minibatch_buffers(d, precision, obs, chains, lp_old_mean, advantages, returns, actor_params, grads,
+                                     workspace, max_rows)
         kf = d.ft_denoising_steps
-        _check(obs, (n, d.sd), torch.float32, "obs")
-        _check(chains, (n, kf + 1, d.xd), torch.float32, "chains")
-        _check(lp_old_mean, (n, kf), torch.float32, "lp_old_mean")
-        _check(advantages, (n,), torch.float32, "advantages")
-        _check(returns, (n,), torch.float32, "returns")
-        na, nc = _n_params(d)
-        _check(actor_params, (na,), torch.float32, "actor_params")
-        _check(grads, (na + nc,), torch.float32, "grads")
-        need = _workspace_bytes(d, _prec(precision), int(max_rows))
-        if workspace.numel() < need:
-            raise ValueError(f"workspace too small: {workspace.numel()} < {need}")
         self.max_rows = int(max_rows)
         self._lib = _lib.load()
         self._dims = _dims_c(d)
@@ -974,8 +982,7 @@ class BoundMinibatch:
             rc = self._lib.dppo_ppo_minibatch(*args, st)
         else:
             rc = self._lib.dppo_ppo_minibatch_part(*args, int(part), st)
-        if rc != 0:
-            raise _lib.DppoError(f"dppo_ppo_minibatch failed ({rc}): {self._lib.dppo_last_error().decode()}")
+        _lib.check(rc, "dppo_ppo_minibatch")
 
 
 class BoundOptimizerStep:
@@ -996,11 +1003,7 @@ class BoundOptimizerStep:
                 raise ValueError(f"{nm}: expected {n} elements")
         self._lib = _lib.load()
         self._dims = _dims_c(d)
-        mode_i = ((_lib.DPPO_ADAMW_KERAS if mode == "keras" else _lib.DPPO_ADAMW_TORCH) |
-                  (_lib.DPPO_STEP_DEFER_SAMPLER_TABLES if defer_sampler_tables else 0) |
-                  (_lib.DPPO_STEP_L2_FROM_PL2 if l2_from_pl2 else 0) |
-                  (_lib.DPPO_STEP_FUSED_PACK if fused_pack else 0) |
-                  (_lib.DPPO_STEP_CLEAR_GRADS if clear_grads else 0))
+        mode_i = _step_mode(mode, defer_sampler_tables, l2_from_pl2, fused_pack, clear_grads)
         self._head = (ctypes.byref(self._dims), _prec(precision), ptr(params), ptr(grads), ptr(m), ptr(v), int(n))
         self._hp = (float(weight_decay), float(beta1), float(beta2), float(eps), mode_i, ptr(actor_params),
                     ptr(packed_actor), ptr(critic_params), ptr(packed_critic))
@@ -1016,14 +1019,11 @@ class BoundOptimizerStep:
         """metrics_out: a device tensor or a dppo_host_alloc address (as optimizer_step); metrics: a
         device tensor or address; stream: a raw stream handle (default: the current stream); clear: a
         ClearRanges (byte ranges zeroed after the step's last read, dppo_optimizer_step_ex)."""
-        mo = metrics_out if isinstance(metrics_out, int) else (metrics_out.data_ptr() if metrics_out is not None else None)
-        mi = metrics if isinstance(metrics, int) else ptr(metrics)
         cp, cb, cn = (None, None, 0) if clear is None else clear.args
-        rc = self._fn(*self._head, int(step), float(lr), *self._hp, mi, ctypes.c_void_p(mo) if mo else None,
-                      int(n_metrics), ctypes.c_uint64(int(metrics_tag)), cp, cb, cn,
-                      stream_handle(self._dev) if stream is None else stream, *self._clip)
-        if rc != 0:
-            raise _lib.DppoError(f"dppo_optimizer_step failed ({rc}): {self._lib.dppo_last_error().decode()}")
+        _lib.check(self._fn(*self._head, int(step), float(lr), *self._hp, _address(metrics), _address(metrics_out),
+                            int(n_metrics), ctypes.c_uint64(int(metrics_tag)), cp, cb, cn,
+                            stream_handle(self._dev) if stream is None else stream, *self._clip),
+                   "dppo_optimizer_step")
 
 
 class ClearRanges:
@@ -1037,11 +1037,9 @@ class ClearRanges:
         self._ptrs = (ctypes.c_void_p * 4)()
         self._bytes = (ctypes.c_size_t * 4)()
         cnt = ctypes.c_int(0)
-        mptr = metrics if isinstance(metrics, int) else metrics.data_ptr()
-        rc = lib.dppo_ppo_clear_ranges(ctypes.byref(_dims_c(d)), _prec(precision), int(rows), ptr(workspace),
-                                       ctypes.c_void_p(mptr), int(part), self._ptrs, self._bytes, ctypes.byref(cnt))
-        if rc != 0:
-            raise _lib.DppoError(f"dppo_ppo_clear_ranges failed ({rc}): {lib.dppo_last_error().decode()}")
+        _lib.check(lib.dppo_ppo_clear_ranges(ctypes.byref(_dims_c(d)), _prec(precision), int(rows), ptr(workspace),
+                                             _address(metrics), int(part), self._ptrs, self._bytes, ctypes.byref(cnt)),
+                   "dppo_ppo_clear_ranges")
         self.count = cnt.value
         self.args = (self._ptrs, self._bytes, self.count)
         self._keep = (workspace, metrics)
@@ -1068,15 +1066,15 @@ def pretrain_minibatch(d: ModelDims, precision, packed_actor, actor_params, sche
     _check(t, (n,), torch.int32, "t")
     _check(noise, (n, d.xd), torch.float32, "noise")
     _check(qsched, (d.denoising_steps, 2), torch.float32, "qsched")
-    na = spec_count(actor_param_spec(d))
+    na = _n_params(d)[0]
     _check(actor_params, (na,), torch.float32, "actor_params")
     if grads.numel() < na:
         raise ValueError("grads: needs at least the actor parameter count")
     _check(metrics, (16,), torch.float64, "metrics")
-    need = int(_lib.query("dppo_ppo_workspace_bytes", ctypes.byref(d.c()), _prec(precision), int(n)))
+    need = _workspace_bytes(d, _prec(precision), int(n))
     if workspace.numel() < need:
         raise ValueError(f"workspace too small: {workspace.numel()} < {need}")
-    _lib.call("dppo_pretrain_minibatch", ctypes.byref(d.c()), _prec(precision), ptr(packed_actor), ptr(actor_params),
+    _lib.call("dppo_pretrain_minibatch", ctypes.byref(_dims_c(d)), _prec(precision), ptr(packed_actor), ptr(actor_params),
               ptr(sched), ptr(qsched), ptr(x_start), ptr(cond), ptr(t), ptr(noise), int(n), int(g), float(loss_scale),
               ptr(workspace), ptr(grads), ptr(metrics), stream_handle(x_start.device))
     return metrics[0] * (float(loss_scale) / (g * d.xd))

@@ -27,6 +27,9 @@ SCHED_COLS = 8
 PRECISION = {"fp32": DPPO_F32, "f32": DPPO_F32, "bf16": DPPO_BF16, "fp16": DPPO_F16, "f16": DPPO_F16}
 # the actor's activation_type (DPPO_ACT_*): an attribute of a packed actor image (dppo_pack_actor_act)
 ACTIVATION = {"ReLU": 0, "Mish": 1}
+# the actor's head (DPPO_HEAD_*), the image's second attribute (dppo_pack_actor_head): "residual" is
+# ResidualMLP (residual_style=True), "plain" the reference's MLP([in, h, h, out]) (residual_style=False)
+HEAD = {"residual": 0, "plain": 1}
 
 
 class DppoDims(ctypes.Structure):
@@ -63,6 +66,7 @@ _SIGNATURES = {
     "dppo_pack_actor": (_I, [_DIMS, _I, _P, _P, _P]),
     "dppo_pack_critic": (_I, [_DIMS, _I, _P, _P, _P]),
     "dppo_pack_actor_act": (_I, [_DIMS, _I, _I, _P, _P, _P]),
+    "dppo_pack_actor_head": (_I, [_DIMS, _I, _I, _I, _P, _P, _P]),
     "dppo_sample": (_I, [_DIMS, _I, _P, _P, _P, _P, _I, _P, _P, _U64, _U64, _I, _I, _F, _F, _F, _P, _P, _P]),
     "dppo_sample_step": (_I, [_DIMS, _I, _P, _P, _P, _P, _P, _I, _U64, _U64, _I, _I, _F, _F, _F, _P, _P, _P, _I, _P]),
     "dppo_host_alloc": (_I, [_SZ, ctypes.POINTER(ctypes.c_void_p)]),

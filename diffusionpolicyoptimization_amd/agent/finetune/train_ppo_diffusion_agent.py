@@ -886,13 +886,12 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         o = 0
         norms = []
         for spec in (self.model.actor_spec, self.model.critic_spec):
-            for _, shape in spec:
-                k = int(np.prod(shape))
-                seg = g[o:o + k]
+            for _, _, off, k in ops.spec_ranges(spec):   # a plain-head actor's spec skips its unused l2 range
+                seg = g[o + off:o + off + k]
                 nrm = torch.linalg.vector_norm(seg)
                 seg.mul_(torch.clamp(clip_norm / torch.clamp(nrm, min=1e-30), max=1.0))
                 norms.append(nrm)
-                o += k
+            o += ops.spec_count(spec)
         self._torch_norms = torch.stack(norms)
 
     # ------------------------------------------------------------------ one iteration / the loop

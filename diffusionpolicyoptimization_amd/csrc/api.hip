@@ -64,18 +64,25 @@ extern "C" size_t dppo_critic_packed_bytes(const dppo_dims* d, int precision) {
     if (dppo_check_dims(d, &D)) return 0;
     return make_mlp_layout(D.SD, D.HC, 1, 0, precision).total;
 }
-extern "C" int dppo_pack_actor_act(const dppo_dims* d, int precision, int activation, const float* params,
-                                   void* packed, void* stream) {
+extern "C" int dppo_pack_actor_head(const dppo_dims* d, int precision, int activation, int head, const float* params,
+                                    void* packed, void* stream) {
     Dims D;
     int rc = dppo_check_dims(d, &D);
     if (rc) return rc;
     DPPO_CHECK(params && packed, "dppo_pack_actor: null pointer");
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
     DPPO_CHECK(dppo_act_ok(activation), "dppo_pack_actor_act: bad activation %d (DPPO_ACT_RELU or DPPO_ACT_MISH)", activation);
+    DPPO_CHECK(dppo_head_ok(head), "dppo_pack_actor_head: bad head %d (DPPO_HEAD_RESIDUAL or DPPO_HEAD_PLAIN)", head);
+    const int old_head = dppo_actor_image_head(packed);
+    dppo_actor_image_set_head(packed, head);        // the pack's jobs and the fold launch follow the image's head
     rc = dppo_pack_mlp(D.IN, D.H, D.XD, D.TD, precision, params, packed, (hipStream_t)stream, D.K, D.TS);
-    if (rc) return rc;
+    if (rc) { dppo_actor_image_set_head(packed, old_head); return rc; }   // refused: nothing was written
     dppo_actor_image_set_act(packed, activation);   // the image is this activation's from here on
     return DPPO_OK;
+}
+extern "C" int dppo_pack_actor_act(const dppo_dims* d, int precision, int activation, const float* params,
+                                   void* packed, void* stream) {
+    return dppo_pack_actor_head(d, precision, activation, DPPO_HEAD_RESIDUAL, params, packed, stream);
 }
 extern "C" int dppo_pack_actor(const dppo_dims* d, int precision, const float* params, void* packed, void* stream) {
     return dppo_pack_actor_act(d, precision, DPPO_ACT_RELU, params, packed, stream);

@@ -492,7 +492,7 @@ int time_bwd_check(const Dims& D, int nb) {
 // after the actor's dW: the time-MLP backward over nb buckets at t = q * TS (the bucket sums in gseg),
 // W_out's gradient (out_back) and, unless the l2 gradient stays factored, l2's from pl2, in one launch
 int launch_time_bwd(const Dims& D, int precision, const PpoWorkspace& ws, const void* packed_actor,
-                    const float* actor_params, float* ga, int nb, int TS, hipStream_t s, bool l2_back) {
+                    const float* actor_params, float* ga, int nb, int TS, hipStream_t s, bool l2_back, bool plain) {
     const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
     const float* gseg = ws.gseg;
     const float* pl2 = l2_back ? ws.pl2 : ga + FA.l2_w;   // factored: the dW left pl2 in l2's own region
@@ -509,7 +509,10 @@ int launch_time_bwd(const Dims& D, int precision, const PpoWorkspace& ws, const 
     const size_t tsm = tsm0 > sizeof(float) * OB_RED * (TB_THREADS / 256) ? tsm0 : sizeof(float) * OB_RED * (TB_THREADS / 256);
     DPPO_CHECK(tsm <= 160 * 1024, "time_bwd: LDS staging %zu B exceeds 160 KB", tsm);
     const int per = TB_THREADS / 256;
-    const int l2g = l2_back ? dppo_cdiv(D.H, L2B_ROWS) : 0, obg = dppo_cdiv(D.H, ob_rows(l2_nq(D.XD)));
+    // a plain head has neither product: the dW wrote u2^T dy into W_out's own region and l2's stays zero, so
+    // the launch is the time-MLP backward's workgroup alone
+    const int l2g = l2_back && !plain ? dppo_cdiv(D.H, L2B_ROWS) : 0;
+    const int obg = plain ? 0 : dppo_cdiv(D.H, ob_rows(l2_nq(D.XD)));
     const int nq = l2_nq(D.XD);
     const void* fn = time_l2_bwd_fn(precision, nq);
     { const int rc_ = dppo_func_lds(fn, tsm); if (rc_) return rc_; }
@@ -545,6 +548,8 @@ extern "C" int dppo_materialize_l2(const dppo_dims* d, int precision, const void
     if (rc) return rc;
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
     DPPO_CHECK(packed_actor && grads && workspace && batch_rows > 0, "dppo_materialize_l2: bad arguments");
+    // a plain-head image has no l2 layer: its minibatch deferred nothing and the l2 range is already its final zero
+    if (dppo_actor_image_head(packed_actor) == DPPO_HEAD_PLAIN) return DPPO_OK;
     hipStream_t s = (hipStream_t)stream;
     const PpoWorkspace ws = make_ppo_workspace(D, precision, batch_rows, (uint8_t*)workspace);
     const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);

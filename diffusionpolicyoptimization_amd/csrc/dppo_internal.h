@@ -48,6 +48,12 @@ int dppo_mark_tables_stale(const Dims& D, int precision, const float* actor_para
 int dppo_actor_image_act(const void* packed);
 void dppo_actor_image_set_act(const void* packed, int activation);
 inline bool dppo_act_ok(int a) { return a == DPPO_ACT_RELU || a == DPPO_ACT_MISH; }
+// the head (DPPO_HEAD_*) recorded the same way (dppo_pack_actor_head): RESIDUAL for an unlisted address. The
+// pack, the fold launch, the fused step's job list and the table refresh look it up by the image's address,
+// so an entry that packs sets it BEFORE it packs
+int dppo_actor_image_head(const void* packed);
+void dppo_actor_image_set_head(const void* packed, int head);
+inline bool dppo_head_ok(int h) { return h == DPPO_HEAD_RESIDUAL || h == DPPO_HEAD_PLAIN; }
 // device address of mapped pinned host memory (dppo_host_alloc), cached; null if not mapped (host_staging.hip)
 void* mapped_ptr(const void* host);
 

@@ -33,9 +33,11 @@ DWPlan dw_plan(DWTile tile, const DWItem* items, int n_items, size_t ldm, int mi
 // ---- backward_tail.hip: what follows the dW launches -------------------------------------------
 // after the actor's dW: the time-MLP backward over nb buckets at t = q * TS (the bucket sums in
 // ws.gseg), W_out's gradient (out_back) and, with l2_back, l2's from ws.pl2, in one launch; without
-// l2_back the l2 gradient stays factored in its own region of ga (DPPO_PPO_L2_DEFERRED)
+// l2_back the l2 gradient stays factored in its own region of ga (DPPO_PPO_L2_DEFERRED); plain (a
+// DPPO_HEAD_PLAIN image): the time-MLP backward alone (the dW left W_out's gradient in place, l2's is zero)
 int launch_time_bwd(const Dims& D, int precision, const PpoWorkspace& ws, const void* packed_actor,
-                    const float* actor_params, float* ga, int nb, int TS, hipStream_t s, bool l2_back = true);
+                    const float* actor_params, float* ga, int nb, int TS, hipStream_t s, bool l2_back = true,
+                    bool plain = false);
 // host check only: DPPO_EUNSUPPORTED ("time_bwd needs %zu B LDS") where launch_time_bwd's workgroup
 // over nb buckets would not fit a CU's 160 KiB; callers ask before their first launch
 int time_bwd_check(const Dims& D, int nb);

@@ -464,6 +464,8 @@ static int step_prologue(const StepArgs& a, StepCtx& c) {
     c.FC = make_flat_offsets(D.SD, D.HC, 1, 0);
     c.vt = L2Virt{};
     if (c.l2v) {
+        DPPO_CHECK(!a.packed_actor || dppo_actor_image_head(a.packed_actor) != DPPO_HEAD_PLAIN,
+                   "dppo_optimizer_step: DPPO_STEP_L2_FROM_PL2 on a plain-head actor image (it has no l2 layer)");
         DPPO_CHECK(a.packed_actor && a.actor_params == a.w.params,
                    "dppo_optimizer_step: DPPO_STEP_L2_FROM_PL2 needs the actor's image and the actor range first");
         DPPO_CHECK(a.w.n >= (int64_t)c.FA.count, "dppo_optimizer_step: DPPO_STEP_L2_FROM_PL2 needs the whole actor range");

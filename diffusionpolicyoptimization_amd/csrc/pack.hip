@@ -27,6 +27,7 @@ struct TembArgs {
     const float* params;
     FlatOffsets F;
     int TD, stride, R, XD, H, nout, tables, nfold;
+    int plain;            // DPPO_HEAD_PLAIN image: no l2 layer, no skip (dppo_layout.h "plain head")
     int first_table;      // table block b runs time_table_block(first_table + b): R skips the TEMB rows
     float *temb, *tin, *bout2;
     uint8_t *fold, *rout;
@@ -63,7 +64,7 @@ __device__ void time_table_block(const TembArgs& b, int blk) {
 #pragma unroll
             for (int q = 0; q < 32; ++q) acc[q] = 0.f;
             for (int h = tid; h < H; h += 128) {
-                const float bl2 = params[F.l2_b + h];
+                const float bl2 = b.plain ? 0.f : params[F.l2_b + h];   // plain head: B_OUT2 = b_out
 #pragma unroll
                 for (int q = 0; q < 32; ++q)
                     if (q < XD) acc[q] += bl2 * (float)(ET)params[F.out_w + (size_t)h * XD + q];
@@ -119,6 +120,23 @@ __device__ void fold_block(const TembArgs& b, int T) {
         const float* params = b.params;
         const FlatOffsets& F = b.F;
         const float* wo = params + F.out_w;
+        if (b.plain) {   // plain head: M = rnd(W_out) (hi exact, lo zero), no residual term (ROUT zero)
+            if (tid < 64 * nt_out) {
+                const int lane = tid & 63, n = tid >> 6, o = 16 * n + (lane & 15), jq = lane >> 4;
+                ET e[8], w[8];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int f = 16 * T + 4 * jq + q;
+                    e[q] = (ET)((o < XD && f < H) ? wo[(size_t)f * XD + o] : 0.f);
+                    e[4 + q] = (ET)0.f;
+                    w[q] = w[4 + q] = (ET)0.f;
+                }
+                const size_t idx = ((size_t)T * nt_out + n) * 64 + lane;
+                reinterpret_cast<u32x4*>(b.fold)[idx] = __builtin_bit_cast(u32x4, e);
+                reinterpret_cast<u32x4*>(b.rout)[idx] = __builtin_bit_cast(u32x4, w);
+            }
+            return;   // the whole block: no barrier is skipped
+        }
         const int XDP = XD <= 16 ? 16 : 32, JC = XD <= 16 ? JMAX : JMAX / 2;
         const int g = tid >> 6, fr = (tid & 63) >> 2, oq = tid & 3;
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -220,6 +238,7 @@ struct RtFoldArgs {
     size_t off_wout, off_tl2, off_fold, off_fold0, off_tfold, off_bout, off_temb;
     int H, XD, IN, nt_out, ks_h, ks_in, ks_out_t, nm, nm0;
     int TD, TS, R;        // the TEMB table's rows (row r = t_emb(r TS), r < R)
+    int plain;            // DPPO_HEAD_PLAIN: M = rnd(W_out), M0 = 0, RT_BOUT = b_out (no MFMA, no bias fold)
 };
 // one M (M0) tile: NO out tiles, the k-steps in batches of KB whose loads are all issued before the
 // batch's MFMAs, with no branch inside a batch (a conditional load made hipcc wait vmcnt(0) per k-step:
@@ -339,6 +358,10 @@ __global__ __launch_bounds__(64) void rt_fold_kernel(RtFoldArgs a) {
     }
     const __amdgpu_buffer_rsrc_t rs = packed_rsrc(a.img);
     if (b == a.nm + a.nm0) {   // RT_BOUT
+        if (a.plain) {
+            if (lane < 16 * a.nt_out) ((float*)(a.img + a.off_bout))[lane] = lane < XD ? prm[a.F.out_b + lane] : 0.f;
+            return;
+        }
         if (a.nt_out > 1) rt_fold_bias<P, 2>(a, rs, lane);
         else rt_fold_bias<P, 1>(a, rs, lane);
         return;
@@ -346,7 +369,12 @@ __global__ __launch_bounds__(64) void rt_fold_kernel(RtFoldArgs a) {
     const bool m0 = b >= a.nm;
     const int T = m0 ? b - a.nm : b;
     const int kb4 = a.ks_h % 8 ? 4 : 8;   // k-steps per batch (H = 128 / 384 with 2-byte operands: 4)
-    if (m0) {
+    if (a.plain) {   // the tile's M values read off W_out (rounded as the pack rounds); M0 tiles are zero
+        for (int idx = lane; idx < 32 * 16; idx += 64) {
+            const int o = idx >> 4, i = idx & 15, f = 16 * T + i;
+            sm[o][i] = (!m0 && o < XD && f < H) ? (float)(AT)prm[a.F.out_w + (size_t)f * XD + o] : 0.f;
+        }
+    } else if (m0) {
         if (a.nt_out > 1) { if (kb4 == 8) rt_fold_tile<P, 2, 8, true>(a, rs, T, lane, sm); else rt_fold_tile<P, 2, 4, true>(a, rs, T, lane, sm); }
         else { if (kb4 == 8) rt_fold_tile<P, 1, 8, true>(a, rs, T, lane, sm); else rt_fold_tile<P, 1, 4, true>(a, rs, T, lane, sm); }
     } else {
@@ -480,6 +508,7 @@ static int add_mlp_jobs(PackArgs& a, int in_dim, int hidden, int out_dim, int ti
     const FlatOffsets F = make_flat_offsets(in_dim, hidden, out_dim, time_dim);
     const int KG = dppo_prec_2b(precision) ? 32 : 16;
     const bool actor = time_dim > 0;
+    const bool plain = actor && dppo_actor_image_head(packed) == DPPO_HEAD_PLAIN;
     // the split sampler's tables (every precision since r06: fp32 runs the split kernel at P = 4, its fold
     // from RT_FOLD and its residual from W_OUT, so only the 2-byte images carry FOLD / ROUT)
     const bool split_tables = actor && L.temb_steps > 0;
@@ -509,7 +538,13 @@ static int add_mlp_jobs(PackArgs& a, int in_dim, int hidden, int out_dim, int ti
         mat(F.out_w, hidden, out_dim, false, SEG_W_OUT);
         cpy(F.out_b, out_dim, 16 * L.nt_out, SEG_B_OUT);
         // transposed images: W^T viewed as a [K'=out][N'=in] weight, i.e. element (k', n') = W[n'][k']
-        mat(F.out_w, out_dim, hidden, true, SEG_T_OUT);
+        if (plain) {   // dh3 = dy W_out^T is the skip's share of dh1: none (the whole segment is zero)
+            PackJob& J = a.j[a.njobs++];
+            J.kind = 2; J.dst = P_out(packed) + L.off[SEG_T_OUT];
+            J.n = (int)(packed_matrix_bytes(out_dim, hidden, KG) / 4); J.threads = (J.n + 3) / 4;
+        } else {
+            mat(F.out_w, out_dim, hidden, true, SEG_T_OUT);
+        }
         mat(F.l2_w, hidden, hidden, true, SEG_T_L2);   // the actor's: the A operand of its fold (rt_fold_kernel)
         mat(F.l1_w, hidden, hidden, true, SEG_T_L1);
     }
@@ -527,7 +562,7 @@ static int add_mlp_jobs(PackArgs& a, int in_dim, int hidden, int out_dim, int ti
         if (a.tb.params) return dppo_set_error(DPPO_EINVAL, "pack: one actor per launch");
         TembArgs& b = a.tb;
         b.params = params; b.F = F; b.TD = time_dim; b.stride = time_stride; b.R = L.temb_steps; b.XD = out_dim;
-        b.H = hidden; b.nout = 16 * L.nt_out;
+        b.H = hidden; b.nout = 16 * L.nt_out; b.plain = plain ? 1 : 0;
         b.temb = (float*)(P_out(packed) + L.off[SEG_TEMB]);
         b.tin = (float*)(P_out(packed) + L.off[SEG_TIN]);
         b.bout2 = (float*)(P_out(packed) + L.off[SEG_B_OUT2]);
@@ -546,6 +581,8 @@ static int add_mlp_jobs(PackArgs& a, int in_dim, int hidden, int out_dim, int ti
 // geometry; the TEMB table is derived separately (the fused step's last workgroup)
 int dppo_fuse_jobs(int in_dim, int hidden, int out_dim, int time_dim, int precision, void* packed, int temb_steps,
                    FuseJob* jobs) {
+    // a plain-head actor image keeps T_OUT zero (add_mlp_jobs): W_out has no transposed slots to rewrite
+    const bool plain = time_dim > 0 && dppo_actor_image_head(packed) == DPPO_HEAD_PLAIN;
     const MlpLayout L = make_mlp_layout(in_dim, hidden, out_dim, time_dim, precision, temb_steps);
     const FlatOffsets F = make_flat_offsets(in_dim, hidden, out_dim, time_dim);
     const int KG = dppo_prec_2b(precision) ? 32 : 16;
@@ -567,7 +604,7 @@ int dppo_fuse_jobs(int in_dim, int hidden, int out_dim, int time_dim, int precis
     job(1, F.l2_w, hh, hidden, hidden, SEG_T_L2);
     job(2, F.l2_b, hidden, 0, 0, SEG_B_L2);
     job(0, F.out_w, ho, hidden, out_dim, SEG_W_OUT);
-    job(1, F.out_w, ho, out_dim, hidden, SEG_T_OUT);
+    if (!plain) job(1, F.out_w, ho, out_dim, hidden, SEG_T_OUT);
     job(2, F.out_b, out_dim, 0, 0, SEG_B_OUT);
     return n <= FUSE_MAXJ ? n : -1;
 }
@@ -620,26 +657,42 @@ int mark_stale(const Dims& D, int precision, const float* params, const void* pa
 }
 }  // namespace
 
-// The activation of an actor image (include/dppo.h, dppo_pack_actor_act): only Mish images are listed
-// (ReLU, the default of an unlisted address, erases the entry), keyed by the image's address like g_stale.
+// The attributes of an actor image (include/dppo.h, dppo_pack_actor_act / dppo_pack_actor_head): its
+// activation and its head. Only images with a non-default attribute are listed (ReLU / RESIDUAL, the
+// defaults of an unlisted address, erase the entry), keyed by the image's address like g_stale.
 namespace {
-std::mutex g_act_mu;
-std::vector<const void*> g_mish;
-}  // namespace
-int dppo_actor_image_act(const void* packed) {
-    std::lock_guard<std::mutex> lk(g_act_mu);
-    for (const void* p : g_mish)
-        if (p == packed) return DPPO_ACT_MISH;
-    return DPPO_ACT_RELU;
+struct ImageAttr { const void* packed; int act, head; };
+std::mutex g_attr_mu;
+std::vector<ImageAttr> g_attr;
+ImageAttr image_attr(const void* packed) {
+    std::lock_guard<std::mutex> lk(g_attr_mu);
+    for (const ImageAttr& e : g_attr)
+        if (e.packed == packed) return e;
+    return ImageAttr{packed, DPPO_ACT_RELU, DPPO_HEAD_RESIDUAL};
 }
-void dppo_actor_image_set_act(const void* packed, int activation) {
-    std::lock_guard<std::mutex> lk(g_act_mu);
-    for (size_t i = 0; i < g_mish.size(); ++i)
-        if (g_mish[i] == packed) {
-            if (activation != DPPO_ACT_MISH) { g_mish[i] = g_mish.back(); g_mish.pop_back(); }
+void set_image_attr(const ImageAttr& a) {
+    std::lock_guard<std::mutex> lk(g_attr_mu);
+    const bool dflt = a.act == DPPO_ACT_RELU && a.head == DPPO_HEAD_RESIDUAL;
+    for (size_t i = 0; i < g_attr.size(); ++i)
+        if (g_attr[i].packed == a.packed) {
+            if (dflt) { g_attr[i] = g_attr.back(); g_attr.pop_back(); }
+            else g_attr[i] = a;
             return;
         }
-    if (activation == DPPO_ACT_MISH) g_mish.push_back(packed);
+    if (!dflt) g_attr.push_back(a);
+}
+}  // namespace
+int dppo_actor_image_act(const void* packed) { return image_attr(packed).act; }
+int dppo_actor_image_head(const void* packed) { return image_attr(packed).head; }
+void dppo_actor_image_set_act(const void* packed, int activation) {
+    ImageAttr a = image_attr(packed);
+    a.act = activation;
+    set_image_attr(a);
+}
+void dppo_actor_image_set_head(const void* packed, int head) {
+    ImageAttr a = image_attr(packed);
+    a.head = head;
+    set_image_attr(a);
 }
 
 // the fused step leaves the actor image's split-sampler tables stale like a PACK_UPDATE pack
@@ -680,6 +733,7 @@ int dppo_pack_rt_fold(int in_dim, int hidden, int out_dim, int time_dim, int pre
     a.nm0 = L.ks_in * L.KG / 16;   // RT_FOLD0's padded k range, 16 rows per tile
     // and the TEMB table (one block per row): the row tiles read their time embeddings from it
     a.off_temb = L.off[SEG_TEMB]; a.TD = time_dim; a.TS = time_stride; a.R = L.temb_steps;
+    a.plain = dppo_actor_image_head(packed_actor) == DPPO_HEAD_PLAIN ? 1 : 0;
     if (time_dim > 32) return dppo_set_error(DPPO_EUNSUPPORTED, "row-tile fold: time_dim %d > 32", time_dim);
     const dim3 grid(a.nm + a.nm0 + 1 + a.R);
     DppoKtScope kt(KT_PACK_ALL, s);

@@ -141,7 +141,7 @@ __device__ inline float stream_act(float x) {
     else return fmaxf(x, 0.f);
 }
 
-template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, bool RES, int ACT>
+template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, bool RES, int ACT, int HEAD>
 __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
     SPHASE_START;
     using AT = typename P::AT;
@@ -317,7 +317,16 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
             const int col = (ntile0 + n) * 16 + ccol(lane);
             const float bv = bb[H + col];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) tB[crow(lane, r) * ldh + col] = P::cvt(stream_act<ACT>(acc[0][n][r] + bv));
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (HEAD == DPPO_HEAD_PLAIN) {
+                    // plain head (no l2 layer, no skip): the out-Dense's input is act(h2) itself, kept in the
+                    // skip's registers past the l2 product, whose result this instantiation drops
+                    h1[0][n][r] = stream_act<ACT>(acc[0][n][r] + bv);
+                    tB[crow(lane, r) * ldh + col] = P::cvt(h1[0][n][r]);
+                } else {
+                    tB[crow(lane, r) * ldh + col] = P::cvt(stream_act<ACT>(acc[0][n][r] + bv));
+                }
+            }
         }
         lds_sync();
         SPHASE(3);
@@ -330,7 +339,10 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
             const int col = (ntile0 + n) * 16 + ccol(lane);
             const float bv = bb[2 * H + col];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) tA[crow(lane, r) * ldh + col] = P::cvt(acc[0][n][r] + bv + h1[0][n][r]);
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (HEAD == DPPO_HEAD_PLAIN) tA[crow(lane, r) * ldh + col] = P::cvt(h1[0][n][r]);
+                else tA[crow(lane, r) * ldh + col] = P::cvt(acc[0][n][r] + bv + h1[0][n][r]);
+            }
         }
         lds_sync();
         SPHASE(4);
@@ -396,14 +408,14 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
 // dry (every launcher below): run the instantiation's host checks only and launch nothing. sample_impl
 // and dppo_sample_step ask first, so a geometry without an instantiation is refused before anything is
 // enqueued (deferred tables, the observation's copy)
-template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, bool RES, int ACT>
+template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, bool RES, int ACT, int HEAD>
 static int launch_sample_q(const SampleArgs& a, hipStream_t s, bool dry) {
     if (a.L.ks_h != ksh_for<P>(NT, SW) || a.L.ks_in != KSI || a.L.ks_h % SW != 0)
         return dppo_set_error(DPPO_EUNSUPPORTED, "sampler: hidden %d not supported at this precision", a.H);
     const size_t lds = stream_lds_total<P>(a, NO, SW);
     if (lds > 160 * 1024) return dppo_set_error(DPPO_EUNSUPPORTED, "sampler needs %zu B of LDS", lds);
     if (dry) return DPPO_OK;
-    auto k = sample_kernel<P, NT, NO, KSI, INJ, QD, SW, RK, RES, ACT>;
+    auto k = sample_kernel<P, NT, NO, KSI, INJ, QD, SW, RK, RES, ACT, HEAD>;
     { const int rc_ = dppo_func_lds((const void*)k, (size_t)lds); if (rc_) return rc_; }
     DppoKtScope kt(KT_SAMPLER, s);
     hipLaunchKernelGGL(k, dim3(dppo_cdiv(a.E, 16)), dim3(SW * 64), lds, s, a);
@@ -423,25 +435,25 @@ static char sampler_cfg() {
     return c;
 }
 
-template <class P, int NT16, int NO, int KSI, bool INJ, int ACT>   // NT16: n-tiles per wave of a 16-wave layout
+template <class P, int NT16, int NO, int KSI, bool INJ, int ACT, int HEAD>   // NT16: n-tiles per wave of a 16-wave layout
 static int launch_sample_k(const SampleArgs& a, hipStream_t s, bool dry) {
     constexpr StreamGeom g = stream_geom(P::KG == 32, NT16 * 256);
-    return launch_sample_q<P, NT16 * 16 / g.SW, NO, KSI, INJ, g.QD, g.SW, g.RK, g.RES, ACT>(a, s, dry);
+    return launch_sample_q<P, NT16 * 16 / g.SW, NO, KSI, INJ, g.QD, g.SW, g.RK, g.RES, ACT, HEAD>(a, s, dry);
 }
 
-template <class P, int NT, int NO, int KSI, int ACT>
+template <class P, int NT, int NO, int KSI, int ACT, int HEAD>
 static int launch_sample(const SampleArgs& a, hipStream_t s, bool dry) {
-    if (a.noise) return launch_sample_k<P, NT, NO, KSI, true, ACT>(a, s, dry);
-    return launch_sample_k<P, NT, NO, KSI, false, ACT>(a, s, dry);
+    if (a.noise) return launch_sample_k<P, NT, NO, KSI, true, ACT, HEAD>(a, s, dry);
+    return launch_sample_k<P, NT, NO, KSI, false, ACT, HEAD>(a, s, dry);
 }
 
-template <class P, int ACT>
+template <class P, int ACT, int HEAD>
 static int dispatch_sample(const SampleArgs& a, hipStream_t s, bool dry) {
     const int NT = a.H / (16 * 16);   // n-tiles per wave of the 16-wave layout
     const int NO = dppo_cdiv(a.XD, 16);
     const int KSI = a.L.ks_in;
 #define DPPO_SAMPLE_CASE(nt, no, ksi) \
-    if (NT == nt && NO == no && KSI == ksi) return launch_sample<P, nt, no, ksi, ACT>(a, s, dry);
+    if (NT == nt && NO == no && KSI == ksi) return launch_sample<P, nt, no, ksi, ACT, HEAD>(a, s, dry);
     if constexpr (P::KG == 32) {   // bf16: H = 512 (NT 2)
         DPPO_SAMPLE_CASE(2, 1, 2) DPPO_SAMPLE_CASE(2, 2, 2) DPPO_SAMPLE_CASE(2, 1, 4) DPPO_SAMPLE_CASE(2, 2, 4)
     } else {                       // fp32: H = 512 or 256
@@ -471,22 +483,34 @@ extern "C" int dppo_sampler_stream_bytes(const dppo_dims* d, int precision, int6
     return DPPO_OK;
 }
 
-template <int ACT>
+template <int ACT, int HEAD>
 static int dispatch_stream_a(const SampleArgs& a, int precision, hipStream_t s, bool dry) {
-    return precision == DPPO_BF16 ? dispatch_sample<PolicyBF16, ACT>(a, s, dry)
-         : precision == DPPO_F16  ? dispatch_sample<PolicyF16, ACT>(a, s, dry) : dispatch_sample<PolicyF32, ACT>(a, s, dry);
+    return precision == DPPO_BF16 ? dispatch_sample<PolicyBF16, ACT, HEAD>(a, s, dry)
+         : precision == DPPO_F16  ? dispatch_sample<PolicyF16, ACT, HEAD>(a, s, dry)
+                                  : dispatch_sample<PolicyF32, ACT, HEAD>(a, s, dry);
 }
-static int dispatch_stream(const SampleArgs& a, int precision, int act, hipStream_t s, bool dry) {
-    return act == DPPO_ACT_MISH ? dispatch_stream_a<DPPO_ACT_MISH>(a, precision, s, dry)
-                                : dispatch_stream_a<DPPO_ACT_RELU>(a, precision, s, dry);
+// The streaming kernel is instantiated per head: the plain head's two differences (which value rides the
+// skip's registers, what the l2 epilogue stores) are compile-time, so the residual instantiations are the
+// code they were before the plain head existed
+template <int HEAD>
+static int dispatch_stream_h(const SampleArgs& a, int precision, int act, hipStream_t s, bool dry) {
+    return act == DPPO_ACT_MISH ? dispatch_stream_a<DPPO_ACT_MISH, HEAD>(a, precision, s, dry)
+                                : dispatch_stream_a<DPPO_ACT_RELU, HEAD>(a, precision, s, dry);
+}
+static int dispatch_stream(const SampleArgs& a, int precision, int act, int head, hipStream_t s, bool dry) {
+    return head == DPPO_HEAD_PLAIN ? dispatch_stream_h<DPPO_HEAD_PLAIN>(a, precision, act, s, dry)
+                                   : dispatch_stream_h<DPPO_HEAD_RESIDUAL>(a, precision, act, s, dry);
 }
 
 // The activation of a sampler launch: its two images' (ReLU where none was recorded), which must agree:
 // one instantiation runs both actors' steps
-static int sample_act(const void* packed_base, const void* packed_ft, int* act) {
+static int sample_act(const void* packed_base, const void* packed_ft, int* act, int* head) {
     *act = dppo_actor_image_act(packed_ft);
     DPPO_CHECK(dppo_actor_image_act(packed_base) == *act,
                "dppo_sample: the base and the fine-tuned actor images carry different activations");
+    *head = dppo_actor_image_head(packed_ft);
+    DPPO_CHECK(dppo_actor_image_head(packed_base) == *head,
+               "dppo_sample: the base and the fine-tuned actor images carry different heads");
     return DPPO_OK;
 }
 
@@ -498,9 +522,9 @@ static void sample_geometry(const Dims& D, int precision, SampleArgs& a) {
 
 // Does a kernel take the shape (a: sample_geometry's fields and E)? The split kernel where its plan
 // does, else the streaming kernel's instantiation checks (dry); launches and enqueues nothing.
-static int sample_supported(const SampleArgs& a, int precision, int act, bool* split) {
+static int sample_supported(const SampleArgs& a, int precision, int act, int head, bool* split) {
     *split = sampler_cfg() == 'x' && split_plan(precision, a.H, a.XD, a.SD, a.E, a.K, a.KF).P > 0;
-    return *split ? DPPO_OK : dispatch_stream(a, precision, act, nullptr, true);
+    return *split ? DPPO_OK : dispatch_stream(a, precision, act, head, nullptr, true);
 }
 
 // The one launch path: `a` carries the caller's pointers and scalars (fields it does not use are
@@ -516,11 +540,11 @@ static int sample_impl(const dppo_dims* d, int precision, SampleArgs a, void* st
     DPPO_CHECK(a.packed_base && a.packed_ft && a.sched && (a.cond || a.cond_tagged) && a.actions,
                "dppo_sample: null pointer argument");
     sample_geometry(D, precision, a);
-    int act = DPPO_ACT_RELU;
-    rc = sample_act(a.packed_base, a.packed_ft, &act);
+    int act = DPPO_ACT_RELU, head = DPPO_HEAD_RESIDUAL;
+    rc = sample_act(a.packed_base, a.packed_ft, &act, &head);
     if (rc) return rc;
     bool split = false;
-    rc = sample_supported(a, precision, act, &split);
+    rc = sample_supported(a, precision, act, head, &split);
     if (rc) return rc;
     // tables an optimizer step deferred (DPPO_STEP_DEFER_SAMPLER_TABLES) are re-derived first, on this stream
     rc = dppo_refresh_sampler_tables(a.packed_ft, stream);
@@ -529,10 +553,20 @@ static int sample_impl(const dppo_dims* d, int precision, SampleArgs a, void* st
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (split) {
-        rc = launch_sample_split(a, precision, act, s);
+        // The split kernel reaches a plain head through the image alone (FOLD / RT_FOLD = rnd(W_out), ROUT
+        // zero). Its fp32 form takes the skip's operand from W_OUT, which a plain image needs as it is: those
+        // loads go to the image's T_OUT segment instead, all zero in a plain image and at least as large
+        // (nt_h ks_out_t >= nt_out ks_h fragments at XD <= 32)
+        SampleArgs as = a;
+        if (head == DPPO_HEAD_PLAIN && !dppo_prec_2b(precision)) {
+            DPPO_CHECK(packed_matrix_bytes(a.XD, a.H, a.L.KG) >= packed_matrix_bytes(a.H, a.XD, a.L.KG),
+                       "dppo_sample: plain head: T_OUT is smaller than the W_OUT loads it stands in for");
+            as.L.off[SEG_W_OUT] = as.L.off[SEG_T_OUT];
+        }
+        rc = launch_sample_split(as, precision, act, s);
         if (rc != DPPO_EUNSUPPORTED) return rc;
     }
-    return dispatch_stream(a, precision, act, s, false);
+    return dispatch_stream(a, precision, act, head, s, false);
 }
 
 // the three plan queries: dims checked and the split kernel's plan looked up once ({0, ...} under
@@ -627,11 +661,11 @@ extern "C" int dppo_sample_step(const dppo_dims* d, int precision, const void* p
         SampleArgs q = {};
         q.E = n_envs;
         sample_geometry(D, precision, q);
-        int act = DPPO_ACT_RELU;
-        rc = sample_act(packed_base, packed_ft, &act);
+        int act = DPPO_ACT_RELU, head = DPPO_HEAD_RESIDUAL;
+        rc = sample_act(packed_base, packed_ft, &act, &head);
         if (rc) return rc;
         bool split = false;
-        rc = sample_supported(q, precision, act, &split);
+        rc = sample_supported(q, precision, act, head, &split);
         if (rc) return rc;
         DPPO_HIP(hipMemcpyAsync(cond, cond_host, sizeof(float) * (size_t)n_envs * D.SD, hipMemcpyHostToDevice, s));
         rc = dppo_sample(d, precision, packed_base, packed_ft, sched, cond, n_envs, nullptr, nullptr, seed, call_id,

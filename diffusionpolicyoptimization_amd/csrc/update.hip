@@ -214,8 +214,11 @@ extern "C" int dppo_pack_all(const dppo_dims* d, int precision, const float* act
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
     DPPO_CHECK(!packed_actor == !actor_params && !packed_critic == !critic_params,
                "dppo_pack_all: a packed image needs its parameters");
+    const int old_head = packed_actor ? dppo_actor_image_head(packed_actor) : DPPO_HEAD_RESIDUAL;
+    if (packed_actor) dppo_actor_image_set_head(packed_actor, DPPO_HEAD_RESIDUAL);   // = dppo_pack_actor, before the pack
     rc = dppo_pack_models(D, precision, actor_params, packed_actor, critic_params, packed_critic, (hipStream_t)stream);
-    if (rc == DPPO_OK && packed_actor) dppo_actor_image_set_act(packed_actor, DPPO_ACT_RELU);   // = dppo_pack_actor
+    if (rc == DPPO_OK && packed_actor) dppo_actor_image_set_act(packed_actor, DPPO_ACT_RELU);
+    if (rc != DPPO_OK && packed_actor) dppo_actor_image_set_head(packed_actor, old_head);
     return rc;
 }
 
@@ -333,13 +336,19 @@ constexpr int PRETRAIN_MIN_CHUNK_ROWS = 64;
 static float* grad_at(float* g, size_t off) { return g ? g + off : nullptr; }
 // the actor's: PPO (the in-layer's bias and time-MLP gradients from the one-hot bucket rows) or
 // pretraining (those come from K bucket sums, seg_reduce + time_bwd)
-static void actor_dw_items(const Dims& D, const PpoWorkspace& ws, float* ga, bool pretrain, bool l2_def, DWItem (&it)[4]) {
+// plain (DPPO_HEAD_PLAIN image): u2^T dy IS W_out's gradient and goes straight to its region; the l2 region
+// keeps the zeros of the minibatch's zeroing (no factored form to defer)
+static void actor_dw_items(const Dims& D, const PpoWorkspace& ws, float* ga, bool pretrain, bool l2_def, DWItem (&it)[4],
+                           bool plain = false) {
     const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
     it[0] = pretrain ? DWItem{ws.a0T, D.IN, ws.dh1T, D.H, grad_at(ga, FA.in_w), EXTRA_NONE, nullptr}
                      : DWItem{ws.a0T, D.IN, ws.dh1T, D.H, grad_at(ga, FA.in_w), EXTRA_ONEHOT, ws.gseg, D.KF};
     it[1] = DWItem{ws.u1T, D.H, ws.dh2T, D.H, grad_at(ga, FA.l1_w), EXTRA_ONES, grad_at(ga, FA.l1_b)};
-    it[2] = DWItem{ws.u2T, D.H, ws.dyT, D.XD, l2_def ? grad_at(ga, FA.l2_w) : ws.pl2, EXTRA_NONE, nullptr};   // l2 through the out layer
-    it[3] = DWItem{ws.a0T, D.IN, ws.dyT, D.XD, ws.pa0, EXTRA_ONES, grad_at(ga, FA.out_b)};   // out through the fold (out_back)
+    it[2] = DWItem{ws.u2T, D.H, ws.dyT, D.XD, plain ? grad_at(ga, FA.out_w) : (l2_def ? grad_at(ga, FA.l2_w) : ws.pl2),
+                   EXTRA_NONE, nullptr};   // l2 through the out layer (plain: W_out itself)
+    // out through the fold (out_back). Plain: nothing reads pa0 (no out_back runs); the product is kept for its
+    // EXTRA_ONES column sum, db_out, at the cost of one unused [IN][XD] GEMM per minibatch
+    it[3] = DWItem{ws.a0T, D.IN, ws.dyT, D.XD, ws.pa0, EXTRA_ONES, grad_at(ga, FA.out_b)};
 }
 static void critic_dw_items(const Dims& D, const PpoWorkspace& ws, float* gc, DWItem (&it)[4]) {
     const FlatOffsets FC = make_flat_offsets(D.SD, D.HC, 1, 0);
@@ -445,7 +454,8 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     lh.clip_vloss = hp->clip_vloss_coef > 0.f && hp->old_values ? hp->clip_vloss_coef : 0.f;
     lh.old_values = lh.clip_vloss > 0.f ? hp->old_values : nullptr;
     // the actor's l2 gradient left factored in its own grads region (include/dppo.h)
-    const bool l2_def = (hp->flags & DPPO_PPO_L2_DEFERRED) != 0;
+    const bool plain = dppo_actor_image_head(m.packed_ft) == DPPO_HEAD_PLAIN;   // no l2: nothing to defer
+    const bool l2_def = (hp->flags & DPPO_PPO_L2_DEFERRED) != 0 && !plain;
 
     ActorArgs aa = {};
     aa.packed = (const uint8_t*)m.packed_ft;
@@ -524,7 +534,7 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     };
     auto actor_grads = [&]() -> int {
         DWItem items[4];
-        actor_dw_items(D, ws, ga, false, l2_def, items);
+        actor_dw_items(D, ws, ga, false, l2_def, items, plain);
         DppoKtScope kt(KT_DW_ACTOR, s);
         return launch_dw(DWTile::ACTOR, precision, items, 4, ws, 1.f / gscale, nullptr, PPO_MIN_CHUNK_ROWS, s);
     };
@@ -532,7 +542,7 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     // (Forking the time-MLP backward beside the dW (r05, profiles/r05y_tb_fork_ab.txt) and running it
     // inside a one-launch actor step (r06, profiles/r06de_actor_tail_ab.txt) were both measured slower.)
     auto actor_tail = [&]() -> int {
-        return launch_time_bwd(D, precision, ws, m.packed_ft, m.actor_params, ga, D.KF, D.TS, s, !l2_def);
+        return launch_time_bwd(D, precision, ws, m.packed_ft, m.actor_params, ga, D.KF, D.TS, s, !l2_def, plain);
     };
 
     if (part == MB_CRITIC) return critic_half(s);
@@ -661,7 +671,8 @@ extern "C" int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const 
 
     // the in-layer's bias and time-MLP gradients come from K bucket sums (seg_reduce + time_bwd)
     DWItem items[4];
-    actor_dw_items(D, ws, ga, true, false, items);
+    const bool plain = dppo_actor_image_head(packed_actor) == DPPO_HEAD_PLAIN;
+    actor_dw_items(D, ws, ga, true, false, items, plain);
     rc = launch_dw(DWTile::ACTOR, precision, items, 4, ws, 1.f / gscale, nullptr, PRETRAIN_MIN_CHUNK_ROWS, s);
     if (rc) return rc;
     const float inv = 1.f / gscale;
@@ -675,5 +686,5 @@ extern "C" int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const 
         hipLaunchKernelGGL(seg_reduce_kernel<float>, dim3(D.H), dim3(256), 0, s, (const float*)ws.dh1T, ws.seg, ws.ldm,
                            D.K, ws.gseg, D.H, inv);
     DPPO_HIP(hipGetLastError());
-    return launch_time_bwd(D, precision, ws, packed_actor, actor_params, ga, D.K, 1, s);
+    return launch_time_bwd(D, precision, ws, packed_actor, actor_params, ga, D.K, 1, s, true, plain);
 }

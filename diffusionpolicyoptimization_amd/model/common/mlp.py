@@ -47,8 +47,35 @@ class ResidualMLP:
 
 
 class MLP:
-    """Plain MLP (mlp.py:35-92) — only reachable from cfgs with residual_style: False, which the
-    kernels do not implement; kept as a loud error rather than a silent fallback."""
+    """Plain MLP (mlp.py:35-92), reached from cfgs with residual_style: False. The kernels implement the
+    two-hidden-layer shape of the reference's default mlp_dims, dims [in, h, h, out]:
+        h1 = in(x);  u1 = act(h1);  h2 = l1(u1);  a = act(h2);  y = out(a)
+    (the residual network with the l2 layer and the skip removed; include/dppo.h DPPO_HEAD_PLAIN). Every other
+    shape or option is a loud error rather than a silent fallback."""
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("non-residual MLP heads are not implemented by the MI355X kernels")
+    SHAPE = "[in, h, h, out] with out_activation_type='Identity' and no layernorm, dropout or append"
+
+    def __init__(self, dim_list, append_dim=0, append_layers=None, activation_type="Tanh", out_activation_type="Identity",
+                 use_layernorm=False, use_layernorm_final=False, dropout=0):
+        dim_list = list(dim_list)
+        if len(dim_list) != 4 or dim_list[1] != dim_list[2]:
+            raise NotImplementedError(f"MLP {dim_list}: the kernels implement the plain head {self.SHAPE}")
+        if use_layernorm or use_layernorm_final or dropout or append_dim or append_layers:
+            raise NotImplementedError(f"MLP layernorm / dropout / append: the kernels implement the plain head {self.SHAPE}")
+        if out_activation_type != "Identity":
+            raise NotImplementedError(f"MLP out_activation_type {out_activation_type!r}: the kernels implement {self.SHAPE}")
+        if activation_type not in SUPPORTED_ACTIVATIONS:
+            raise NotImplementedError(f"activation {activation_type} not implemented")
+        self.dim_list = dim_list
+        self.activation_type = activation_type
+
+    @property
+    def hidden(self):
+        return self.dim_list[1]
+
+    def init_params(self, rng, prefix=""):
+        """in, l1 and out only: a plain head has no l2 (its range of the flat layout stays zero)."""
+        i, h, o = self.dim_list[0], self.dim_list[1], self.dim_list[-1]
+        return {prefix + "in_w": glorot_uniform(rng, i, h), prefix + "in_b": np.zeros(h, np.float32),
+                prefix + "l1_w": glorot_uniform(rng, h, h), prefix + "l1_b": np.zeros(h, np.float32),
+                prefix + "out_w": glorot_uniform(rng, h, o), prefix + "out_b": np.zeros(o, np.float32)}

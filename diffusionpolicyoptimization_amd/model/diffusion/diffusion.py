@@ -81,7 +81,7 @@ class DiffusionModel:
                                       horizon_steps=self.horizon_steps, cond_steps=net.cond_dim // self.obs_dim,
                                       time_dim=net.time_dim, actor_hidden=net.hidden,
                                       denoising_steps=self.denoising_steps, ft_denoising_steps=1, time_stride=1,
-                                      activation=net.activation_type)
+                                      activation=net.activation_type, head=net.head)
         self.pre_spec = ops.actor_param_spec(self.pre_dims)
         path = self.network_path
         if path is not None and not os.path.exists(str(path)):
@@ -89,6 +89,7 @@ class DiffusionModel:
         if path is not None and str(path).endswith(".npz"):
             with np.load(str(path), allow_pickle=False) as f:
                 pref = "network." if any(k.startswith("network.") for k in f.files) else ""
+                ops.check_checkpoint_head(f.files, self.pre_spec, path, pref)
                 p = {n: np.asarray(f[pref + n], np.float32).reshape(s) for n, s in self.pre_spec}
         elif path is not None and str(path).endswith(".h5"):      # Keras-3 weights (util/keras_weights.py)
             p = keras_weights.load_actor(str(path), self.pre_spec)

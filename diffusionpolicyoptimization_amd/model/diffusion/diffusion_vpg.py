@@ -54,7 +54,7 @@ class VPGDiffusion(DiffusionModel):
                                   horizon_steps=self.horizon_steps, cond_steps=cond_steps, time_dim=actor.time_dim,
                                   actor_hidden=actor.hidden, critic_hidden=critic.hidden,
                                   denoising_steps=self.sampling_steps, ft_denoising_steps=self.ft_denoising_steps,
-                                  time_stride=self.time_stride, activation=actor.activation_type)
+                                  time_stride=self.time_stride, activation=actor.activation_type, head=actor.head)
         self.actor_spec = ops.actor_param_spec(self.dims)
         self.critic_spec = ops.critic_param_spec(self.dims)
         self.n_actor = ops.spec_count(self.actor_spec)
@@ -169,7 +169,9 @@ class VPGDiffusion(DiffusionModel):
         if path.endswith(".npz"):
             with np.load(path, allow_pickle=False) as f:
                 keys = [k for k in f.files]
-                pref = "actor." if any(k.startswith("actor.") for k in keys) else ""
+                # a fine-tune checkpoint's base actor, a pretrain checkpoint (DiffusionModel.save_network), or bare names
+                pref = next((p for p in ("actor.", "network.") if any(k.startswith(p) for k in keys)), "")
+                ops.check_checkpoint_head(keys, self.actor_spec, path, pref)
                 return {n: np.asarray(f[pref + n], np.float32).reshape(s) for n, s in self.actor_spec}
         if path.endswith(".h5"):          # Keras-3 weights of a DiffusionMLP (pretrain checkpoint)
             return keras_weights.load_actor(path, self.actor_spec)
@@ -226,6 +228,7 @@ class VPGDiffusion(DiffusionModel):
             return
         eta = None
         with np.load(path, allow_pickle=False) as f:
+            ops.check_checkpoint_head(f.files, self.actor_spec, path, "actor_ft.")
             for prefix, flat, spec in (("actor.", self.base_params, self.actor_spec),
                                        ("actor_ft.", self.actor_ft_params, self.actor_spec),
                                        ("critic.", self.critic_params, self.critic_spec)):

@@ -1,12 +1,13 @@
 """DiffusionMLP (reference model/diffusion/mlp_diffusion.py:12-90).
 
-input = concat[x.flat (Ta*Da), t_emb (time_dim), state.flat (To*Do)] -> ResidualMLP -> eps, with
+input = concat[x.flat (Ta*Da), t_emb (time_dim), state.flat (To*Do)] -> ResidualMLP (residual_style=True,
+mlp_dims [h, h, h]) or the plain MLP (residual_style=False, the reference's default, mlp_dims [h, h]) -> eps, with
 t_emb = Dense(2*time_dim, mish)(SinusoidalPosEmb(t)) -> Dense(time_dim). The network is evaluated
 only inside the fused HIP kernels (sampler / logprob / PPO update), so this class is the
 configuration + parameter container."""
 import numpy as np
 
-from ..common.mlp import ResidualMLP, glorot_uniform
+from ..common.mlp import MLP, ResidualMLP, glorot_uniform
 
 
 class DiffusionMLP:
@@ -14,8 +15,6 @@ class DiffusionMLP:
                  activation_type="Mish", out_activation_type="Identity", use_layernorm=False, residual_style=False):
         if cond_mlp_dims is not None:
             raise NotImplementedError("cond_mlp_dims (obs encoder) is not used by the gym fine-tune cfgs")
-        if not residual_style:
-            raise NotImplementedError("DiffusionMLP(residual_style=False) is not implemented on MI355X")
         if activation_type not in ("ReLU", "Mish"):
             raise NotImplementedError(f"activation_type {activation_type!r}: the actor kernels implement ReLU and Mish")
         self.action_dim, self.horizon_steps, self.cond_dim, self.time_dim = action_dim, horizon_steps, cond_dim, time_dim
@@ -25,8 +24,10 @@ class DiffusionMLP:
         self.residual_style = residual_style
         output_dim = action_dim * horizon_steps
         self.input_dim = time_dim + output_dim + cond_dim
-        self.mlp_mean = ResidualMLP([self.input_dim] + self.mlp_dims + [output_dim], activation_type=activation_type,
-                                    out_activation_type=out_activation_type, use_layernorm=use_layernorm)
+        model = ResidualMLP if residual_style else MLP
+        self.mlp_mean = model([self.input_dim] + self.mlp_dims + [output_dim], activation_type=activation_type,
+                              out_activation_type=out_activation_type, use_layernorm=use_layernorm)
+        self.head = "residual" if residual_style else "plain"   # ops.ModelDims.head
         self.hidden = self.mlp_mean.hidden
 
     def init_params(self, rng):

@@ -33,10 +33,16 @@ class ModelDims:
     # the actor's activation_type, "ReLU" or "Mish". Python-only: it is no field of dppo_dims; pack_actor
     # records it with the packed image (dppo_pack_actor_act) and every kernel launch follows the image
     activation: str = "ReLU"
+    # the actor's head, "residual" (ResidualMLP) or "plain" (MLP([in, h, h, out]), residual_style=False).
+    # Python-only like the activation: pack_actor records it with the image (dppo_pack_actor_head). The flat
+    # layout is the same; a plain actor leaves its l2 range unused and zero (actor_param_spec)
+    head: str = "residual"
 
     def __post_init__(self):
         if self.activation not in _lib.ACTIVATION:
             raise ValueError(f"activation must be one of {sorted(_lib.ACTIVATION)}, got {self.activation!r}")
+        if self.head not in _lib.HEAD:
+            raise ValueError(f"head must be one of {sorted(_lib.HEAD)}, got {self.head!r}")
 
     @property
     def xd(self):
@@ -56,12 +62,30 @@ class ModelDims:
                              self.time_stride)
 
 
+class ParamSpec(list):
+    """[(name, shape)] of the tensors a network HAS, each with its element offset in a flat layout of
+    `total` elements that may hold ranges no tensor uses (a plain-head actor: the residual layout without
+    l2). flatten_params leaves such ranges zero; unflatten_params skips them; spec_count is `total`."""
+
+    def __init__(self, items, offsets, total):
+        super().__init__(items)
+        self.offsets, self.total = dict(offsets), int(total)
+
+
 def actor_param_spec(d: ModelDims):
-    """Flat fp32 layout of include/dppo.h (Keras kernels [in,out])."""
+    """Flat fp32 layout of include/dppo.h (Keras kernels [in,out]). A plain-head actor (d.head == "plain")
+    lists the time MLP, in, l1 and out at the SAME offsets and total: its l2 range is unused and zero."""
     td, h, xd = d.time_dim, d.actor_hidden, d.xd
-    return [("time_w1", (td, 2 * td)), ("time_b1", (2 * td,)), ("time_w2", (2 * td, td)), ("time_b2", (td,)),
+    full = [("time_w1", (td, 2 * td)), ("time_b1", (2 * td,)), ("time_w2", (2 * td, td)), ("time_b2", (td,)),
             ("in_w", (d.actor_in, h)), ("in_b", (h,)), ("l1_w", (h, h)), ("l1_b", (h,)),
             ("l2_w", (h, h)), ("l2_b", (h,)), ("out_w", (h, xd)), ("out_b", (xd,))]
+    if d.head != "plain":
+        return full
+    offsets, o = {}, 0
+    for n, s in full:
+        offsets[n] = o
+        o += int(np.prod(s))
+    return ParamSpec([(n, s) for n, s in full if n not in ("l2_w", "l2_b")], offsets, o)
 
 
 def critic_param_spec(d: ModelDims):
@@ -70,7 +94,22 @@ def critic_param_spec(d: ModelDims):
             ("l2_w", (h, h)), ("l2_b", (h,)), ("out_w", (h, 1)), ("out_b", (1,))]
 
 
+def spec_ranges(spec):
+    """(name, shape, offset, count) of each tensor of a spec in its flat layout: consecutive for a list, a
+    ParamSpec's own offsets (which skip its unused ranges)."""
+    o = 0
+    for n, s in spec:
+        k = int(np.prod(s))
+        if isinstance(spec, ParamSpec):
+            o = spec.offsets[n]
+        yield n, s, o, k
+        o += k
+
+
 def spec_count(spec):
+    """Elements of the flat layout (a ParamSpec's total counts its unused ranges)."""
+    if isinstance(spec, ParamSpec):
+        return spec.total
     return int(sum(int(np.prod(s)) for _, s in spec))
 
 
@@ -99,17 +138,25 @@ def _workspace_bytes(d, prec, rows):
 
 
 def flatten_params(spec, params):
-    return np.concatenate([np.asarray(params[n], np.float32).reshape(-1) for n, _ in spec])
+    flat = np.zeros(spec_count(spec), np.float32)
+    for n, _, o, k in spec_ranges(spec):
+        flat[o:o + k] = np.asarray(params[n], np.float32).reshape(-1)
+    return flat
 
 
 def unflatten_params(spec, flat):
-    out, o = {}, 0
     flat = np.asarray(flat)
-    for n, s in spec:
-        k = int(np.prod(s))
-        out[n] = flat[o:o + k].reshape(s)
-        o += k
-    return out
+    return {n: flat[o:o + k].reshape(s) for n, s, o, k in spec_ranges(spec)}
+
+
+def check_checkpoint_head(names, spec, path, prefix=""):
+    """A checkpoint's actor tensors (the file's names under `prefix`) must be the spec's head: a residual file
+    (it has `prefix`l2_w) does not load into a plain actor, nor a plain file into a residual one. Another
+    network's l2_w in the same file (the critic's) does not count."""
+    has, wants = prefix + "l2_w" in set(names), any(n == "l2_w" for n, _ in spec)
+    if has != wants:
+        kind = lambda l2: "residual (with l2)" if l2 else "plain (no l2)"
+        raise ValueError(f"{path}: the checkpoint holds a {kind(has)} actor, the model is {kind(wants)}")
 
 
 def _check(t, shape, dtype, name):
@@ -166,8 +213,9 @@ def pack_all(d: ModelDims, precision, actor_params=None, packed_actor=None, crit
     _check(critic_params, (nc,), torch.float32, "critic params")
     _check(packed_critic, (cb,), torch.uint8, "packed critic")
     t = actor_params if actor_params is not None else critic_params
-    if actor_params is not None and d.activation != "ReLU":
-        # dppo_pack_all records ReLU for the actor image (= dppo_pack_actor): a Mish actor packs on its own
+    if actor_params is not None and (d.activation != "ReLU" or d.head != "residual"):
+        # dppo_pack_all records ReLU / RESIDUAL for the actor image (= dppo_pack_actor): a Mish or plain-head
+        # actor packs on its own
         pack_actor(d, actor_params, precision, out=packed_actor)
         if critic_params is not None:
             pack_critic(d, critic_params, precision, out=packed_critic)
@@ -386,16 +434,16 @@ class MappedDoubles:
 
 
 def pack_actor(d: ModelDims, params_flat, precision, out=None):
-    """The packed image of an actor; d.activation is recorded with it (dppo_pack_actor_act) and decides
-    which kernels every later launch on the image runs."""
+    """The packed image of an actor; d.activation and d.head are recorded with it (dppo_pack_actor_head) and
+    decide which kernels every later launch on the image runs."""
     p = _prec(precision)
     _check(params_flat, (_n_params(d)[0],), torch.float32, "actor params")
     if out is None:
         out = torch.empty(_packed_bytes(d, p)[0], dtype=torch.uint8, device=params_flat.device)
     else:
         _check(out, (_packed_bytes(d, p)[0],), torch.uint8, "packed actor")
-    _lib.call("dppo_pack_actor_act", ctypes.byref(_dims_c(d)), p, _lib.ACTIVATION[d.activation], ptr(params_flat),
-              ptr(out), stream_handle(params_flat.device))
+    _lib.call("dppo_pack_actor_head", ctypes.byref(_dims_c(d)), p, _lib.ACTIVATION[d.activation], _lib.HEAD[d.head],
+              ptr(params_flat), ptr(out), stream_handle(params_flat.device))
     return out
 
 

@@ -11,6 +11,12 @@ written twice. For the reference's classes that gives:
       and of network_path (diffusion_vpg.py:85-97);
   CriticObs (model/common/critic.py:33): Q1/... (same ResidualMLP names);
   PPODiffusion (agent/finetune/train_agent.py:127-133): actor/, actor_ft/, critic/.
+A plain-head DiffusionMLP (residual_style=False: mlp_mean is the reference's MLP, model/common/mlp.py:35-92,
+whose module_list holds one Sequential([Dense, activation]) per layer) is written by the same rule as
+      mlp_mean/module_list/{sequential, sequential_1, sequential_2}/layers/dense   (in, l1, out)
+and has no l2. This package round-trips its own files under that naming; the match with a file Keras wrote
+for the reference's MLP is UNPINNED (Keras cannot be installed here, and no such file was available). A file
+of one head does not load into a model of the other (the l2 variables are missing or unread).
 Reading is tolerant of the container names (any residual block / the Sequential's Dense layers in
 Keras's numbering) and checks every shape against the flat spec; what is missing is named in the
 error. Parity is pinned to this published layout, not to a file Keras wrote (TF/Keras cannot be
@@ -32,9 +38,19 @@ def _dense_paths(prefix):
             "l2": f"{prefix}residual_blocks/{BLOCK}/l2", "out": f"{prefix}output_layer"}
 
 
-def actor_paths(prefix=""):
+def _plain_paths(prefix):
+    """Keras-3 paths of the plain MLP([in, h, h, out]) under `prefix` (naming unpinned, module docstring)."""
+    seq = lambda i: f"{prefix}module_list/sequential{'_%d' % i if i else ''}/layers/dense"
+    return {"in": seq(0), "l1": seq(1), "out": seq(2)}
+
+
+def _is_plain(names):
+    return not any(n == "l2_w" for n in names)
+
+
+def actor_paths(prefix="", plain=False):
     """flat-spec name -> dataset path (ops.actor_param_spec names)."""
-    p = _dense_paths(prefix + "mlp_mean/")
+    p = (_plain_paths if plain else _dense_paths)(prefix + "mlp_mean/")
     te = prefix + "time_embedding/layers/"
     out = {"time_w1": te + "dense/vars/0", "time_b1": te + "dense/vars/1",
            "time_w2": te + "dense_1/vars/0", "time_b2": te + "dense_1/vars/1"}
@@ -136,9 +152,10 @@ def load_actor(path, spec, prefixes=("", "network/", "actor/", "actor_ft/")):
         raise ValueError(f"{path}: no DiffusionMLP (mlp_mean/...) found; datasets: "
                          + ", ".join(sorted(k for k in data if k != "__groups__"))[:2000])
     used = set()
-    got, missing = _resolve(data, actor_paths(p), used)
+    got, missing = _resolve(data, actor_paths(p, _is_plain(n for n, _ in spec)), used)
     if missing:
-        raise ValueError(f"{path}: missing DiffusionMLP variables: {missing}")
+        raise ValueError(f"{path}: missing DiffusionMLP variables (a plain-head file has no residual block, a "
+                         f"residual file no module_list): {missing}")
     _check_unused(path, data, used, (p + "mlp_mean/", p + "time_embedding/"), "DiffusionMLP")
     return _checked(got, spec, "actor", path)
 
@@ -158,8 +175,9 @@ def load_ppo_model(path, actor_spec, critic_spec):
         out["eta"] = {"logit": float(np.asarray(data[ETA_LOGIT]).reshape(-1)[0]), "m": float(opt[0]),
                       "v": float(opt[1]), "step": int(opt[2])}
         used.update(k for k in (ETA_LOGIT, ETA_OPT) if k in data)
-    for key, paths, spec in (("actor", actor_paths("actor/"), actor_spec),
-                             ("actor_ft", actor_paths("actor_ft/"), actor_spec),
+    plain = _is_plain(n for n, _ in actor_spec)
+    for key, paths, spec in (("actor", actor_paths("actor/", plain), actor_spec),
+                             ("actor_ft", actor_paths("actor_ft/", plain), actor_spec),
                              ("critic", critic_paths("critic/"), critic_spec)):
         got, missing = _resolve(data, paths, used)
         if missing:
@@ -169,10 +187,14 @@ def load_ppo_model(path, actor_spec, critic_spec):
     return out
 
 
-def _empty_groups(prefix, network):
+def _empty_groups(prefix, network, plain=False):
     """The (empty) `vars` groups Keras writes for every saveable without variables of its own."""
     g = [prefix + "vars"]
-    if network == "actor":
+    if network == "actor" and plain:
+        g += [prefix + "mlp_mean/vars", prefix + "time_embedding/vars",
+              prefix + "time_embedding/layers/sinusoidal_pos_emb/vars"]
+        g += [prefix + f"mlp_mean/module_list/sequential{'_%d' % i if i else ''}/vars" for i in range(3)]
+    elif network == "actor":
         g += [prefix + "mlp_mean/vars", prefix + f"mlp_mean/residual_blocks/{BLOCK}/vars",
               prefix + "time_embedding/vars", prefix + "time_embedding/layers/sinusoidal_pos_emb/vars"]
     else:
@@ -182,8 +204,9 @@ def _empty_groups(prefix, network):
 
 def save_actor(path, params):
     """A DiffusionMLP at the file root (agent/pretrain/train_agent.py:150-154 layout)."""
-    write_h5(path, {actor_paths("")[k]: np.asarray(v, np.float32) for k, v in params.items()},
-             groups=_empty_groups("", "actor"))
+    plain = _is_plain(params)
+    write_h5(path, {actor_paths("", plain)[k]: np.asarray(v, np.float32) for k, v in params.items()},
+             groups=_empty_groups("", "actor", plain))
 
 
 def save_ppo_model(path, actor, actor_ft, critic, eta=None):
@@ -193,11 +216,12 @@ def save_ppo_model(path, actor, actor_ft, critic, eta=None):
     if eta is not None:
         d[ETA_LOGIT] = np.array([eta["logit"]], np.float32)
         d[ETA_OPT] = np.array([eta["m"], eta["v"], eta["step"]], np.float64)
-    for prefix, params, paths in (("actor/", actor, actor_paths("actor/")),
-                                  ("actor_ft/", actor_ft, actor_paths("actor_ft/")),
+    plain = _is_plain(actor)
+    for prefix, params, paths in (("actor/", actor, actor_paths("actor/", plain)),
+                                  ("actor_ft/", actor_ft, actor_paths("actor_ft/", plain)),
                                   ("critic/", critic, critic_paths("critic/"))):
         for k, v in params.items():
             d[paths[k]] = np.asarray(v, np.float32)
-    groups = ["vars"] + _empty_groups("actor/", "actor") + _empty_groups("actor_ft/", "actor") + \
+    groups = ["vars"] + _empty_groups("actor/", "actor", plain) + _empty_groups("actor_ft/", "actor", plain) + \
         _empty_groups("critic/", "critic") + (["eta"] if eta is not None else [])
     write_h5(path, d, groups=groups)

@@ -22,6 +22,8 @@
  *               in_w[XD+TD+SD, H] in_b[H] l1_w[H,H] l1_b[H] l2_w[H,H] l2_b[H] out_w[H,XD] out_b[XD]
  *       critic: in_w[SD,HC] in_b[HC] l1_w[HC,HC] l1_b[HC] l2_w[HC,HC] l2_b[HC] out_w[HC,1] out_b[1]
  *     with XD = horizon*action_dim, SD = cond_steps*obs_dim, TD = time_dim.
+ *     A plain-head actor (DPPO_HEAD_PLAIN, dppo_pack_actor_head) keeps this layout with the l2_w / l2_b
+ *     range unused: zero on creation, its gradient written as zero, so it stays zero under AdamW.
  */
 #ifndef DPPO_H
 #define DPPO_H
@@ -165,6 +167,37 @@ DPPO_API int dppo_pack_critic(const dppo_dims* d, int precision, const float* pa
 enum { DPPO_ACT_RELU = 0, DPPO_ACT_MISH = 1 };
 DPPO_API int dppo_pack_actor_act(const dppo_dims* d, int precision, int activation, const float* params, void* packed,
                                  void* stream);
+/* The actor's head (DiffusionMLP residual_style, model/diffusion/mlp_diffusion.py:12-25), the image's second
+ * attribute (an addition within ABI 15). DPPO_HEAD_RESIDUAL is ResidualMLP (in-Dense, one two-Dense block with
+ * its skip, out-Dense). DPPO_HEAD_PLAIN is the reference's MLP([in, h, h, out]) of the default mlp_dims = [h, h]
+ * (model/common/mlp.py:35-92):
+ *     h1 = in(x);  u1 = act(h1);  h2 = l1(u1);  a = act(h2);  eps = W_out^T a + b_out
+ * i.e. the residual network with the l2 layer and the skip removed. dppo_pack_actor_head packs like
+ * dppo_pack_actor_act and records both attributes; dppo_pack_actor, dppo_pack_actor_act and dppo_pack_all
+ * record RESIDUAL, so re-packing a buffer through them resets the head. A head outside the enum is
+ * DPPO_EINVAL; so is a sampler launch whose base and fine-tuned images carry different heads, before anything
+ * is enqueued ("... carry different heads").
+ * Flat layout: unchanged. A plain actor uses the actor layout above with the l2_w / l2_b range UNUSED:
+ * dppo_dims, dppo_actor_param_count, every flat offset, the optimizer ranges and the data-parallel buckets
+ * stay as they are. The caller creates that range as zero; every gradient entry writes it as zero (also
+ * under DPPO_PPO_L2_DEFERRED, which has nothing to defer), and AdamW (Keras or torch mode) of a zero
+ * parameter with a zero gradient is exactly zero, so it stays zero. The pack copies the range into the W_L2 /
+ * T_L2 / B_L2 segments like any other, but no result on a plain image depends on those segments (the
+ * streaming sampler is instantiated per head and its plain form drops the l2 product).
+ * What the image holds, in the folded form the kernels compute (eps = W_out^T h1 + M^T a + B_OUT2; row tiles
+ * eps = a M + a0 M0 + b): FOLD / RT_FOLD = rnd(W_out) (hi = rnd(W_out), lo = 0: exact), RT_TFOLD its
+ * transpose, ROUT and RT_FOLD0 (the skip's operands) zero, B_OUT2 / RT_BOUT = b_out, T_OUT (the row tile's
+ * dh3 = dy W_out^T operand, the skip's share of dh1) zero; W_L2 / T_L2 / B_L2 are the packed range (no result uses it).
+ * The split sampler and the row tiles run a plain image unchanged (the fp32 split kernel takes its skip
+ * operand from the zero T_OUT segment instead of W_OUT); the streaming sampler feeds act(h2) through its
+ * skip path. In a minibatch dW_out = u2^T dy is written in place and no l2_back / out_back product runs;
+ * the fused optimizer step leaves T_OUT zero and the fold launch derives M = rnd(W_out) again.
+ * DPPO_STEP_L2_FROM_PL2 on a plain image is DPPO_EINVAL; dppo_materialize_l2 on one does nothing. The supported-geometry tables (sampler, update) and
+ * dppo_ppo_plan_act apply to a plain image line for line, with the same messages. The critic has no plain
+ * form. */
+enum { DPPO_HEAD_RESIDUAL = 0, DPPO_HEAD_PLAIN = 1 };
+DPPO_API int dppo_pack_actor_head(const dppo_dims* d, int precision, int activation, int head, const float* params,
+                                  void* packed, void* stream);
 
 /* ---- a9: diffusion-policy action sampler, VPGDiffusion.call (model/diffusion/diffusion_vpg.py:250-339) ----
  * All K DDPM steps for n_envs rows in ONE launch: DiffusionMLP forward on MFMA + fused DDPM

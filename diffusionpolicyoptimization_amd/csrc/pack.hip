@@ -768,7 +768,23 @@ int dppo_pack_models(const Dims& D, int precision, const float* actor_params, vo
                      void* const* zero_ptrs, const size_t* zero_bytes, int n_zero) {
     PackArgs a = {};
     int rc;
-    // byte ranges zeroed by the same launch (4-byte words, < 2^33 bytes each): jobs of their own
+    // byte ranges zeroed by the same launch (4-byte words, < 2^33 bytes each): jobs of their own. Both
+    // networks' images fill the job table on their own (13 + 11 jobs): ranges that would not fit beside
+    // the images are zeroed by a launch of their own first (the caller, staged_step, has already run
+    // AdamW, so refusing here would leave stepped parameters under stale images)
+    const int img_jobs = (actor_params && packed_actor ? (defer_sampler_tables ? 12 : 13) : 0) +
+                         (critic_params && packed_critic ? 11 : 0);   // add_mlp_jobs' counts
+    if (n_zero > 0 && n_zero + img_jobs > PACK_MAXJ) {
+        PackArgs z = {};
+        for (int r = 0; r < n_zero; ++r) {
+            if (z.njobs == PACK_MAXJ) return dppo_set_error(DPPO_EINVAL, "pack: too many jobs in one launch");
+            PackJob& J = z.j[z.njobs++];
+            J.kind = 2; J.dst = (uint8_t*)zero_ptrs[r]; J.n = (int)(zero_bytes[r] / 4); J.threads = (J.n + 3) / 4;
+        }
+        rc = launch_pack(z, precision, s);
+        if (rc) return rc;
+        n_zero = 0;
+    }
     for (int r = 0; r < n_zero; ++r) {
         if (a.njobs == PACK_MAXJ) return dppo_set_error(DPPO_EINVAL, "pack: too many jobs in one launch");
         PackJob& J = a.j[a.njobs++];

@@ -557,6 +557,21 @@ DPPO_API int dppo_materialize_l2(const dppo_dims* d, int precision, const void* 
  * DPPO_STEP_DEFER_SAMPLER_TABLES left them stale; a no-op otherwise (ABI 7). */
 DPPO_API int dppo_refresh_sampler_tables(const void* packed_actor, void* stream);
 
+/* Supported geometry of the optimizer step (dppo_optimizer_step, _ex and _clip, every form: staged,
+ * DPPO_STEP_FUSED_PACK, DPPO_STEP_CLEAR_GRADS, DPPO_STEP_L2_FROM_PL2, the clip scales). The step kernels have
+ * no per-geometry instantiations (the tile step takes each tensor's rows, columns and k-steps as arguments),
+ * so the step runs wherever the dimension check and the pack of the images accept the model: hidden widths
+ * 128/256/384/512, horizon_steps*action_dim <= 32, cond_steps*obs_dim <= 64, any input width, and for an
+ * actor image time_dim <= 32 with time_dim a multiple of 4 (the fold that follows every actor pack wants
+ * W_in 16-B aligned in the flat layout). That is wider than the row tiles' table above: an actor the update
+ * entries refuse (actor_hidden 256 or fewer than 33 inputs in fp32) still steps and packs.
+ *   geometry (tests/test_optimizer_step_gpu.py)      fp32   bf16   fp16
+ *   hopper (XD 12, 39 inputs), walker (XD 24, 57)    runs   runs   runs
+ *   horizon 8 x action 4 (XD 32)                     runs   runs   runs
+ *   time_dim 32, actor_hidden 256                    runs   runs   runs
+ *   cond_steps 2 walker (74 inputs), obs 3 action 1  runs   runs   runs
+ * A staged step over [actor | critic] with both images and clear ranges zeroes the ranges in a launch of
+ * its own (the two images fill the pack launch's job table). */
 DPPO_API int dppo_optimizer_step(const dppo_dims* d, int precision, float* params, const float* grads, float* m,
                         float* v, int64_t n, int64_t step, float lr, float weight_decay, float beta1,
                         float beta2, float eps, int mode, const float* actor_params, void* packed_actor,

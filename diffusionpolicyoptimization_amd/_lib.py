@@ -65,6 +65,8 @@ _SIGNATURES = {
     "dppo_critic_packed_bytes": (_SZ, [_DIMS, _I]),
     "dppo_pack_actor": (_I, [_DIMS, _I, _P, _P, _P]),
     "dppo_pack_critic": (_I, [_DIMS, _I, _P, _P, _P]),
+    "dppo_pack_critic_head": (_I, [_DIMS, _I, _I, _P, _P, _P]),
+    "dppo_forget_image": (_I, [_P]),
     "dppo_pack_actor_act": (_I, [_DIMS, _I, _I, _P, _P, _P]),
     "dppo_pack_actor_head": (_I, [_DIMS, _I, _I, _I, _P, _P, _P]),
     "dppo_sample": (_I, [_DIMS, _I, _P, _P, _P, _P, _I, _P, _P, _U64, _U64, _I, _I, _F, _F, _F, _P, _P, _P]),

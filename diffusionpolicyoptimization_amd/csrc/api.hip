@@ -87,13 +87,21 @@ extern "C" int dppo_pack_actor_act(const dppo_dims* d, int precision, int activa
 extern "C" int dppo_pack_actor(const dppo_dims* d, int precision, const float* params, void* packed, void* stream) {
     return dppo_pack_actor_act(d, precision, DPPO_ACT_RELU, params, packed, stream);
 }
-extern "C" int dppo_pack_critic(const dppo_dims* d, int precision, const float* params, void* packed, void* stream) {
+extern "C" int dppo_pack_critic_head(const dppo_dims* d, int precision, int head, const float* params, void* packed,
+                                     void* stream) {
     Dims D;
     int rc = dppo_check_dims(d, &D);
     if (rc) return rc;
     DPPO_CHECK(params && packed, "dppo_pack_critic: null pointer");
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
-    return dppo_pack_mlp(D.SD, D.HC, 1, 0, precision, params, packed, (hipStream_t)stream);
+    DPPO_CHECK(dppo_head_ok(head), "dppo_pack_critic_head: bad head %d (DPPO_HEAD_RESIDUAL or DPPO_HEAD_PLAIN)", head);
+    rc = dppo_pack_mlp(D.SD, D.HC, 1, 0, precision, params, packed, (hipStream_t)stream);
+    if (rc) return rc;   // refused: nothing was written, the image keeps its head
+    dppo_critic_image_set_head(packed, head);   // the bytes are the same for both heads; the launches follow this
+    return DPPO_OK;
+}
+extern "C" int dppo_pack_critic(const dppo_dims* d, int precision, const float* params, void* packed, void* stream) {
+    return dppo_pack_critic_head(d, precision, DPPO_HEAD_RESIDUAL, params, packed, stream);
 }
 
 // ---- kernel timer: (start, end) event pairs per launch of a timed kernel, summed on read ----

@@ -529,15 +529,18 @@ int launch_time_bwd(const Dims& D, int precision, const PpoWorkspace& ws, const 
     return DPPO_OK;
 }
 
-// the critic's l2 weight gradient from cpl2 (N = 1)
+// the critic's l2 weight gradient from cpl2 (N = 1). plain: no row group forms the product (the dW wrote l2's
+// gradient; adding the factored one would count it twice), the launch only zeroes the sample counts, and
+// without counts (dedup off) there is nothing to launch
 int launch_critic_l2_back(const Dims& D, int precision, const PpoWorkspace& ws, const void* packed_critic, float* gc,
-                          uint32_t* zcnt, hipStream_t s) {
+                          uint32_t* zcnt, hipStream_t s, bool plain) {
+    if (plain && !zcnt) return DPPO_OK;
     const FlatOffsets FC = make_flat_offsets(D.SD, D.HC, 1, 0);
     const MlpLayout L = make_mlp_layout(D.SD, D.HC, 1, 0, precision);
     L2Back l2b = {ws.cpl2, gc + FC.out_b, (const uint8_t*)packed_critic + L.off[SEG_W_OUT], gc + FC.l2_w, gc + FC.l2_b,
                   D.HC, 1, precision, zcnt, ws.crow_n, ws.crow_cnt};
     DppoKtScope kt(KT_L2_BACK, s);
-    launch_l2_back(precision, (unsigned)dppo_cdiv(D.HC, L2B_ROWS), s, l2b, dppo_cdiv(D.HC, L2B_ROWS), OutBack{}, 0);
+    launch_l2_back(precision, (unsigned)dppo_cdiv(D.HC, L2B_ROWS), s, l2b, plain ? 0 : dppo_cdiv(D.HC, L2B_ROWS), OutBack{}, 0);
     DPPO_HIP(hipGetLastError());
     return DPPO_OK;
 }

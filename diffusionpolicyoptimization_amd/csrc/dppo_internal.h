@@ -54,6 +54,11 @@ inline bool dppo_act_ok(int a) { return a == DPPO_ACT_RELU || a == DPPO_ACT_MISH
 int dppo_actor_image_head(const void* packed);
 void dppo_actor_image_set_head(const void* packed, int head);
 inline bool dppo_head_ok(int h) { return h == DPPO_HEAD_RESIDUAL || h == DPPO_HEAD_PLAIN; }
+// the head of the critic image at `packed` (dppo_pack_critic_head), in the same table: RESIDUAL for an unlisted
+// address. The image's bytes do not depend on it; the row tile, the dW problem list and the critic's last
+// launch do (rowtile.hip, update.hip)
+int dppo_critic_image_head(const void* packed);
+void dppo_critic_image_set_head(const void* packed, int head);
 // device address of mapped pinned host memory (dppo_host_alloc), cached; null if not mapped (host_staging.hip)
 void* mapped_ptr(const void* host);
 

@@ -11,7 +11,8 @@ struct PpoWorkspace {
     // actor (no dh3 image: l2's weight gradient is formed through the out layer, see pl2; no h3 image:
     // the folded row tile never forms h3, see pa0)
     void *a0T, *u1T, *u2T, *dyT, *dh2T, *dh1T;
-    // critic
+    // critic (a DPPO_HEAD_PLAIN critic image: ch3T holds u3 = mish(h3), the out-Dense's operand, and the tile
+    // also writes cdh3T, see below)
     void *csT, *cu1T, *cu2T, *ch3T, *cdvT, *cdh2T, *cdh1T;
     int8_t* seg;      // [ldm] t of each row (bucket id for the one-hot bias/temb sums), -1 invalid
     // l2's weight gradient through the linear out layer: dh3 = dy W_out^T, so
@@ -34,6 +35,10 @@ struct PpoWorkspace {
     // the multiplicities stay in the per-stream count scratch, crit_rows_kernel)
     int* crow_n;
     int* crow_cnt;
+    // plain critic only: dh3 [HC][ldm], l2's weight gradient is the true product cu2T^T cdh3T there (no factored
+    // form: the out layer reads mish(h3)). Appended last, so every other offset is what it was; the workspace is
+    // sized before an image is known, so every caller's grows by this image (HC ldm operand elements)
+    void* cdh3T;
     size_t total;
 };
 
@@ -62,6 +67,7 @@ inline PpoWorkspace make_ppo_workspace(const Dims& D, int precision, int rows, u
     w.stats = base ? (double*)(base + o) : nullptr; o += 8 * 4;
     w.crow_cnt = base ? (int*)(base + o) : nullptr; o = dppo_align256(o + 4);
     w.crow_n = base ? (int*)(base + o) : nullptr; o = dppo_align256(o + 4 * w.ldm);
+    w.cdh3T = take(D.HC);
     w.total = o;
     return w;
 }

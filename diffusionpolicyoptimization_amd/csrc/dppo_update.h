@@ -42,9 +42,10 @@ int launch_time_bwd(const Dims& D, int precision, const PpoWorkspace& ws, const 
 // over nb buckets would not fit a CU's 160 KiB; callers ask before their first launch
 int time_bwd_check(const Dims& D, int nb);
 // the critic's l2 weight gradient from ws.cpl2 (N = 1); with zcnt, the launch also zeroes the
-// minibatch's sample counts zcnt[ws.crow_n[r]], r < *ws.crow_cnt
+// minibatch's sample counts zcnt[ws.crow_n[r]], r < *ws.crow_cnt. plain (a DPPO_HEAD_PLAIN critic image, whose
+// l2 gradient the dW formed): the same launch without the product, the zeroing alone
 int launch_critic_l2_back(const Dims& D, int precision, const PpoWorkspace& ws, const void* packed_critic, float* gc,
-                          uint32_t* zcnt, hipStream_t s);
+                          uint32_t* zcnt, hipStream_t s, bool plain = false);
 
 // ---- update.hip ---------------------------------------------------------------------------------
 // zero up to 4 byte ranges (4-B aligned, sizes multiples of 4) in one launch of `blocks` workgroups

@@ -658,21 +658,22 @@ int mark_stale(const Dims& D, int precision, const float* params, const void* pa
 }  // namespace
 
 // The attributes of an actor image (include/dppo.h, dppo_pack_actor_act / dppo_pack_actor_head): its
-// activation and its head. Only images with a non-default attribute are listed (ReLU / RESIDUAL, the
-// defaults of an unlisted address, erase the entry), keyed by the image's address like g_stale.
+// activation and its head, and of a critic image (dppo_pack_critic_head): its head, chead. Only images with a
+// non-default attribute are listed (ReLU / RESIDUAL, the defaults of an unlisted address, erase the entry),
+// keyed by the image's address like g_stale.
 namespace {
-struct ImageAttr { const void* packed; int act, head; };
+struct ImageAttr { const void* packed; int act, head, chead; };
 std::mutex g_attr_mu;
 std::vector<ImageAttr> g_attr;
 ImageAttr image_attr(const void* packed) {
     std::lock_guard<std::mutex> lk(g_attr_mu);
     for (const ImageAttr& e : g_attr)
         if (e.packed == packed) return e;
-    return ImageAttr{packed, DPPO_ACT_RELU, DPPO_HEAD_RESIDUAL};
+    return ImageAttr{packed, DPPO_ACT_RELU, DPPO_HEAD_RESIDUAL, DPPO_HEAD_RESIDUAL};
 }
 void set_image_attr(const ImageAttr& a) {
     std::lock_guard<std::mutex> lk(g_attr_mu);
-    const bool dflt = a.act == DPPO_ACT_RELU && a.head == DPPO_HEAD_RESIDUAL;
+    const bool dflt = a.act == DPPO_ACT_RELU && a.head == DPPO_HEAD_RESIDUAL && a.chead == DPPO_HEAD_RESIDUAL;
     for (size_t i = 0; i < g_attr.size(); ++i)
         if (g_attr[i].packed == a.packed) {
             if (dflt) { g_attr[i] = g_attr.back(); g_attr.pop_back(); }
@@ -692,6 +693,20 @@ void dppo_actor_image_set_act(const void* packed, int activation) {
 void dppo_actor_image_set_head(const void* packed, int head) {
     ImageAttr a = image_attr(packed);
     a.head = head;
+    set_image_attr(a);
+}
+// the image's memory is being released: its address reads as never packed from here on (defaults, no
+// pending table refresh), whatever is allocated there next
+extern "C" int dppo_forget_image(const void* packed) {
+    if (!packed) return DPPO_OK;
+    set_image_attr(ImageAttr{packed, DPPO_ACT_RELU, DPPO_HEAD_RESIDUAL, DPPO_HEAD_RESIDUAL});
+    clear_stale(packed);
+    return DPPO_OK;
+}
+int dppo_critic_image_head(const void* packed) { return image_attr(packed).chead; }
+void dppo_critic_image_set_head(const void* packed, int head) {
+    ImageAttr a = image_attr(packed);
+    a.chead = head;
     set_image_attr(a);
 }
 

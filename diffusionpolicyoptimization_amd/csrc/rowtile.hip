@@ -578,7 +578,12 @@ struct CriticSmem {
     }
 };
 
-template <class P, int MT, int NT, bool TRAIN, int WAVES>
+// HEAD (DPPO_HEAD_*, the image's attribute): RESIDUAL is h3 = l2(u2) + h1, V = out(h3); PLAIN is the reference's
+// MLP([SD, HC, HC, HC, 1]): h3 = l2(u2), u3 = mish(h3), V = out(u3). The PLAIN branches are `if constexpr`
+// only, so the RESIDUAL instantiations are the code they were. A PLAIN TRAIN tile carries H3 to its backward
+// beside H1 and H2 (4 MT NT more registers), writes u3 where the residual tile writes h3 (ch3T, the out-Dense
+// gradient's operand) and a dh3 image (cdh3T): l2's weight gradient is a true product there
+template <class P, int MT, int NT, bool TRAIN, int WAVES, int HEAD>
 __device__ __forceinline__ void critic_rowtile_body(const CriticArgs& a) {
     using AT = typename P::AT;
     constexpr int THREADS = 64 * WAVES;
@@ -651,7 +656,10 @@ __device__ __forceinline__ void critic_rowtile_body(const CriticArgs& a) {
     const int ntile0 = wave * NT;
     const __amdgpu_buffer_rsrc_t rs = packed_rsrc(a.packed);
     auto W = [&](int seg) { return wsrc(rs, L.off[seg]); };
+    constexpr bool plain = HEAD == DPPO_HEAD_PLAIN;
     f32x4 H1[MT][NT], H2[MT][NT], acc[MT][NT];
+    [[maybe_unused]] f32x4 H3[MT][NT];   // PLAIN only: L3's accumulator, kept for B4 (RESIDUAL accumulates into acc)
+    f32x4 (&h3)[MT][NT] = *[&] { if constexpr (plain) return &H3; else return &acc; }();
     WRing<NT> R;
     ring_prime(R, W(SEG_W_IN), KSI, ntile0, lane);
     ORing<NOK, 1> ob;
@@ -680,20 +688,23 @@ __device__ __forceinline__ void critic_rowtile_body(const CriticArgs& a) {
     store_acc_lds<P, MT, NT>(tB, ldh, ntile0, lane, acc);
     if constexpr (train) store_accT<P, MT, NT>(wsr, ws_off(a.ws, a.ws.cu2T), ldm32, ntile0, grow32, lane, acc);
     lds_sync();
-    // L3: h3 = mish(h2) W_l2 + b + h1
-    gemm_stream<P, MT, NT, KSH>(tB, ldh, W(SEG_W_L2), ntile0, acc, lane, R,
+    // L3: h3 = mish(h2) W_l2 + b + h1 (PLAIN: no + h1, and the out-Dense operand is u3 = mish(h3))
+    gemm_stream<P, MT, NT, KSH>(tB, ldh, W(SEG_W_L2), ntile0, h3, lane, R,
                                 train ? NextLayer{W(SEG_T_OUT), KSO, ntile0} : NextLayer{W(SEG_W_L2), KSH, ntile0});
-    add_bias(acc, bias + 2 * HC, ntile0, lane);
+    add_bias(h3, bias + 2 * HC, ntile0, lane);
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[m][n][r] += H1[m][n][r];
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (plain) acc[m][n][r] = mishf(H3[m][n][r]);
+                else acc[m][n][r] += H1[m][n][r];
+            }
     store_acc_lds<P, MT, NT>(tA, ldh, ntile0, lane, acc);
     if constexpr (train) store_accT<P, MT, NT>(wsr, ws_off(a.ws, a.ws.ch3T), ldm32, ntile0, grow32, lane, acc);
     lds_sync();
-    // L4: V = h3 W_out + b
+    // L4: V = h3 W_out + b (PLAIN: u3)
     {
         f32x4 po[MT][1];
         gemm_narrow_pre<P, MT, NOK, 1, WAVES>(tA, ldh, ob, po, wave, lane);
@@ -739,8 +750,18 @@ __device__ __forceinline__ void critic_rowtile_body(const CriticArgs& a) {
     if constexpr (!train) return;
     lds_sync();
     // B4: dh3 = dV W_out^T (kept only in tB, re-read by B2; no image, as the actor's)
+    // PLAIN: dh3 = (dV W_out^T) * mish'(h3), to tB and to the cdh3T image (l2's dW operand)
     gemm_stream<P, MT, NT, KSO>(a0, lda0, W(SEG_T_OUT), ntile0, acc, lane, R, NextLayer{W(SEG_T_L2), KSH, ntile0});
+    if constexpr (plain) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int n = 0; n < NT; ++n)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[m][n][r] *= mish_gradf(H3[m][n][r]);
+    }
     store_acc_lds<P, MT, NT>(tB, ldh, ntile0, lane, acc);
+    if constexpr (plain) store_accT<P, MT, NT>(wsr, ws_off(a.ws, a.ws.cdh3T), ldm32, ntile0, grow32, lane, acc);
     lds_sync();
     // B3: dh2 = (dh3 W_l2^T) * mish'(h2)
     gemm_stream<P, MT, NT, KSH>(tB, ldh, W(SEG_T_L2), ntile0, acc, lane, R, NextLayer{W(SEG_T_L1), KSH, ntile0});
@@ -753,7 +774,7 @@ __device__ __forceinline__ void critic_rowtile_body(const CriticArgs& a) {
     store_acc_lds<P, MT, NT>(tA, ldh, ntile0, lane, acc);
     store_accT<P, MT, NT>(wsr, ws_off(a.ws, a.ws.cdh2T), ldm32, ntile0, grow32, lane, acc);
     lds_sync();
-    // B2: dh1 = dh3 + (dh2 W_l1^T) * mish'(h1)
+    // B2: dh1 = dh3 + (dh2 W_l1^T) * mish'(h1) (PLAIN: no dh3 term, tB is not re-read)
     gemm_stream<P, MT, NT, KSH>(tA, ldh, W(SEG_T_L1), ntile0, acc, lane, R, NextLayer{W(SEG_T_L1), KSH, ntile0});
 #pragma unroll
     for (int m = 0; m < MT; ++m)
@@ -761,8 +782,12 @@ __device__ __forceinline__ void critic_rowtile_body(const CriticArgs& a) {
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float dh3 = P::tof(tB[(m * 16 + crow(lane, r)) * ldh + (ntile0 + n) * 16 + ccol(lane)]);
-                acc[m][n][r] = dh3 + acc[m][n][r] * mish_gradf(H1[m][n][r]);
+                if constexpr (plain) {
+                    acc[m][n][r] *= mish_gradf(H1[m][n][r]);
+                } else {
+                    const float dh3 = P::tof(tB[(m * 16 + crow(lane, r)) * ldh + (ntile0 + n) * 16 + ccol(lane)]);
+                    acc[m][n][r] = dh3 + acc[m][n][r] * mish_gradf(H1[m][n][r]);
+                }
             }
     store_accT<P, MT, NT>(wsr, ws_off(a.ws, a.ws.cdh1T), ldm32, ntile0, grow32, lane, acc);
 }
@@ -777,13 +802,13 @@ template <class P, int MT, int NT, int NO, int KSI, bool TRAIN, int WAVES, int A
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4))) void actor_rowtile_kernel_o4(ActorArgs a) {
     actor_rowtile_body<P, MT, NT, NO, KSI, TRAIN, WAVES, ACT>(a);
 }
-template <class P, int MT, int NT, bool TRAIN, int WAVES>
+template <class P, int MT, int NT, bool TRAIN, int WAVES, int HEAD>
 __global__ __launch_bounds__(64 * WAVES) void critic_rowtile_kernel(CriticArgs a) {
-    critic_rowtile_body<P, MT, NT, TRAIN, WAVES>(a);
+    critic_rowtile_body<P, MT, NT, TRAIN, WAVES, HEAD>(a);
 }
-template <class P, int MT, int NT, bool TRAIN, int WAVES>
+template <class P, int MT, int NT, bool TRAIN, int WAVES, int HEAD>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4))) void critic_rowtile_kernel_o4(CriticArgs a) {
-    critic_rowtile_body<P, MT, NT, TRAIN, WAVES>(a);
+    critic_rowtile_body<P, MT, NT, TRAIN, WAVES, HEAD>(a);
 }
 
 // Row-tile shapes: actor 64 rows on 16 waves (2-byte operands, H = 512, XD <= 16, at least one
@@ -917,7 +942,7 @@ int launch_actor_rowtile(const ActorArgs& a, int precision, hipStream_t s, bool 
     return dispatch_actor<PolicyF32, 2, 16>(a, s, dry);
 }
 
-template <class P, int MT, int NT, bool TRAIN, int WAVES, bool O4>
+template <class P, int MT, int NT, bool TRAIN, int WAVES, bool O4, int HEAD>
 static int launch_critic_t(const CriticArgs& a, hipStream_t s, bool dry) {
     if (a.L.ks_in != 2 || a.L.ks_h != ksh_for<P>(NT, WAVES) || a.L.ks_out_t != 2 || a.L.ks_h != WAVES * nok_for<P>(NT))
         return dppo_set_error(DPPO_EUNSUPPORTED, "critic row tile: layout does not match the instantiation");
@@ -926,7 +951,7 @@ static int launch_critic_t(const CriticArgs& a, hipStream_t s, bool dry) {
     if ((size_t)4 * WAVES * 16 * MT * 16 > sizeof(typename P::AT) * 16 * MT * (a.HC + lds_pad_elems<P>()))
         return dppo_set_error(DPPO_EUNSUPPORTED, "critic: partial buffer does not fit");
     if (dry) return DPPO_OK;
-    auto k = O4 ? critic_rowtile_kernel_o4<P, MT, NT, TRAIN, WAVES> : critic_rowtile_kernel<P, MT, NT, TRAIN, WAVES>;
+    auto k = O4 ? critic_rowtile_kernel_o4<P, MT, NT, TRAIN, WAVES, HEAD> : critic_rowtile_kernel<P, MT, NT, TRAIN, WAVES, HEAD>;
     { const int rc_ = dppo_func_lds((const void*)k, (size_t)S.total); if (rc_) return rc_; }
     // TRAIN mode covers every row of the 64-padded feature-major images (padding rows get
     // finite activations and zero gradients), so the dW kernel never reads unwritten memory
@@ -939,12 +964,19 @@ static int launch_critic_t(const CriticArgs& a, hipStream_t s, bool dry) {
     return DPPO_OK;
 }
 
-template <class P, int MT, int WAVES, bool O4>
-static int dispatch_critic(const CriticArgs& a, hipStream_t s, bool dry) {
+template <class P, int MT, int WAVES, bool O4, int HEAD>
+static int dispatch_critic_h(const CriticArgs& a, hipStream_t s, bool dry) {
     const int NT = a.HC / (16 * WAVES);
     const bool tr = a.mode == ROWS_TRAIN;
-    if (NT == 2) return tr ? launch_critic_t<P, MT, 2, true, WAVES, O4>(a, s, dry) : launch_critic_t<P, MT, 2, false, WAVES, O4>(a, s, dry);
+    if (NT == 2) return tr ? launch_critic_t<P, MT, 2, true, WAVES, O4, HEAD>(a, s, dry)
+                           : launch_critic_t<P, MT, 2, false, WAVES, O4, HEAD>(a, s, dry);
     return dppo_set_error(DPPO_EUNSUPPORTED, "critic: hidden %d not instantiated", a.HC);
+}
+// the image's head (dppo_pack_critic_head) picks the instantiation, in the dry check too
+template <class P, int MT, int WAVES, bool O4>
+static int dispatch_critic(const CriticArgs& a, hipStream_t s, bool dry) {
+    return dppo_critic_image_head(a.packed) == DPPO_HEAD_PLAIN ? dispatch_critic_h<P, MT, WAVES, O4, DPPO_HEAD_PLAIN>(a, s, dry)
+                                                               : dispatch_critic_h<P, MT, WAVES, O4, DPPO_HEAD_RESIDUAL>(a, s, dry);
 }
 
 // 16-row MFMA tiles per critic row tile: 2 (4, a 64-row tile, measured slower at N = 1 and equal on

@@ -218,6 +218,7 @@ extern "C" int dppo_pack_all(const dppo_dims* d, int precision, const float* act
     if (packed_actor) dppo_actor_image_set_head(packed_actor, DPPO_HEAD_RESIDUAL);   // = dppo_pack_actor, before the pack
     rc = dppo_pack_models(D, precision, actor_params, packed_actor, critic_params, packed_critic, (hipStream_t)stream);
     if (rc == DPPO_OK && packed_actor) dppo_actor_image_set_act(packed_actor, DPPO_ACT_RELU);
+    if (rc == DPPO_OK && packed_critic) dppo_critic_image_set_head(packed_critic, DPPO_HEAD_RESIDUAL);   // = dppo_pack_critic
     if (rc != DPPO_OK && packed_actor) dppo_actor_image_set_head(packed_actor, old_head);
     return rc;
 }
@@ -350,11 +351,15 @@ static void actor_dw_items(const Dims& D, const PpoWorkspace& ws, float* ga, boo
     // EXTRA_ONES column sum, db_out, at the cost of one unused [IN][XD] GEMM per minibatch
     it[3] = DWItem{ws.a0T, D.IN, ws.dyT, D.XD, ws.pa0, EXTRA_ONES, grad_at(ga, FA.out_b)};
 }
-static void critic_dw_items(const Dims& D, const PpoWorkspace& ws, float* gc, DWItem (&it)[4]) {
+// the critic's. plain (DPPO_HEAD_PLAIN image): problem 2 is the true product cu2T^T cdh3T -> l2_w with its column
+// sums -> l2_b, an HC x HC problem like problem 1 (cpl2 is not written: the out layer reads mish(h3), so there is
+// no factored form), and ch3T holds u3
+static void critic_dw_items(const Dims& D, const PpoWorkspace& ws, float* gc, DWItem (&it)[4], bool plain = false) {
     const FlatOffsets FC = make_flat_offsets(D.SD, D.HC, 1, 0);
     it[0] = DWItem{ws.csT, D.SD, ws.cdh1T, D.HC, grad_at(gc, FC.in_w), EXTRA_ONES, grad_at(gc, FC.in_b)};
     it[1] = DWItem{ws.cu1T, D.HC, ws.cdh2T, D.HC, grad_at(gc, FC.l1_w), EXTRA_ONES, grad_at(gc, FC.l1_b)};
-    it[2] = DWItem{ws.cu2T, D.HC, ws.cdvT, 1, ws.cpl2, EXTRA_NONE, nullptr};
+    it[2] = plain ? DWItem{ws.cu2T, D.HC, ws.cdh3T, D.HC, grad_at(gc, FC.l2_w), EXTRA_ONES, grad_at(gc, FC.l2_b)}
+                  : DWItem{ws.cu2T, D.HC, ws.cdvT, 1, ws.cpl2, EXTRA_NONE, nullptr};
     it[3] = DWItem{ws.ch3T, D.HC, ws.cdvT, 1, grad_at(gc, FC.out_w), EXTRA_ONES, grad_at(gc, FC.out_b)};
 }
 
@@ -456,6 +461,7 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     // the actor's l2 gradient left factored in its own grads region (include/dppo.h)
     const bool plain = dppo_actor_image_head(m.packed_ft) == DPPO_HEAD_PLAIN;   // no l2: nothing to defer
     const bool l2_def = (hp->flags & DPPO_PPO_L2_DEFERRED) != 0 && !plain;
+    const bool cplain = dppo_critic_image_head(m.packed_critic) == DPPO_HEAD_PLAIN;
 
     ActorArgs aa = {};
     aa.packed = (const uint8_t*)m.packed_ft;
@@ -508,7 +514,8 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     aa.adv_stats = stats;
     // the critic's half on stream st: its distinct samples (sample-weighted value loss,
     // crit_rows_kernel), its row tiles, its dW (on the small ring, beside the actor's tail) and its
-    // l2 gradient, which also zeroes the sample counts
+    // l2 gradient, which also zeroes the sample counts (a plain critic: the same last launch with the factored
+    // product off, the dW formed l2's gradient)
     auto critic_half = [&](hipStream_t st) -> int {
         uint32_t* crit_cnt = nullptr;
         if (crit_dedup()) {
@@ -524,13 +531,13 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
         int rc_ = launch_critic_rowtile(ca, precision, st);
         if (rc_) return rc_;
         DWItem items[4];
-        critic_dw_items(D, ws, gc, items);
+        critic_dw_items(D, ws, gc, items, cplain);
         {
             DppoKtScope kt(KT_DW_CRITIC, st);
             rc_ = launch_dw(DWTile::CRITIC, precision, items, 4, ws, 1.f / gscale, ca.crow_cnt, PPO_MIN_CHUNK_ROWS, st);
         }
         if (rc_) return rc_;
-        return launch_critic_l2_back(D, precision, ws, m.packed_critic, gc, crit_cnt, st);
+        return launch_critic_l2_back(D, precision, ws, m.packed_critic, gc, crit_cnt, st, cplain);
     };
     auto actor_grads = [&]() -> int {
         DWItem items[4];

@@ -1,23 +1,36 @@
-"""CriticObs (reference model/common/critic.py:15-54): ResidualMLP([Do*To, h, h, h, 1], Mish).
+"""CriticObs (reference model/common/critic.py:15-54): ResidualMLP([Do*To, h, h, h, 1], Mish) with
+residual_style=True (the fine-tune cfgs), or the class default residual_style=False: the plain
+MLP([Do*To, h, h, h, 1], Mish).
 
 Construction mirrors the reference kwargs; the forward runs the HIP value kernel
 (dppo_critic_forward) once the owning VPGDiffusion has placed the weights on the device."""
 import numpy as np
 import torch
 
-from .mlp import ResidualMLP
+from .mlp import MLP, ResidualMLP
+
+# the one hidden width the critic row tile instantiates (csrc/rowtile.hip dispatch_critic)
+PLAIN_HIDDEN = 256
 
 
 class CriticObs:
     def __init__(self, cond_dim, mlp_dims, activation_type="Mish", use_layernorm=False, residual_style=False,
                  **kwargs):
-        if not residual_style:
-            raise NotImplementedError("CriticObs(residual_style=False) is not implemented on MI355X")
         if activation_type != "Mish":
             raise NotImplementedError("the critic kernels implement the cfg's Mish activation")
         self.cond_dim = cond_dim
-        self.net = ResidualMLP([cond_dim] + list(mlp_dims) + [1], activation_type=activation_type,
-                               use_layernorm=use_layernorm)
+        dims = [cond_dim] + list(mlp_dims) + [1]
+        if residual_style:
+            self.net = ResidualMLP(dims, activation_type=activation_type, use_layernorm=use_layernorm)
+        else:
+            shape = f"mlp_dims = [{PLAIN_HIDDEN}, {PLAIN_HIDDEN}, {PLAIN_HIDDEN}] (three equal hidden layers, Mish, no layernorm)"
+            if use_layernorm:
+                raise NotImplementedError(f"CriticObs(residual_style=False, use_layernorm=True): the plain critic kernels implement {shape}")
+            if list(mlp_dims) != [PLAIN_HIDDEN] * 3:
+                raise NotImplementedError(f"CriticObs(residual_style=False, mlp_dims={list(mlp_dims)}): the plain critic "
+                                          f"kernels implement {shape}")
+            self.net = MLP(dims, activation_type=activation_type)
+        self.head = "residual" if residual_style else "plain"   # ops.ModelDims.critic_head
         self.hidden = self.net.hidden
         self._owner = None
 

@@ -50,16 +50,25 @@ class MLP:
     """Plain MLP (mlp.py:35-92), reached from cfgs with residual_style: False. The kernels implement the
     two-hidden-layer shape of the reference's default mlp_dims, dims [in, h, h, out]:
         h1 = in(x);  u1 = act(h1);  h2 = l1(u1);  a = act(h2);  y = out(a)
-    (the residual network with the l2 layer and the skip removed; include/dppo.h DPPO_HEAD_PLAIN). Every other
-    shape or option is a loud error rather than a silent fallback."""
+    (the residual network with the l2 layer and the skip removed; include/dppo.h DPPO_HEAD_PLAIN). For the critic
+    (CriticObs residual_style=False) they also implement three equal hidden layers with one output and Mish,
+    dims [in, h, h, h, 1]:
+        h1 = in(x);  u1 = mish(h1);  h2 = l1(u1);  u2 = mish(h2);  h3 = l2(u2);  u3 = mish(h3);  y = out(u3)
+    (include/dppo.h dppo_pack_critic_head). Every other shape or option is a loud error rather than a silent
+    fallback."""
 
     SHAPE = "[in, h, h, out] with out_activation_type='Identity' and no layernorm, dropout or append"
+    CRITIC_SHAPE = "[in, h, h, h, 1] with Mish, out_activation_type='Identity' and no layernorm, dropout or append"
 
     def __init__(self, dim_list, append_dim=0, append_layers=None, activation_type="Tanh", out_activation_type="Identity",
                  use_layernorm=False, use_layernorm_final=False, dropout=0):
         dim_list = list(dim_list)
-        if len(dim_list) != 4 or dim_list[1] != dim_list[2]:
-            raise NotImplementedError(f"MLP {dim_list}: the kernels implement the plain head {self.SHAPE}")
+        # the critic's shape: four Dense layers (in, l1, l2, out), the flat layout of the residual critic
+        self.layers4 = (len(dim_list) == 5 and dim_list[1] == dim_list[2] == dim_list[3] and dim_list[4] == 1
+                        and activation_type == "Mish")
+        if not self.layers4 and (len(dim_list) != 4 or dim_list[1] != dim_list[2]):
+            raise NotImplementedError(f"MLP {dim_list}: the kernels implement the plain head {self.SHAPE} "
+                                      f"(the critic's: {self.CRITIC_SHAPE})")
         if use_layernorm or use_layernorm_final or dropout or append_dim or append_layers:
             raise NotImplementedError(f"MLP layernorm / dropout / append: the kernels implement the plain head {self.SHAPE}")
         if out_activation_type != "Identity":
@@ -74,8 +83,12 @@ class MLP:
         return self.dim_list[1]
 
     def init_params(self, rng, prefix=""):
-        """in, l1 and out only: a plain head has no l2 (its range of the flat layout stays zero)."""
+        """in, l1 and out only: a plain head has no l2 (its range of the flat layout stays zero). The critic's
+        [in, h, h, h, 1] has l2 as its third Dense layer, so all four."""
         i, h, o = self.dim_list[0], self.dim_list[1], self.dim_list[-1]
-        return {prefix + "in_w": glorot_uniform(rng, i, h), prefix + "in_b": np.zeros(h, np.float32),
-                prefix + "l1_w": glorot_uniform(rng, h, h), prefix + "l1_b": np.zeros(h, np.float32),
-                prefix + "out_w": glorot_uniform(rng, h, o), prefix + "out_b": np.zeros(o, np.float32)}
+        p = {prefix + "in_w": glorot_uniform(rng, i, h), prefix + "in_b": np.zeros(h, np.float32),
+             prefix + "l1_w": glorot_uniform(rng, h, h), prefix + "l1_b": np.zeros(h, np.float32)}
+        if self.layers4:
+            p.update({prefix + "l2_w": glorot_uniform(rng, h, h), prefix + "l2_b": np.zeros(h, np.float32)})
+        p.update({prefix + "out_w": glorot_uniform(rng, h, o), prefix + "out_b": np.zeros(o, np.float32)})
+        return p

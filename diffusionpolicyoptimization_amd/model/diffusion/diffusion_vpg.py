@@ -54,7 +54,8 @@ class VPGDiffusion(DiffusionModel):
                                   horizon_steps=self.horizon_steps, cond_steps=cond_steps, time_dim=actor.time_dim,
                                   actor_hidden=actor.hidden, critic_hidden=critic.hidden,
                                   denoising_steps=self.sampling_steps, ft_denoising_steps=self.ft_denoising_steps,
-                                  time_stride=self.time_stride, activation=actor.activation_type, head=actor.head)
+                                  time_stride=self.time_stride, activation=actor.activation_type, head=actor.head,
+                                  critic_head=getattr(critic, "head", "residual"))
         self.actor_spec = ops.actor_param_spec(self.dims)
         self.critic_spec = ops.critic_param_spec(self.dims)
         self.n_actor = ops.spec_count(self.actor_spec)
@@ -202,7 +203,8 @@ class VPGDiffusion(DiffusionModel):
             sp = lambda spec, flat: ops.unflatten_params(spec, flat.detach().cpu().numpy())
             keras_weights.save_ppo_model(str(path), sp(self.actor_spec, self.base_params),
                                          sp(self.actor_spec, self.actor_ft_params),
-                                         sp(self.critic_spec, self.critic_params), eta=eta)
+                                         sp(self.critic_spec, self.critic_params), eta=eta,
+                                         critic_plain=self.dims.critic_head == "plain")
             return
         d = {}
         for prefix, flat, spec in (("actor.", self.base_params, self.actor_spec),
@@ -210,6 +212,8 @@ class VPGDiffusion(DiffusionModel):
                                    ("critic.", self.critic_params, self.critic_spec)):
             for n, v in ops.unflatten_params(spec, flat.detach().cpu().numpy()).items():
                 d[prefix + n] = v
+        if self.dims.critic_head != "residual":   # both heads hold the same tensors: the file says which
+            d[ops.CRITIC_HEAD_KEY] = np.array(self.dims.critic_head)
         if eta is not None:
             d["eta.state"] = np.array([eta["logit"], eta["m"], eta["v"]], np.float32)
             d["eta.step"] = np.array(eta["step"], np.int64)
@@ -217,7 +221,8 @@ class VPGDiffusion(DiffusionModel):
 
     def load_weights(self, path):
         if str(path).endswith(".h5"):
-            w = keras_weights.load_ppo_model(str(path), self.actor_spec, self.critic_spec)
+            w = keras_weights.load_ppo_model(str(path), self.actor_spec, self.critic_spec,
+                                             critic_plain=self.dims.critic_head == "plain")
             for key, flat, spec in (("actor", self.base_params, self.actor_spec),
                                     ("actor_ft", self.actor_ft_params, self.actor_spec),
                                     ("critic", self.critic_params, self.critic_spec)):
@@ -229,6 +234,8 @@ class VPGDiffusion(DiffusionModel):
         eta = None
         with np.load(path, allow_pickle=False) as f:
             ops.check_checkpoint_head(f.files, self.actor_spec, path, "actor_ft.")
+            ops.check_checkpoint_critic_head(f.files, self.dims.critic_head, path,
+                                             f[ops.CRITIC_HEAD_KEY] if ops.CRITIC_HEAD_KEY in f.files else None)
             for prefix, flat, spec in (("actor.", self.base_params, self.actor_spec),
                                        ("actor_ft.", self.actor_ft_params, self.actor_spec),
                                        ("critic.", self.critic_params, self.critic_spec)):

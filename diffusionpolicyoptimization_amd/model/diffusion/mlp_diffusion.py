@@ -27,6 +27,8 @@ class DiffusionMLP:
         model = ResidualMLP if residual_style else MLP
         self.mlp_mean = model([self.input_dim] + self.mlp_dims + [output_dim], activation_type=activation_type,
                               out_activation_type=out_activation_type, use_layernorm=use_layernorm)
+        if not residual_style and len(self.mlp_mean.dim_list) != 4:   # MLP's critic shape is no actor head
+            raise NotImplementedError(f"MLP {self.mlp_mean.dim_list}: the kernels implement the plain head {MLP.SHAPE}")
         self.head = "residual" if residual_style else "plain"   # ops.ModelDims.head
         self.hidden = self.mlp_mean.hidden
 

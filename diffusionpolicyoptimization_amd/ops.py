@@ -9,6 +9,7 @@ import functools
 import os
 import math
 import time
+import weakref
 from dataclasses import dataclass
 
 import numpy as np
@@ -37,12 +38,18 @@ class ModelDims:
     # Python-only like the activation: pack_actor records it with the image (dppo_pack_actor_head). The flat
     # layout is the same; a plain actor leaves its l2 range unused and zero (actor_param_spec)
     head: str = "residual"
+    # the critic's head, "residual" (ResidualMLP) or "plain" (MLP([sd, h, h, h, 1]), CriticObs residual_style=False).
+    # Python-only: pack_critic records it with the critic image (dppo_pack_critic_head). Layout, spec and image
+    # bytes are the same for both
+    critic_head: str = "residual"
 
     def __post_init__(self):
         if self.activation not in _lib.ACTIVATION:
             raise ValueError(f"activation must be one of {sorted(_lib.ACTIVATION)}, got {self.activation!r}")
         if self.head not in _lib.HEAD:
             raise ValueError(f"head must be one of {sorted(_lib.HEAD)}, got {self.head!r}")
+        if self.critic_head not in _lib.HEAD:
+            raise ValueError(f"critic_head must be one of {sorted(_lib.HEAD)}, got {self.critic_head!r}")
 
     @property
     def xd(self):
@@ -159,6 +166,21 @@ def check_checkpoint_head(names, spec, path, prefix=""):
         raise ValueError(f"{path}: the checkpoint holds a {kind(has)} actor, the model is {kind(wants)}")
 
 
+CRITIC_HEAD_KEY = "critic.head"   # .npz checkpoints: present ("plain") only for a plain critic
+
+
+def check_checkpoint_critic_head(names, head, path, file_head=None):
+    """A .npz checkpoint's critic must be the model's head. Both heads have the same tensors, so a plain critic's
+    file carries CRITIC_HEAD_KEY = "plain" (file_head: its value when the caller has read it); a file without the
+    key holds a residual critic. A file without a critic passes."""
+    names = set(names)
+    if not any(n.startswith("critic.") for n in names):
+        return
+    has = (str(file_head) if file_head is not None else "plain") if CRITIC_HEAD_KEY in names else "residual"
+    if has != head:
+        raise ValueError(f"{path}: the checkpoint holds a {has} critic, the model is {head}")
+
+
 def _check(t, shape, dtype, name):
     if t is None:
         return
@@ -219,6 +241,12 @@ def pack_all(d: ModelDims, precision, actor_params=None, packed_actor=None, crit
         pack_actor(d, actor_params, precision, out=packed_actor)
         if critic_params is not None:
             pack_critic(d, critic_params, precision, out=packed_critic)
+        return
+    if critic_params is not None and d.critic_head != "residual":
+        # dppo_pack_all records RESIDUAL for the critic image too (= dppo_pack_critic): a plain critic packs on its own
+        if actor_params is not None:
+            pack_actor(d, actor_params, precision, out=packed_actor)
+        pack_critic(d, critic_params, precision, out=packed_critic)
         return
     _lib.call("dppo_pack_all", ctypes.byref(_dims_c(d)), p, ptr(actor_params), ptr(packed_actor), ptr(critic_params),
               ptr(packed_critic), stream_handle(t.device))
@@ -433,6 +461,31 @@ class MappedDoubles:
                 raise _lib.DppoError(f"mapped tag {tag} not seen within {timeout_s} s (found {a[index]})")
 
 
+def _forget_image(address):
+    try:
+        _lib.call("dppo_forget_image", ctypes.c_void_p(address))
+    except Exception:   # interpreter shutdown: the library may be gone, and so is its table
+        pass
+
+
+def _forget_on_free(img):
+    """The library keeps an image's attributes (activation, heads) in a host table keyed by the image's ADDRESS.
+    When the image tensor dies its memory returns to the allocator, and another tensor at that address (a clone
+    of an image, say) would inherit the attributes: the entry is erased with the tensor (dppo_forget_image). An
+    image that is a view of a larger buffer lives as long as that buffer does: the entry then goes with the base."""
+    if img._base is not None:
+        fins = img._base.__dict__.setdefault("_dppo_forget_views", {})
+        fin = fins.get(img.data_ptr())
+        if fin is None or not fin.alive:
+            fins[img.data_ptr()] = fin = weakref.finalize(img._base, _forget_image, img.data_ptr())
+            fin.atexit = False
+        return
+    fin = getattr(img, "_dppo_forget", None)
+    if fin is None or not fin.alive:
+        img._dppo_forget = weakref.finalize(img, _forget_image, img.data_ptr())
+        img._dppo_forget.atexit = False
+
+
 def pack_actor(d: ModelDims, params_flat, precision, out=None):
     """The packed image of an actor; d.activation and d.head are recorded with it (dppo_pack_actor_head) and
     decide which kernels every later launch on the image runs."""
@@ -444,18 +497,22 @@ def pack_actor(d: ModelDims, params_flat, precision, out=None):
         _check(out, (_packed_bytes(d, p)[0],), torch.uint8, "packed actor")
     _lib.call("dppo_pack_actor_head", ctypes.byref(_dims_c(d)), p, _lib.ACTIVATION[d.activation], _lib.HEAD[d.head],
               ptr(params_flat), ptr(out), stream_handle(params_flat.device))
+    _forget_on_free(out)
     return out
 
 
 def pack_critic(d: ModelDims, params_flat, precision, out=None):
+    """The packed image of a critic; d.critic_head is recorded with it (dppo_pack_critic_head) and decides which
+    row tile and weight-gradient problems every later launch on the image runs."""
     p = _prec(precision)
     _check(params_flat, (_n_params(d)[1],), torch.float32, "critic params")
     if out is None:
         out = torch.empty(_packed_bytes(d, p)[1], dtype=torch.uint8, device=params_flat.device)
     else:
         _check(out, (_packed_bytes(d, p)[1],), torch.uint8, "packed critic")
-    _lib.call("dppo_pack_critic", ctypes.byref(_dims_c(d)), p, ptr(params_flat), ptr(out),
+    _lib.call("dppo_pack_critic_head", ctypes.byref(_dims_c(d)), p, _lib.HEAD[d.critic_head], ptr(params_flat), ptr(out),
               stream_handle(params_flat.device))
+    _forget_on_free(out)
     return out
 
 

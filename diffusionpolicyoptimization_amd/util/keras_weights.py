@@ -17,6 +17,11 @@ whose module_list holds one Sequential([Dense, activation]) per layer) is writte
 and has no l2. This package round-trips its own files under that naming; the match with a file Keras wrote
 for the reference's MLP is UNPINNED (Keras cannot be installed here, and no such file was available). A file
 of one head does not load into a model of the other (the l2 variables are missing or unread).
+A plain CriticObs (residual_style=False: Q1 is the reference's MLP([in, h, h, h, 1]), four Sequentials) follows
+the same mapping under critic/Q1/:
+      Q1/module_list/{sequential, sequential_1, sequential_2, sequential_3}/layers/dense   (in, l1, l2, out)
+equally UNPINNED against a file Keras wrote. A residual critic file does not load into a plain critic, nor
+the reverse: the error names both heads.
 Reading is tolerant of the container names (any residual block / the Sequential's Dense layers in
 Keras's numbering) and checks every shape against the flat spec; what is missing is named in the
 error. Parity is pinned to this published layout, not to a file Keras wrote (TF/Keras cannot be
@@ -44,6 +49,12 @@ def _plain_paths(prefix):
     return {"in": seq(0), "l1": seq(1), "out": seq(2)}
 
 
+def _plain_critic_paths(prefix):
+    """Keras-3 paths of the plain critic MLP([in, h, h, h, 1]) under `prefix` (naming unpinned, module docstring)."""
+    seq = lambda i: f"{prefix}module_list/sequential{'_%d' % i if i else ''}/layers/dense"
+    return {"in": seq(0), "l1": seq(1), "l2": seq(2), "out": seq(3)}
+
+
 def _is_plain(names):
     return not any(n == "l2_w" for n in names)
 
@@ -59,9 +70,9 @@ def actor_paths(prefix="", plain=False):
     return out
 
 
-def critic_paths(prefix=""):
+def critic_paths(prefix="", plain=False):
     out = {}
-    for k, v in _dense_paths(prefix + "Q1/").items():
+    for k, v in (_plain_critic_paths if plain else _dense_paths)(prefix + "Q1/").items():
         out[f"{k}_w"], out[f"{k}_b"] = v + "/vars/0", v + "/vars/1"
     return out
 
@@ -164,10 +175,20 @@ ETA_LOGIT = "eta/vars/0"                 # EtaFixed's one variable, where Keras 
 ETA_OPT = "eta/optimizer_state"         # [m, v, step] of its AdamW (resume exactly)
 
 
-def load_ppo_model(path, actor_spec, critic_spec):
+def check_critic_head(data, plain, path, prefix="critic/"):
+    """The file's critic must be the model's head (both have l2, so the container names tell them apart)."""
+    has = any(k.startswith(prefix + "Q1/module_list/") for k in data)
+    if has != bool(plain) and any(k.startswith(prefix + "Q1/") for k in data):
+        kind = lambda p: "plain (MLP)" if p else "residual (ResidualMLP)"
+        raise ValueError(f"{path}: the checkpoint holds a {kind(has)} critic, the model is {kind(plain)}")
+
+
+def load_ppo_model(path, actor_spec, critic_spec, critic_plain=False):
     """{"actor", "actor_ft", "critic"} dicts from a fine-tune checkpoint (PPODiffusion.save_weights),
-    plus "eta" = {"logit", "m", "v", "step"} when the model learned eta."""
+    plus "eta" = {"logit", "m", "v", "step"} when the model learned eta. critic_plain: the model's critic is
+    the plain MLP (CriticObs residual_style=False)."""
     data = read_h5(path)
+    check_critic_head(data, critic_plain, path)
     out = {}
     used = set()
     if ETA_LOGIT in data:
@@ -178,7 +199,7 @@ def load_ppo_model(path, actor_spec, critic_spec):
     plain = _is_plain(n for n, _ in actor_spec)
     for key, paths, spec in (("actor", actor_paths("actor/", plain), actor_spec),
                              ("actor_ft", actor_paths("actor_ft/", plain), actor_spec),
-                             ("critic", critic_paths("critic/"), critic_spec)):
+                             ("critic", critic_paths("critic/", critic_plain), critic_spec)):
         got, missing = _resolve(data, paths, used)
         if missing:
             raise ValueError(f"{path}: missing {key} variables: {missing}")
@@ -197,6 +218,8 @@ def _empty_groups(prefix, network, plain=False):
     elif network == "actor":
         g += [prefix + "mlp_mean/vars", prefix + f"mlp_mean/residual_blocks/{BLOCK}/vars",
               prefix + "time_embedding/vars", prefix + "time_embedding/layers/sinusoidal_pos_emb/vars"]
+    elif plain:
+        g += [prefix + "Q1/vars"] + [prefix + f"Q1/module_list/sequential{'_%d' % i if i else ''}/vars" for i in range(4)]
     else:
         g += [prefix + "Q1/vars", prefix + f"Q1/residual_blocks/{BLOCK}/vars"]
     return g
@@ -209,9 +232,10 @@ def save_actor(path, params):
              groups=_empty_groups("", "actor", plain))
 
 
-def save_ppo_model(path, actor, actor_ft, critic, eta=None):
+def save_ppo_model(path, actor, actor_ft, critic, eta=None, critic_plain=False):
     """PPODiffusion.save_weights (agent/finetune/train_agent.py:127-133 layout); eta: the learnable
-    eta's {"logit", "m", "v", "step"} (learn_eta models), stored under eta/."""
+    eta's {"logit", "m", "v", "step"} (learn_eta models), stored under eta/. critic_plain: the critic is the
+    plain MLP and takes the plain-MLP variable paths."""
     d = {}
     if eta is not None:
         d[ETA_LOGIT] = np.array([eta["logit"]], np.float32)
@@ -219,9 +243,9 @@ def save_ppo_model(path, actor, actor_ft, critic, eta=None):
     plain = _is_plain(actor)
     for prefix, params, paths in (("actor/", actor, actor_paths("actor/", plain)),
                                   ("actor_ft/", actor_ft, actor_paths("actor_ft/", plain)),
-                                  ("critic/", critic, critic_paths("critic/"))):
+                                  ("critic/", critic, critic_paths("critic/", critic_plain))):
         for k, v in params.items():
             d[paths[k]] = np.asarray(v, np.float32)
     groups = ["vars"] + _empty_groups("actor/", "actor", plain) + _empty_groups("actor_ft/", "actor", plain) + \
-        _empty_groups("critic/", "critic") + (["eta"] if eta is not None else [])
+        _empty_groups("critic/", "critic", critic_plain) + (["eta"] if eta is not None else [])
     write_h5(path, d, groups=groups)

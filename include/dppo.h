@@ -193,11 +193,38 @@ DPPO_API int dppo_pack_actor_act(const dppo_dims* d, int precision, int activati
  * skip path. In a minibatch dW_out = u2^T dy is written in place and no l2_back / out_back product runs;
  * the fused optimizer step leaves T_OUT zero and the fold launch derives M = rnd(W_out) again.
  * DPPO_STEP_L2_FROM_PL2 on a plain image is DPPO_EINVAL; dppo_materialize_l2 on one does nothing. The supported-geometry tables (sampler, update) and
- * dppo_ppo_plan_act apply to a plain image line for line, with the same messages. The critic has no plain
- * form. */
+ * dppo_ppo_plan_act apply to a plain image line for line, with the same messages. The critic's head is an
+ * attribute of its own image (dppo_pack_critic_head below). */
 enum { DPPO_HEAD_RESIDUAL = 0, DPPO_HEAD_PLAIN = 1 };
 DPPO_API int dppo_pack_actor_head(const dppo_dims* d, int precision, int activation, int head, const float* params,
                                   void* packed, void* stream);
+/* The critic's head (CriticObs residual_style, model/common/critic.py:15-38), an attribute of the packed critic
+ * image recorded like the actor's, keyed by the image's address (an addition within ABI 15). DPPO_HEAD_RESIDUAL is
+ * ResidualMLP; DPPO_HEAD_PLAIN is the reference's MLP([SD, HC, HC, HC, 1]) (model/common/mlp.py:35-92), the class
+ * default with the cfgs' mlp_dims = [256, 256, 256], Mish:
+ *     residual:  h1 = in(s); u1 = mish(h1); h2 = l1(u1); u2 = mish(h2); h3 = l2(u2) + h1;  V = out(h3)
+ *     plain:     h1 = in(s); u1 = mish(h1); h2 = l1(u1); u2 = mish(h2); h3 = l2(u2); u3 = mish(h3); V = out(u3)
+ * The four Dense layers have the same shapes in both, so the flat critic layout above (in_w ... out_b),
+ * dppo_critic_param_count, dppo_critic_packed_bytes, the image's segments, the optimizer ranges, the clip norms
+ * and the data-parallel buckets are unchanged, and the image BYTES of a plain pack equal those of a residual pack
+ * of the same parameters: only the attribute differs. dppo_pack_critic_head packs like dppo_pack_critic and
+ * records `head`; dppo_pack_critic and dppo_pack_all record RESIDUAL, so re-packing a buffer through them resets
+ * it; the optimizer steps (staged or DPPO_STEP_FUSED_PACK) rewrite the image and leave the attribute alone; an
+ * address never packed through these entries reads as RESIDUAL. A head outside the enum is DPPO_EINVAL.
+ * dppo_critic_forward and dppo_ppo_minibatch{,_part} look the image up and run that head's row tile (the only
+ * critic hidden width instantiated, 256, for both). In a minibatch a plain critic's l2 gradient is a true
+ * weight-gradient product (u2^T dh3 from a dh3 image the row tile writes, dppo_ppo_workspace_bytes below), not
+ * the factored form through the out layer; the critic's last launch then only re-zeroes the stream's sample counts. */
+DPPO_API int dppo_pack_critic_head(const dppo_dims* d, int precision, int head, const float* params, void* packed,
+                                   void* stream);
+/* The attributes above (an actor image's activation and head, a critic image's head) live in a host table keyed
+ * by the image's ADDRESS, so they outlive the buffer: memory allocated at the same address later (a copy of an
+ * image, which was never packed through these entries, for one) would read the old owner's attributes instead of
+ * the defaults. A caller that releases an image buffer whose attributes are not the defaults calls
+ * dppo_forget_image first: the address then reads as never packed (ReLU / RESIDUAL / RESIDUAL, no pending
+ * sampler-table refresh). Host-only, no launch; NULL is accepted (an addition within ABI 15). The Python package
+ * does this when an image tensor it packed is freed (ops.pack_actor / ops.pack_critic). */
+DPPO_API int dppo_forget_image(const void* packed);
 
 /* ---- a9: diffusion-policy action sampler, VPGDiffusion.call (model/diffusion/diffusion_vpg.py:250-339) ----
  * All K DDPM steps for n_envs rows in ONE launch: DiffusionMLP forward on MFMA + fused DDPM
@@ -455,6 +482,9 @@ DPPO_API int dppo_eta_step(float* eta_state, const double* metrics, int64_t step
                            float beta1, float beta2, float eps, int mode, float eta_min, float eta_max,
                            const float* ddim_base, float* sched, int ddim_steps, float* eta_out, void* stream);
 
+/* The workspace is sized before an image is known, so one size serves both critic heads: it ends with the plain
+ * critic's dh3 image (critic_hidden x batch_rows rounded up to 64, operand elements: 2 B, fp32 4 B), which a
+ * residual critic leaves unused. Every other offset is what it was before that image was added. */
 DPPO_API size_t dppo_ppo_workspace_bytes(const dppo_dims* d, int precision, int batch_rows);
 /* Which kernel paths a launch of `rows` rows takes on the current device (read-only host arithmetic,
  * the same functions the launchers call; no device work; an addition within ABI 15). mode: a
@@ -465,7 +495,9 @@ DPPO_API size_t dppo_ppo_workspace_bytes(const dppo_dims* d, int precision, int 
  *    the same two of the critic's launch (host-side: with sample dedup the kernel re-cuts the same
  *    number of chunks over the device-side count of distinct samples)};
  * the weight-gradient fields are 0 where the mode has no such launch (logprob: all four; pretrain:
- * the critic's). */
+ * the critic's). The critic's two are those of the RESIDUAL critic's problem list (10 output tiles at
+ * critic_hidden 256); a plain critic image's list has 12 (its l2 problem is HC x HC), so its launch may cut fewer
+ * chunks on the same rows: this query takes no image and does not report that. */
 enum { DPPO_PLAN_TRAIN = 0, DPPO_PLAN_PRETRAIN = 1, DPPO_PLAN_LOGPROB = 2 };
 DPPO_API int dppo_ppo_plan(const dppo_dims* d, int precision, int rows, int mode, int* out);
 /* the same for an actor image of the given activation (DPPO_ACT_*; dppo_ppo_plan is the ReLU plan): a

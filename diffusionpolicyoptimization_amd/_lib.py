@@ -30,6 +30,8 @@ ACTIVATION = {"ReLU": 0, "Mish": 1}
 # the actor's head (DPPO_HEAD_*), the image's second attribute (dppo_pack_actor_head): "residual" is
 # ResidualMLP (residual_style=True), "plain" the reference's MLP([in, h, h, out]) (residual_style=False)
 HEAD = {"residual": 0, "plain": 1}
+# the critic's layer normalisation (DPPO_LN_*), the critic image's second attribute (dppo_pack_critic_ln)
+LAYERNORM = {False: 0, True: 1}
 
 
 class DppoDims(ctypes.Structure):
@@ -67,6 +69,12 @@ _SIGNATURES = {
     "dppo_pack_critic": (_I, [_DIMS, _I, _P, _P, _P]),
     "dppo_pack_critic_head": (_I, [_DIMS, _I, _I, _P, _P, _P]),
     "dppo_forget_image": (_I, [_P]),
+    "dppo_pack_critic_ln": (_I, [_DIMS, _I, _I, _I, _P, _P, _P]),
+    "dppo_critic_param_count_ln": (_SZ, [_DIMS, _I, _I]),
+    "dppo_critic_packed_bytes_ln": (_SZ, [_DIMS, _I, _I, _I]),
+    "dppo_grad_clip_workspace_bytes_ln": (_SZ, [_DIMS, _I, _I, _I]),
+    "dppo_grad_clip_scales_ln": (_I, [_DIMS, _I, _I, _I, _P, _F, _P, _P, _P, _P]),
+    "dppo_ppo_clear_ranges_ln": (_I, [_DIMS, _I, _I, _I, _I, _P, _P, _I, _P, _P, ctypes.POINTER(ctypes.c_int)]),
     "dppo_pack_actor_act": (_I, [_DIMS, _I, _I, _P, _P, _P]),
     "dppo_pack_actor_head": (_I, [_DIMS, _I, _I, _I, _P, _P, _P]),
     "dppo_sample": (_I, [_DIMS, _I, _P, _P, _P, _P, _I, _P, _P, _U64, _U64, _I, _I, _F, _F, _F, _P, _P, _P]),
@@ -98,6 +106,7 @@ _SIGNATURES = {
     "dppo_ppo_workspace_bytes": (_SZ, [_DIMS, _I, _I]),
     "dppo_ppo_plan": (_I, [_DIMS, _I, _I, _I, ctypes.POINTER(ctypes.c_int)]),
     "dppo_ppo_plan_act": (_I, [_DIMS, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)]),
+    "dppo_ppo_plan_critic": (_I, [_DIMS, _I, _I, _I, ctypes.POINTER(ctypes.c_int)]),
     "dppo_ppo_adv_stats": (_I, [_P, _I64, _I, _U64, _I, _I64, _I, _P, _P, _P]),
     "dppo_ppo_adv_stats_all": (_I, [_P, _I64, _I, _U64, _I, _I, _I64, _I, _P, _P]),
     "dppo_ppo_minibatch": (_I, [_DIMS, _I, ctypes.POINTER(DppoPpoHparams), _P, _P, _P, _P, _P, _P, _P, _P, _P,

@@ -513,13 +513,15 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
             self._met_dev = [torch.zeros(16, dtype=torch.float64, device=dev) for _ in range(2)]
             self._ev_rows = torch.cuda.Event()
             self._ev_met = torch.cuda.Event()
-        # the clip's norm table (12 actor + 8 critic variables), scale table and partial-sum workspaces:
-        # allocated once, captured by the bound norm launches and optimizer steps
+        # the clip's norm table (12 actor + 8 critic variables, plus a layer-normed critic's gamma / beta
+        # vectors), scale table and partial-sum workspaces: allocated once, captured by the bound norm launches
+        # and optimizer steps
+        nv = 12 + len(self.model.critic_spec)
         if clip_dev and self._clip_buf is None:
             ws = [torch.empty(ops.grad_clip_workspace_bytes(self.model.dims, net) // 8, dtype=torch.float64, device=dev)
                   for net in ("actor", "critic")]
-            self._clip_buf = (torch.zeros(20, dtype=torch.float32, device=dev),
-                              torch.ones(20, dtype=torch.float32, device=dev), *ws)
+            self._clip_buf = (torch.zeros(nv, dtype=torch.float32, device=dev),
+                              torch.ones(nv, dtype=torch.float32, device=dev), *ws)
 
     def _prepare_update(self):
         """The rollout's hand-off to the epochs: rewards and flags to the device, episode sums, reward

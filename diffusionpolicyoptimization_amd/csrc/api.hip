@@ -87,18 +87,41 @@ extern "C" int dppo_pack_actor_act(const dppo_dims* d, int precision, int activa
 extern "C" int dppo_pack_actor(const dppo_dims* d, int precision, const float* params, void* packed, void* stream) {
     return dppo_pack_actor_act(d, precision, DPPO_ACT_RELU, params, packed, stream);
 }
-extern "C" int dppo_pack_critic_head(const dppo_dims* d, int precision, int head, const float* params, void* packed,
-                                     void* stream) {
+extern "C" size_t dppo_critic_param_count_ln(const dppo_dims* d, int head, int layernorm) {
+    Dims D;
+    if (dppo_check_dims(d, &D) || !dppo_head_ok(head) || !dppo_ln_ok(layernorm)) return 0;
+    return make_flat_offsets(D.SD, D.HC, 1, 0).count +
+           critic_ln_flat_count(D.HC, critic_ln_sites(head == DPPO_HEAD_PLAIN, layernorm == DPPO_LN_ON));
+}
+extern "C" size_t dppo_critic_packed_bytes_ln(const dppo_dims* d, int precision, int head, int layernorm) {
+    Dims D;
+    if (dppo_check_dims(d, &D) || !dppo_head_ok(head) || !dppo_ln_ok(layernorm)) return 0;
+    const int sites = critic_ln_sites(head == DPPO_HEAD_PLAIN, layernorm == DPPO_LN_ON);
+    return make_mlp_layout(D.SD, D.HC, 1, 0, precision).total + (sites ? critic_ln_image_bytes(D.HC, sites) : 0);
+}
+extern "C" int dppo_pack_critic_ln(const dppo_dims* d, int precision, int head, int layernorm, const float* params,
+                                   void* packed, void* stream) {
     Dims D;
     int rc = dppo_check_dims(d, &D);
     if (rc) return rc;
     DPPO_CHECK(params && packed, "dppo_pack_critic: null pointer");
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
     DPPO_CHECK(dppo_head_ok(head), "dppo_pack_critic_head: bad head %d (DPPO_HEAD_RESIDUAL or DPPO_HEAD_PLAIN)", head);
+    DPPO_CHECK(dppo_ln_ok(layernorm), "dppo_pack_critic_ln: bad layernorm %d (DPPO_LN_OFF or DPPO_LN_ON)", layernorm);
+    // the pack's job list follows the image's attributes (the tail), so they are set before it packs
+    const int old_head = dppo_critic_image_head(packed), old_ln = dppo_critic_image_ln(packed);
+    dppo_critic_image_set_head(packed, head);
+    dppo_critic_image_set_ln(packed, layernorm);
     rc = dppo_pack_mlp(D.SD, D.HC, 1, 0, precision, params, packed, (hipStream_t)stream);
-    if (rc) return rc;   // refused: nothing was written, the image keeps its head
-    dppo_critic_image_set_head(packed, head);   // the bytes are the same for both heads; the launches follow this
-    return DPPO_OK;
+    if (rc) {   // refused: nothing was written, the image keeps its attributes
+        dppo_critic_image_set_head(packed, old_head);
+        dppo_critic_image_set_ln(packed, old_ln);
+    }
+    return rc;
+}
+extern "C" int dppo_pack_critic_head(const dppo_dims* d, int precision, int head, const float* params, void* packed,
+                                     void* stream) {
+    return dppo_pack_critic_ln(d, precision, head, DPPO_LN_OFF, params, packed, stream);
 }
 extern "C" int dppo_pack_critic(const dppo_dims* d, int precision, const float* params, void* packed, void* stream) {
     return dppo_pack_critic_head(d, precision, DPPO_HEAD_RESIDUAL, params, packed, stream);

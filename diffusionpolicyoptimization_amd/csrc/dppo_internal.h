@@ -59,6 +59,17 @@ inline bool dppo_head_ok(int h) { return h == DPPO_HEAD_RESIDUAL || h == DPPO_HE
 // launch do (rowtile.hip, update.hip)
 int dppo_critic_image_head(const void* packed);
 void dppo_critic_image_set_head(const void* packed, int head);
+// the critic image's second attribute (dppo_pack_critic_ln): DPPO_LN_OFF for an unlisted address. Unlike the head
+// it lengthens the image and the flat layout by a tail (dppo_layout.h critic_ln_*); dppo_critic_ln_sites is the
+// number of norms of the image at `packed` (0 without layer norm)
+int dppo_critic_image_ln(const void* packed);
+void dppo_critic_image_set_ln(const void* packed, int layernorm);
+inline bool dppo_ln_ok(int l) { return l == DPPO_LN_OFF || l == DPPO_LN_ON; }
+inline int dppo_critic_ln_sites(const void* packed) {
+    return critic_ln_sites(dppo_critic_image_head(packed) == DPPO_HEAD_PLAIN, dppo_critic_image_ln(packed) == DPPO_LN_ON);
+}
+// the critic's jobs of a pack launch with the image's tail (pack.hip)
+int dppo_pack_critic_image(const Dims& D, int precision, const float* params, void* packed, hipStream_t s);
 // device address of mapped pinned host memory (dppo_host_alloc), cached; null if not mapped (host_staging.hip)
 void* mapped_ptr(const void* host);
 

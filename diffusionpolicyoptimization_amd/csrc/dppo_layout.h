@@ -144,6 +144,18 @@ DPPO_HD inline FlatOffsets make_flat_offsets(int in_dim, int hidden, int out_dim
     return f;
 }
 
+// A layer-normed critic (include/dppo.h dppo_pack_critic_ln) appends a tail to both layouts; every offset above
+// keeps its value. `sites` norms (3 for the plain head: one per hidden layer; 2 for the residual head: the two
+// pre-activation norms of the block), each a gamma [hidden] then a beta [hidden]:
+//   flat   ln1_g, ln1_b, ln2_g, ln2_b(, ln3_g, ln3_b) after out_b: vector v = 2 site + (0 gamma, 1 beta) starts
+//          at FlatOffsets::count + v hidden
+//   image  the same 2 sites vectors, fp32 and dense, in one segment at MlpLayout::total (256-B aligned)
+DPPO_HD inline int critic_ln_sites(bool plain_head, bool layernorm) { return layernorm ? (plain_head ? 3 : 2) : 0; }
+DPPO_HD inline size_t critic_ln_flat_count(int hidden, int sites) { return (size_t)2 * sites * hidden; }
+DPPO_HD inline size_t critic_ln_image_bytes(int hidden, int sites) { return dppo_align256((size_t)4 * 2 * sites * hidden); }
+// Keras' LayerNormalization default in the plain MLP (mlp.py:66), 1e-6 inside the residual block (mlp.py:174-176)
+DPPO_HD inline float critic_ln_eps(bool plain_head) { return plain_head ? 1e-3f : 1e-6f; }
+
 // actor: in = XD + TD + SD, out = XD, time_dim = TD; critic: in = SD, out = 1, time_dim = 0
 struct ModelDims {
     int XD, SD, TD, H, HC, K, KF, Ta, Da;

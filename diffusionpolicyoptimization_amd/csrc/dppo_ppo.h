@@ -142,6 +142,11 @@ struct CriticArgs {
     const int* crow_n;
     const uint32_t* crow_mult;
     const int* crow_cnt;
+    // a layer-normed critic image, TRAIN: the gradient tail [2 sites][HC] (dgamma_k, dbeta_k in the flat layout's
+    // order, dppo_layout.h critic_ln_*), which the tiles add into, and the factor that takes the backward seed
+    // scale out of those sums (the dW's out_scale)
+    float* gln;
+    float ln_unscale;
 };
 
 // the actor row tile of a launch over `rows` rows (the 64-padded image rows in the TRAIN modes):
@@ -153,3 +158,5 @@ ActorTilePlan actor_tile_plan(int precision, int H, int XD, int64_t rows, int ac
 // otherwise); nothing is launched and no device state is read or written
 int launch_actor_rowtile(const ActorArgs& a, int precision, hipStream_t s, bool dry = false);
 int launch_critic_rowtile(const CriticArgs& a, int precision, hipStream_t s, bool dry = false);
+// the same for a layer-normed critic image (rowtile_ln.hip; launch_critic_rowtile routes to it by the image's attribute)
+int launch_critic_rowtile_ln(const CriticArgs& a, int precision, hipStream_t s, bool dry);

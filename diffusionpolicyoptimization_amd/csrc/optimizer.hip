@@ -39,7 +39,7 @@ __device__ inline float l2_virtual_grad(const float* __restrict__ g, const L2Vir
 // end[v] = one past variable v in the range (layout order), INT_MAX past the last variable. A step
 // kernel instantiated with a ClipTab as its trailing argument reads each gradient as the rounded fp32
 // product g[i] * scales[v]; instantiated without one it is the unclipped kernel, argument for argument.
-constexpr int CLIP_MAXV = 20;
+constexpr int CLIP_MAXV = 26;   // 12 actor + 8 critic + up to 6 layer-norm vectors
 struct ClipTab { const float* scales; int end[CLIP_MAXV]; };
 __device__ inline int clip_var(const ClipTab& c, int i) {
     int v = 0;
@@ -411,14 +411,18 @@ struct StepCtx {
     int mode;              // the AdamW mode, the DPPO_STEP_* flags taken out
     bool defer, l2v, fuse, clear_g;
     FlatOffsets FA, FC;
+    int cln_sites;         // the critic's norms (its image's attributes; a clipped range without one: by its length)
+    size_t ccount;         // the critic's parameters with their tail, FC.count + 2 cln_sites HC
     L2Virt vt;
     bool clipped;
     ClipTab clip;
 };
 
 // The variables of the chosen networks (DPPO_NET_*) in layout order: end[v] = one past variable v,
-// counted from the start of the range; returns their number (12 actor, 8 critic)
-static int net_var_ends(const FlatOffsets& FA, const FlatOffsets& FC, int nets, int64_t* end) {
+// counted from the start of the range; returns their number (12 actor, 8 critic + the 2 ln_sites vectors of a
+// layer-normed critic's tail, each a variable of `hidden` elements)
+static int net_var_ends(const FlatOffsets& FA, const FlatOffsets& FC, int nets, int64_t* end, int ln_sites = 0,
+                        int hidden = 0) {
     int nv = 0;
     int64_t base = 0;
     if (nets & DPPO_NET_ACTOR) {
@@ -430,6 +434,7 @@ static int net_var_ends(const FlatOffsets& FA, const FlatOffsets& FC, int nets, 
     if (nets & DPPO_NET_CRITIC) {
         const size_t e[8] = {FC.in_b, FC.l1_w, FC.l1_b, FC.l2_w, FC.l2_b, FC.out_w, FC.out_b, FC.count};
         for (size_t x : e) end[nv++] = base + (int64_t)x;
+        for (int v = 1; v <= 2 * ln_sites; ++v) end[nv++] = base + (int64_t)FC.count + (int64_t)v * hidden;
     }
     return nv;
 }
@@ -462,6 +467,29 @@ static int step_prologue(const StepArgs& a, StepCtx& c) {
     c.mode = a.w.mode & ~(DPPO_STEP_DEFER_SAMPLER_TABLES | DPPO_STEP_L2_FROM_PL2 | DPPO_STEP_FUSED_PACK | DPPO_STEP_CLEAR_GRADS);
     c.FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
     c.FC = make_flat_offsets(D.SD, D.HC, 1, 0);
+    // The critic's layout follows its image's attributes. A clipped critic range without an image is told by its
+    // length (the three layouts differ in it)
+    c.cln_sites = a.packed_critic ? dppo_critic_ln_sites(a.packed_critic) : 0;
+    if (!a.packed_critic && a.nets >= 1 && a.nets <= 3 && (a.nets & DPPO_NET_CRITIC)) {
+        const int64_t rest = a.w.n - (int64_t)c.FC.count - ((a.nets & DPPO_NET_ACTOR) ? (int64_t)c.FA.count : 0);
+        for (int sites = 2; sites <= 3; ++sites)
+            if (rest == (int64_t)critic_ln_flat_count(D.HC, sites)) c.cln_sites = sites;
+    }
+    c.ccount = c.FC.count + critic_ln_flat_count(D.HC, c.cln_sites);
+    if (a.packed_critic && a.critic_params && a.w.params && a.critic_params >= a.w.params &&
+        a.critic_params < a.w.params + a.w.n) {
+        // the range holds the critic from critic_params on: it must hold the layout of the image's attributes
+        const int64_t room = a.w.n - (int64_t)(a.critic_params - a.w.params);
+        DPPO_CHECK(c.cln_sites == 0 || room >= (int64_t)c.ccount,
+                   "dppo_optimizer_step: the critic image is layer-normed (%zu parameters with its gamma / beta tail), the "
+                   "range holds %lld from critic_params on: buffers sized for the layout without the tail", c.ccount,
+                   (long long)room);
+        if (c.cln_sites == 0 && !a.packed_actor && a.critic_params == a.w.params)
+            for (int sites = 2; sites <= 3; ++sites)
+                DPPO_CHECK(a.w.n != (int64_t)(c.FC.count + critic_ln_flat_count(D.HC, sites)),
+                           "dppo_optimizer_step: the range is a layer-normed critic's (%lld parameters), the critic image has "
+                           "no layer norm (dppo_pack_critic_ln)", (long long)a.w.n);
+    }
     c.vt = L2Virt{};
     if (c.l2v) {
         DPPO_CHECK(!a.packed_actor || dppo_actor_image_head(a.packed_actor) != DPPO_HEAD_PLAIN,
@@ -480,7 +508,7 @@ static int step_prologue(const StepArgs& a, StepCtx& c) {
         DPPO_CHECK(a.nets >= 1 && a.nets <= 3, "dppo_optimizer_step_clip: nets %d outside 1..3", a.nets);
         DPPO_CHECK(a.clip_scales, "dppo_optimizer_step_clip: clip_scales is NULL");
         int64_t end[CLIP_MAXV];
-        const int nv = net_var_ends(c.FA, c.FC, a.nets, end);
+        const int nv = net_var_ends(c.FA, c.FC, a.nets, end, c.cln_sites, D.HC);
         const float* crit = a.w.params ? a.w.params + ((a.nets & DPPO_NET_ACTOR) ? c.FA.count : 0) : nullptr;
         DPPO_CHECK(a.w.n == end[nv - 1] && ((a.nets & DPPO_NET_ACTOR) == 0 || !a.actor_params || a.actor_params == a.w.params) &&
                    ((a.nets & DPPO_NET_CRITIC) == 0 || !a.critic_params || a.critic_params == crit),
@@ -645,7 +673,7 @@ static int optimizer_step_impl(const StepArgs& a) {
     const AdamwArgs& w = a.w;
     // the one-launch forms: a single network whose parameters are exactly the range
     const bool one_actor = a.packed_actor && !a.packed_critic && a.actor_params == w.params && w.n == (int64_t)c.FA.count;
-    const bool one_critic = a.packed_critic && !a.packed_actor && a.critic_params == w.params && w.n == (int64_t)c.FC.count;
+    const bool one_critic = a.packed_critic && !a.packed_actor && a.critic_params == w.params && w.n == (int64_t)c.ccount;
     if (!(c.fuse && (one_actor || one_critic) && w.n > 0)) return staged_step(a, c);
     { const int rc_ = check_metrics_copy(a.metrics, c.mout, a.n_metrics, a.metrics_tag); if (rc_) return rc_; }
     DPPO_CHECK(w.step >= 1 && (c.mode == DPPO_ADAMW_KERAS || c.mode == DPPO_ADAMW_TORCH), "dppo_adamw: bad step or mode");
@@ -792,11 +820,11 @@ __global__ __launch_bounds__(CLIP_THREADS) void grad_clip_kernel(const float* __
     }
 }
 
-static int make_clip_vars(const Dims& D, int nets, ClipVars& cv) {
+static int make_clip_vars(const Dims& D, int nets, ClipVars& cv, int ln_sites = 0) {
     const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD), FC = make_flat_offsets(D.SD, D.HC, 1, 0);
     int64_t end[CLIP_MAXV];
     cv = ClipVars{};
-    cv.nv = net_var_ends(FA, FC, nets, end);
+    cv.nv = net_var_ends(FA, FC, nets, end, ln_sites, D.HC);
     DPPO_CHECK(end[cv.nv - 1] < ((int64_t)1 << 31), "dppo_grad_clip: range too large");
     cv.cstart[0] = 0;
     for (int v = 0; v < CLIP_MAXV; ++v) {
@@ -808,25 +836,42 @@ static int make_clip_vars(const Dims& D, int nets, ClipVars& cv) {
     return DPPO_OK;
 }
 
-extern "C" size_t dppo_grad_clip_workspace_bytes(const dppo_dims* d, int nets) {
+extern "C" size_t dppo_grad_clip_workspace_bytes_ln(const dppo_dims* d, int nets, int critic_head, int critic_layernorm) {
     Dims D;
     ClipVars cv;
-    if (dppo_check_dims(d, &D) || nets < 1 || nets > 3 || make_clip_vars(D, nets, cv)) return 0;
+    if (dppo_check_dims(d, &D) || nets < 1 || nets > 3 || !dppo_head_ok(critic_head) || !dppo_ln_ok(critic_layernorm) ||
+        make_clip_vars(D, nets, cv, critic_ln_sites(critic_head == DPPO_HEAD_PLAIN, critic_layernorm == DPPO_LN_ON)))
+        return 0;
     return (size_t)cv.cstart[cv.nv] * sizeof(double);
+}
+extern "C" size_t dppo_grad_clip_workspace_bytes(const dppo_dims* d, int nets) {
+    return dppo_grad_clip_workspace_bytes_ln(d, nets, DPPO_HEAD_RESIDUAL, DPPO_LN_OFF);
 }
 
 extern "C" int dppo_grad_clip_scales(const dppo_dims* d, int nets, const float* grads, float clip_norm, float* norms,
                                      float* scales, void* workspace, void* stream) {
+    return dppo_grad_clip_scales_ln(d, nets, DPPO_HEAD_RESIDUAL, DPPO_LN_OFF, grads, clip_norm, norms, scales, workspace,
+                                    stream);
+}
+
+// the same over the variables of a critic with the given attributes: its gamma / beta vectors follow out_b, each
+// with a norm and a scale of its own (8 + 4 residual, 8 + 6 plain)
+extern "C" int dppo_grad_clip_scales_ln(const dppo_dims* d, int nets, int critic_head, int critic_layernorm,
+                                        const float* grads, float clip_norm, float* norms, float* scales, void* workspace,
+                                        void* stream) {
     Dims D;
     int rc = dppo_check_dims(d, &D);
     if (rc) return rc;
+    DPPO_CHECK(dppo_head_ok(critic_head), "dppo_grad_clip_scales_ln: bad head %d (DPPO_HEAD_RESIDUAL or DPPO_HEAD_PLAIN)", critic_head);
+    DPPO_CHECK(dppo_ln_ok(critic_layernorm), "dppo_grad_clip_scales_ln: bad layernorm %d (DPPO_LN_OFF or DPPO_LN_ON)",
+               critic_layernorm);
     DPPO_CHECK(nets >= 1 && nets <= 3, "dppo_grad_clip_scales: nets %d outside 1..3", nets);
     DPPO_CHECK(clip_norm > 0.f && clip_norm <= 3.0e38f, "dppo_grad_clip_scales: clip_norm must be > 0 and finite");
     DPPO_CHECK(grads && scales, "dppo_grad_clip_scales: grads or scales is NULL");
     DPPO_CHECK(workspace && ((uintptr_t)workspace & 7) == 0, "dppo_grad_clip_scales: workspace must be 8-B aligned");
     DPPO_CHECK(((uintptr_t)grads & 3) == 0, "dppo_grad_clip_scales: grads must be 4-B aligned");
     ClipVars cv;
-    rc = make_clip_vars(D, nets, cv);
+    rc = make_clip_vars(D, nets, cv, critic_ln_sites(critic_head == DPPO_HEAD_PLAIN, critic_layernorm == DPPO_LN_ON));
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     unsigned* ticket = nullptr;

@@ -515,7 +515,9 @@ static int add_mlp_jobs(PackArgs& a, int in_dim, int hidden, int out_dim, int ti
     const bool main_jobs = what == PACK_ALL || what == PACK_UPDATE;
     const bool sampler_tables = split_tables && (what == PACK_ALL || what == PACK_SAMPLER || what == PACK_SAMPLER_TEMB);
     const bool temb_rows = L.temb_steps > 0 && what != PACK_UPDATE;
-    const int jobs = (main_jobs ? 11 + (actor ? 1 : 0) : 0) + (sampler_tables ? 1 : 0);
+    // a layer-normed critic image (dppo_pack_critic_ln): its gamma / beta tail, one dense fp32 copy
+    const int ln_sites = actor ? 0 : dppo_critic_ln_sites(packed);
+    const int jobs = (main_jobs ? 11 + (actor ? 1 : 0) + (ln_sites ? 1 : 0) : 0) + (sampler_tables ? 1 : 0);
     if (a.njobs + jobs > PACK_MAXJ) return dppo_set_error(DPPO_EINVAL, "pack: too many images in one launch");
     auto mat = [&](size_t src, int K, int N, bool tr, int seg) {
         PackJob& J = a.j[a.njobs++];
@@ -547,6 +549,10 @@ static int add_mlp_jobs(PackArgs& a, int in_dim, int hidden, int out_dim, int ti
         }
         mat(F.l2_w, hidden, hidden, true, SEG_T_L2);   // the actor's: the A operand of its fold (rt_fold_kernel)
         mat(F.l1_w, hidden, hidden, true, SEG_T_L1);
+        if (ln_sites) {
+            cpy(F.count, (int)critic_ln_flat_count(hidden, ln_sites), (int)(critic_ln_image_bytes(hidden, ln_sites) / 4), SEG_TIME);
+            a.j[a.njobs - 1].dst = P_out(packed) + L.total;
+        }
     }
     if (sampler_tables) {   // split sampler: W_in rows [x ; state] (skipping the TD time-embedding rows)
         mat(F.in_w, in_dim - time_dim, hidden, false, SEG_W_XS);
@@ -606,6 +612,10 @@ int dppo_fuse_jobs(int in_dim, int hidden, int out_dim, int time_dim, int precis
     job(0, F.out_w, ho, hidden, out_dim, SEG_W_OUT);
     if (!plain) job(1, F.out_w, ho, out_dim, hidden, SEG_T_OUT);
     job(2, F.out_b, out_dim, 0, 0, SEG_B_OUT);
+    if (const int ln_sites = time_dim > 0 ? 0 : dppo_critic_ln_sites(packed)) {   // the layer norms' tail, as add_mlp_jobs
+        job(2, F.count, critic_ln_flat_count(hidden, ln_sites), 0, 0, SEG_TIME);
+        if (n <= FUSE_MAXJ) jobs[n - 1].dst = P_out(packed) + L.total;
+    }
     return n <= FUSE_MAXJ ? n : -1;
 }
 
@@ -662,18 +672,19 @@ int mark_stale(const Dims& D, int precision, const float* params, const void* pa
 // non-default attribute are listed (ReLU / RESIDUAL, the defaults of an unlisted address, erase the entry),
 // keyed by the image's address like g_stale.
 namespace {
-struct ImageAttr { const void* packed; int act, head, chead; };
+struct ImageAttr { const void* packed; int act, head, chead, cln; };
 std::mutex g_attr_mu;
 std::vector<ImageAttr> g_attr;
 ImageAttr image_attr(const void* packed) {
     std::lock_guard<std::mutex> lk(g_attr_mu);
     for (const ImageAttr& e : g_attr)
         if (e.packed == packed) return e;
-    return ImageAttr{packed, DPPO_ACT_RELU, DPPO_HEAD_RESIDUAL, DPPO_HEAD_RESIDUAL};
+    return ImageAttr{packed, DPPO_ACT_RELU, DPPO_HEAD_RESIDUAL, DPPO_HEAD_RESIDUAL, DPPO_LN_OFF};
 }
 void set_image_attr(const ImageAttr& a) {
     std::lock_guard<std::mutex> lk(g_attr_mu);
-    const bool dflt = a.act == DPPO_ACT_RELU && a.head == DPPO_HEAD_RESIDUAL && a.chead == DPPO_HEAD_RESIDUAL;
+    const bool dflt = a.act == DPPO_ACT_RELU && a.head == DPPO_HEAD_RESIDUAL && a.chead == DPPO_HEAD_RESIDUAL &&
+                      a.cln == DPPO_LN_OFF;
     for (size_t i = 0; i < g_attr.size(); ++i)
         if (g_attr[i].packed == a.packed) {
             if (dflt) { g_attr[i] = g_attr.back(); g_attr.pop_back(); }
@@ -699,7 +710,7 @@ void dppo_actor_image_set_head(const void* packed, int head) {
 // pending table refresh), whatever is allocated there next
 extern "C" int dppo_forget_image(const void* packed) {
     if (!packed) return DPPO_OK;
-    set_image_attr(ImageAttr{packed, DPPO_ACT_RELU, DPPO_HEAD_RESIDUAL, DPPO_HEAD_RESIDUAL});
+    set_image_attr(ImageAttr{packed, DPPO_ACT_RELU, DPPO_HEAD_RESIDUAL, DPPO_HEAD_RESIDUAL, DPPO_LN_OFF});
     clear_stale(packed);
     return DPPO_OK;
 }
@@ -707,6 +718,13 @@ int dppo_critic_image_head(const void* packed) { return image_attr(packed).chead
 void dppo_critic_image_set_head(const void* packed, int head) {
     ImageAttr a = image_attr(packed);
     a.chead = head;
+    set_image_attr(a);
+}
+
+int dppo_critic_image_ln(const void* packed) { return image_attr(packed).cln; }
+void dppo_critic_image_set_ln(const void* packed, int layernorm) {
+    ImageAttr a = image_attr(packed);
+    a.cln = layernorm;
     set_image_attr(a);
 }
 
@@ -724,6 +742,12 @@ int dppo_pack_mlp(int in_dim, int hidden, int out_dim, int time_dim, int precisi
     rc = launch_pack(a, precision, s);
     if (rc) return rc;
     return dppo_pack_rt_fold(in_dim, hidden, out_dim, time_dim, precision, params, packed, temb_steps, time_stride, s);
+}
+
+int dppo_pack_critic_image(const Dims& D, int precision, const float* params, void* packed, hipStream_t s) {
+    PackArgs a = {};
+    const int rc = add_mlp_jobs(a, D.SD, D.HC, 1, 0, precision, params, packed, 0, 1);
+    return rc ? rc : launch_pack(a, precision, s);
 }
 
 // the row tiles' fold segments of an actor image whose W_OUT / T_L2 slots are final on stream s (after
@@ -787,8 +811,11 @@ int dppo_pack_models(const Dims& D, int precision, const float* actor_params, vo
     // networks' images fill the job table on their own (13 + 11 jobs): ranges that would not fit beside
     // the images are zeroed by a launch of their own first (the caller, staged_step, has already run
     // AdamW, so refusing here would leave stepped parameters under stale images)
-    const int img_jobs = (actor_params && packed_actor ? (defer_sampler_tables ? 12 : 13) : 0) +
-                         (critic_params && packed_critic ? 11 : 0);   // add_mlp_jobs' counts
+    const int critic_jobs = critic_params && packed_critic ? 11 + (dppo_critic_ln_sites(packed_critic) ? 1 : 0) : 0;
+    const int actor_jobs = actor_params && packed_actor ? (defer_sampler_tables ? 12 : 13) : 0;
+    const int img_jobs = actor_jobs + critic_jobs;   // add_mlp_jobs' counts
+    // a layer-normed critic's 12 jobs do not fit beside the actor's 13: its image goes in a launch of its own
+    const bool critic_alone = img_jobs > PACK_MAXJ;
     if (n_zero > 0 && n_zero + img_jobs > PACK_MAXJ) {
         PackArgs z = {};
         for (int r = 0; r < n_zero; ++r) {
@@ -814,8 +841,12 @@ int dppo_pack_models(const Dims& D, int precision, const float* actor_params, vo
         else clear_stale(packed_actor);   // a full pack makes a pending refresh moot
         if (rc) return rc;
     }
-    if (critic_params && packed_critic) {
+    if (critic_params && packed_critic && !critic_alone) {
         rc = add_mlp_jobs(a, D.SD, D.HC, 1, 0, precision, critic_params, packed_critic, 0, 1);
+        if (rc) return rc;
+    }
+    if (critic_alone) {
+        rc = dppo_pack_critic_image(D, precision, critic_params, packed_critic, s);
         if (rc) return rc;
     }
     rc = launch_pack(a, precision, s);

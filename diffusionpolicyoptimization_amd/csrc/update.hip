@@ -216,7 +216,11 @@ extern "C" int dppo_pack_all(const dppo_dims* d, int precision, const float* act
                "dppo_pack_all: a packed image needs its parameters");
     const int old_head = packed_actor ? dppo_actor_image_head(packed_actor) : DPPO_HEAD_RESIDUAL;
     if (packed_actor) dppo_actor_image_set_head(packed_actor, DPPO_HEAD_RESIDUAL);   // = dppo_pack_actor, before the pack
+    // no layer norm either (the critic's pack jobs follow it, so before the pack like the actor's head)
+    const int old_ln = packed_critic ? dppo_critic_image_ln(packed_critic) : DPPO_LN_OFF;
+    if (packed_critic) dppo_critic_image_set_ln(packed_critic, DPPO_LN_OFF);
     rc = dppo_pack_models(D, precision, actor_params, packed_actor, critic_params, packed_critic, (hipStream_t)stream);
+    if (rc != DPPO_OK && packed_critic) dppo_critic_image_set_ln(packed_critic, old_ln);
     if (rc == DPPO_OK && packed_actor) dppo_actor_image_set_act(packed_actor, DPPO_ACT_RELU);
     if (rc == DPPO_OK && packed_critic) dppo_critic_image_set_head(packed_critic, DPPO_HEAD_RESIDUAL);   // = dppo_pack_critic
     if (rc != DPPO_OK && packed_actor) dppo_actor_image_set_head(packed_actor, old_head);
@@ -282,9 +286,13 @@ enum MbPart { MB_ACTOR = 1, MB_CRITIC = 2, MB_WHOLE = 3, MB_ACTOR_TILES = 4, MB_
 // the atomically accumulated outputs a minibatch half (or the whole) zeroes first: gradients (entry
 // 0), metrics (actor: 0, 2..15; critic: 1), pl2 | bucket sums, cpl2 | stats | crow_cnt. Entries 1..3
 // are what dppo_ppo_clear_ranges reports (the gradients are cleared by the optimizer step's AdamW)
-static ZeroArgs minibatch_zero_args(const Dims& D, const PpoWorkspace& ws, float* grads, double* metrics, MbPart part) {
+// ln_sites: the norms of a layer-normed critic image, whose gradient tail (dgamma / dbeta, added by the row
+// tiles) follows the critic's eight tensors in `grads` and is zeroed with them
+static ZeroArgs minibatch_zero_args(const Dims& D, const PpoWorkspace& ws, float* grads, double* metrics, MbPart part,
+                                    int ln_sites = 0) {
     const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
-    const FlatOffsets FC = make_flat_offsets(D.SD, D.HC, 1, 0);
+    FlatOffsets FC = make_flat_offsets(D.SD, D.HC, 1, 0);
+    FC.count += critic_ln_flat_count(D.HC, ln_sites);
     ZeroArgs z = {};
     // pl2 | pa0 | gseg: the bucket rows the dW adds into, whole wave rows of 16 (K' <= 64)
     const size_t actor_acc = (size_t)((const uint8_t*)(ws.gseg + (size_t)dppo_cdiv(D.KF, 16) * 16 * D.H) - (const uint8_t*)ws.pl2);
@@ -323,6 +331,17 @@ extern "C" int dppo_ppo_clear_ranges(const dppo_dims* d, int precision, int batc
         if (z.p[r]) { ptrs[n] = z.p[r]; bytes[n] = z.n[r]; ++n; }
     *count = n;
     return DPPO_OK;
+}
+// the same for a critic with the given attributes. A layer-normed critic's dgamma / dbeta are accumulated in the
+// gradient buffer's tail, which DPPO_STEP_CLEAR_GRADS clears with the range it steps: the ranges reported here
+// (metrics and workspace accumulators) are the same ones
+extern "C" int dppo_ppo_clear_ranges_ln(const dppo_dims* d, int precision, int critic_head, int critic_layernorm,
+                                        int batch_rows, void* workspace, double* metrics, int part, void** ptrs,
+                                        size_t* bytes, int* count) {
+    DPPO_CHECK(dppo_head_ok(critic_head), "dppo_ppo_clear_ranges_ln: bad head %d (DPPO_HEAD_RESIDUAL or DPPO_HEAD_PLAIN)", critic_head);
+    DPPO_CHECK(dppo_ln_ok(critic_layernorm), "dppo_ppo_clear_ranges_ln: bad layernorm %d (DPPO_LN_OFF or DPPO_LN_ON)",
+               critic_layernorm);
+    return dppo_ppo_clear_ranges(d, precision, batch_rows, workspace, metrics, part, ptrs, bytes, count);
 }
 
 // The weight gradients of one network are one grouped dW launch. No m-chunk under 768 rows in the PPO
@@ -462,6 +481,7 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     const bool plain = dppo_actor_image_head(m.packed_ft) == DPPO_HEAD_PLAIN;   // no l2: nothing to defer
     const bool l2_def = (hp->flags & DPPO_PPO_L2_DEFERRED) != 0 && !plain;
     const bool cplain = dppo_critic_image_head(m.packed_critic) == DPPO_HEAD_PLAIN;
+    const int cln_sites = dppo_critic_ln_sites(m.packed_critic);   // > 0: the critic's gradients end in the norms' tail
 
     ActorArgs aa = {};
     aa.packed = (const uint8_t*)m.packed_ft;
@@ -477,6 +497,8 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     ca.obs = m.obs; ca.SD = D.SD; ca.HC = D.HC; ca.KF = D.KF; ca.mode = ROWS_TRAIN; ca.nrows = rows;
     ca.fk = fk; ca.start = m.start; ca.row_index = m.row_index; ca.returns = m.returns; ca.hp = lh; ca.ws = ws;
     ca.metrics = m.metrics;
+    ca.gln = cln_sites ? gc + make_flat_offsets(D.SD, D.HC, 1, 0).count : nullptr;
+    ca.ln_unscale = 1.f / gscale;
 
     // Every row tile this part runs must have an instantiation before anything is launched: a geometry
     // the dispatch rejects leaves the gradients, the metrics and the stream's sample counts (which the
@@ -500,7 +522,7 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     // MB_ACTOR_TILES zeroed its outputs
     if (part != MB_ACTOR_DW && !(hp->flags & DPPO_PPO_PRECLEARED)) {
         DppoKtScope kt(KT_ZERO, s);
-        rc = launch_zero(minibatch_zero_args(D, ws, m.grads, m.metrics, part), 16, s);
+        rc = launch_zero(minibatch_zero_args(D, ws, m.grads, m.metrics, part, cln_sites), 16, s);
         if (rc) return rc;
     }
     const double* stats = m.adv_stats;

@@ -55,7 +55,8 @@ class VPGDiffusion(DiffusionModel):
                                   actor_hidden=actor.hidden, critic_hidden=critic.hidden,
                                   denoising_steps=self.sampling_steps, ft_denoising_steps=self.ft_denoising_steps,
                                   time_stride=self.time_stride, activation=actor.activation_type, head=actor.head,
-                                  critic_head=getattr(critic, "head", "residual"))
+                                  critic_head=getattr(critic, "head", "residual"),
+                                  critic_layernorm=bool(getattr(critic, "use_layernorm", False)))
         self.actor_spec = ops.actor_param_spec(self.dims)
         self.critic_spec = ops.critic_param_spec(self.dims)
         self.n_actor = ops.spec_count(self.actor_spec)
@@ -197,7 +198,11 @@ class VPGDiffusion(DiffusionModel):
     def save_weights(self, path):
         """PPODiffusion.save_weights: a Keras-3 weights file for *.h5 (actor/, actor_ft/, critic/;
         agent/finetune/train_agent.py:127-133), else .npz with actor./actor_ft./critic. keys. A
-        learn_eta model also saves its eta (eta/ group, or eta.state / eta.step keys)."""
+        learn_eta model also saves its eta (eta/ group, or eta.state / eta.step keys). A layer-normed critic's
+        gamma / beta go into the .npz under the spec's names (critic.ln1_g, critic.ln1_b, ...) and into a Keras .h5 file
+        as vars/0 (gamma) and vars/1 (beta) of each LayerNormalization (util/keras_weights.critic_paths: mapped, not
+        refused; like the plain MLP's paths the naming is not pinned by a file Keras wrote). Loading either kind
+        refuses a file whose layer-norm tensors are not the configured critic's, in both directions."""
         eta = self._eta_checkpoint()
         if str(path).endswith(".h5"):
             sp = lambda spec, flat: ops.unflatten_params(spec, flat.detach().cpu().numpy())
@@ -236,6 +241,7 @@ class VPGDiffusion(DiffusionModel):
             ops.check_checkpoint_head(f.files, self.actor_spec, path, "actor_ft.")
             ops.check_checkpoint_critic_head(f.files, self.dims.critic_head, path,
                                              f[ops.CRITIC_HEAD_KEY] if ops.CRITIC_HEAD_KEY in f.files else None)
+            ops.check_checkpoint_critic_layernorm(f.files, self.critic_spec, path)
             for prefix, flat, spec in (("actor.", self.base_params, self.actor_spec),
                                        ("actor_ft.", self.actor_ft_params, self.actor_spec),
                                        ("critic.", self.critic_params, self.critic_spec)):

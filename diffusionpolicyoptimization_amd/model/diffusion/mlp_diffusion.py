@@ -17,6 +17,8 @@ class DiffusionMLP:
             raise NotImplementedError("cond_mlp_dims (obs encoder) is not used by the gym fine-tune cfgs")
         if activation_type not in ("ReLU", "Mish"):
             raise NotImplementedError(f"activation_type {activation_type!r}: the actor kernels implement ReLU and Mish")
+        if use_layernorm:   # the critic's kernels have the norm (CriticObs); the actor's folded image does not
+            raise NotImplementedError("DiffusionMLP(use_layernorm=True): layer normalisation is implemented for the critic only")
         self.action_dim, self.horizon_steps, self.cond_dim, self.time_dim = action_dim, horizon_steps, cond_dim, time_dim
         self.mlp_dims = list(mlp_dims)
         self.activation_type = activation_type

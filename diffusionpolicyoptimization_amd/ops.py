@@ -42,6 +42,10 @@ class ModelDims:
     # Python-only: pack_critic records it with the critic image (dppo_pack_critic_head). Layout, spec and image
     # bytes are the same for both
     critic_head: str = "residual"
+    # the critic's layer normalisation (CriticObs use_layernorm), Python-only like critic_head: pack_critic records it
+    # with the critic image (dppo_pack_critic_ln). Unlike the head it lengthens the critic's spec, flat layout and
+    # image by the norms' gamma / beta tail (critic_param_spec); every other offset keeps its value
+    critic_layernorm: bool = False
 
     def __post_init__(self):
         if self.activation not in _lib.ACTIVATION:
@@ -50,6 +54,8 @@ class ModelDims:
             raise ValueError(f"head must be one of {sorted(_lib.HEAD)}, got {self.head!r}")
         if self.critic_head not in _lib.HEAD:
             raise ValueError(f"critic_head must be one of {sorted(_lib.HEAD)}, got {self.critic_head!r}")
+        if not isinstance(self.critic_layernorm, bool):
+            raise ValueError(f"critic_layernorm must be a bool, got {self.critic_layernorm!r}")
 
     @property
     def xd(self):
@@ -95,10 +101,21 @@ def actor_param_spec(d: ModelDims):
     return ParamSpec([(n, s) for n, s in full if n not in ("l2_w", "l2_b")], offsets, o)
 
 
+def critic_ln_sites(d: ModelDims):
+    """The norms of the critic: one per hidden layer of the plain head, the residual block's two, none without
+    layer norm."""
+    return (3 if d.critic_head == "plain" else 2) if d.critic_layernorm else 0
+
+
 def critic_param_spec(d: ModelDims):
+    """The critic's eight tensors, then the tail of a layer-normed critic: ln1_g, ln1_b, ln2_g, ln2_b (and ln3_g,
+    ln3_b for the plain head), each [critic_hidden] (include/dppo.h dppo_pack_critic_ln)."""
     h = d.critic_hidden
-    return [("in_w", (d.sd, h)), ("in_b", (h,)), ("l1_w", (h, h)), ("l1_b", (h,)),
+    spec = [("in_w", (d.sd, h)), ("in_b", (h,)), ("l1_w", (h, h)), ("l1_b", (h,)),
             ("l2_w", (h, h)), ("l2_b", (h,)), ("out_w", (h, 1)), ("out_b", (1,))]
+    for k in range(1, critic_ln_sites(d) + 1):
+        spec += [(f"ln{k}_g", (h,)), (f"ln{k}_b", (h,))]
+    return spec
 
 
 def spec_ranges(spec):
@@ -136,7 +153,8 @@ def _n_params(d):
 @functools.lru_cache(maxsize=None)
 def _packed_bytes(d, prec):
     return (int(_lib.query("dppo_actor_packed_bytes", ctypes.byref(_dims_c(d)), prec)),
-            int(_lib.query("dppo_critic_packed_bytes", ctypes.byref(_dims_c(d)), prec)))
+            int(_lib.query("dppo_critic_packed_bytes_ln", ctypes.byref(_dims_c(d)), prec, _lib.HEAD[d.critic_head],
+                           _lib.LAYERNORM[d.critic_layernorm])))
 
 
 @functools.lru_cache(maxsize=None)
@@ -179,6 +197,21 @@ def check_checkpoint_critic_head(names, head, path, file_head=None):
     has = (str(file_head) if file_head is not None else "plain") if CRITIC_HEAD_KEY in names else "residual"
     if has != head:
         raise ValueError(f"{path}: the checkpoint holds a {has} critic, the model is {head}")
+
+
+def check_checkpoint_critic_layernorm(names, spec, path, prefix="critic."):
+    """A .npz checkpoint's critic must hold exactly the model's layer-norm tensors (ln{k}_g / ln{k}_b of the spec): a
+    file with norms the configured critic lacks (or with another head's count of them) and a file without the norms
+    the configured critic has are both refused. A file without a critic passes."""
+    names = set(names)
+    if not any(n.startswith(prefix) for n in names):
+        return
+    is_ln = lambda n: n.startswith("ln") and n[-2:] in ("_g", "_b")
+    has = sorted(n[len(prefix):] for n in names if n.startswith(prefix) and is_ln(n[len(prefix):]))
+    wants = sorted(n for n, _ in spec if is_ln(n))
+    if has != wants:
+        kind = lambda v: f"a layer-normed critic ({', '.join(v)})" if v else "a critic without layer norm"
+        raise ValueError(f"{path}: the checkpoint holds {kind(has)}, the model is {kind(wants)}")
 
 
 def _check(t, shape, dtype, name):
@@ -242,8 +275,9 @@ def pack_all(d: ModelDims, precision, actor_params=None, packed_actor=None, crit
         if critic_params is not None:
             pack_critic(d, critic_params, precision, out=packed_critic)
         return
-    if critic_params is not None and d.critic_head != "residual":
-        # dppo_pack_all records RESIDUAL for the critic image too (= dppo_pack_critic): a plain critic packs on its own
+    if critic_params is not None and (d.critic_head != "residual" or d.critic_layernorm):
+        # dppo_pack_all records RESIDUAL / no layer norm for the critic image too (= dppo_pack_critic): a plain or
+        # layer-normed critic packs on its own
         if actor_params is not None:
             pack_actor(d, actor_params, precision, out=packed_actor)
         pack_critic(d, critic_params, precision, out=packed_critic)
@@ -280,22 +314,32 @@ def optimizer_step(d: ModelDims, precision, params, grads, m, v, step, lr, weigh
                   _clip_nets(d, n, clip_scales))
 
 
-_NET_VARS = {_lib.DPPO_NET_ACTOR: 12, _lib.DPPO_NET_CRITIC: 8, _lib.DPPO_NET_ACTOR | _lib.DPPO_NET_CRITIC: 20}
+def _net_vars(d):
+    """Variables per DPPO_NET_* value: 12 actor, 8 critic plus the layer-norm tail's vectors, and both."""
+    nc = 8 + 2 * critic_ln_sites(d)
+    return {_lib.DPPO_NET_ACTOR: 12, _lib.DPPO_NET_CRITIC: nc, _lib.DPPO_NET_ACTOR | _lib.DPPO_NET_CRITIC: 12 + nc}
+
+
 _NET_NAMES = {"actor": _lib.DPPO_NET_ACTOR, "critic": _lib.DPPO_NET_CRITIC, "both": 3}
 
 
 def _clip_nets(d, n, clip_scales):
     """The DPPO_NET_* value of a clipped step from its scale table's length (12 actor, 8 critic, 20
-    both); the library checks the range against it."""
+    both; a layer-normed critic has 4 or 6 more); the library checks the range against it."""
     _check(clip_scales, (clip_scales.numel(),), torch.float32, "clip_scales")
-    for nets, nv in _NET_VARS.items():
+    nvs = _net_vars(d)
+    if nvs[1] == nvs[2]:   # a 12-variable critic: the range's length tells it from the actor
+        nvs = {nets: nv for nets, nv in nvs.items() if nets == 3 or n == _n_params(d)[nets - 1]}
+    for nets, nv in nvs.items():
         if clip_scales.numel() == nv:
             return nets
-    raise ValueError(f"clip_scales: expected 12 (actor), 8 (critic) or 20 (both) entries, got {clip_scales.numel()}")
+    raise ValueError(f"clip_scales: expected {_net_vars(d)[1]} (actor), {_net_vars(d)[2]} (critic) or {_net_vars(d)[3]} (both) "
+                     f"entries, got {clip_scales.numel()}")
 
 
 def grad_clip_workspace_bytes(d: ModelDims, nets):
-    return int(_lib.query("dppo_grad_clip_workspace_bytes", ctypes.byref(_dims_c(d)), int(_NET_NAMES.get(nets, nets))))
+    return int(_lib.query("dppo_grad_clip_workspace_bytes_ln", ctypes.byref(_dims_c(d)), int(_NET_NAMES.get(nets, nets)),
+                          _lib.HEAD[d.critic_head], _lib.LAYERNORM[d.critic_layernorm]))
 
 
 class BoundGradClip:
@@ -306,11 +350,11 @@ class BoundGradClip:
 
     def __init__(self, d: ModelDims, nets, grads, clip_norm, norms=None, scales=None, workspace=None):
         nets = int(_NET_NAMES.get(nets, nets))
-        if nets not in _NET_VARS:
+        if nets not in _net_vars(d):
             raise ValueError(f"nets: expected 1 (actor), 2 (critic) or 3 (both), got {nets}")
         na, nc = _n_params(d)
         n = (na if nets & 1 else 0) + (nc if nets & 2 else 0)
-        nv = _NET_VARS[nets]
+        nv = _net_vars(d)[nets]
         _check(grads, (n,), torch.float32, "grads")
         dev = grads.device
         if norms is None:
@@ -330,12 +374,13 @@ class BoundGradClip:
             raise ValueError("clip_norm must be > 0")
         self.nets, self.norms, self.scales, self.workspace = nets, norms, scales, workspace
         self._lib = _lib.load()
-        self._args = (ctypes.byref(_dims_c(d)), nets, ptr(grads), float(clip_norm), ptr(norms), ptr(scales), ptr(workspace))
+        self._args = (ctypes.byref(_dims_c(d)), nets, _lib.HEAD[d.critic_head], _lib.LAYERNORM[d.critic_layernorm],
+                      ptr(grads), float(clip_norm), ptr(norms), ptr(scales), ptr(workspace))
         self._dev = dev
         self._keep = (grads,)
 
     def __call__(self, stream=None):
-        _lib.check(self._lib.dppo_grad_clip_scales(*self._args, stream_handle(self._dev) if stream is None else stream),
+        _lib.check(self._lib.dppo_grad_clip_scales_ln(*self._args, stream_handle(self._dev) if stream is None else stream),
                    "dppo_grad_clip_scales")
         return self.scales
 
@@ -502,16 +547,17 @@ def pack_actor(d: ModelDims, params_flat, precision, out=None):
 
 
 def pack_critic(d: ModelDims, params_flat, precision, out=None):
-    """The packed image of a critic; d.critic_head is recorded with it (dppo_pack_critic_head) and decides which
-    row tile and weight-gradient problems every later launch on the image runs."""
+    """The packed image of a critic; d.critic_head and d.critic_layernorm are recorded with it (dppo_pack_critic_ln)
+    and decide which row tile and weight-gradient problems every later launch on the image runs, and whether the
+    parameters and the image end in the norms' gamma / beta tail."""
     p = _prec(precision)
     _check(params_flat, (_n_params(d)[1],), torch.float32, "critic params")
     if out is None:
         out = torch.empty(_packed_bytes(d, p)[1], dtype=torch.uint8, device=params_flat.device)
     else:
         _check(out, (_packed_bytes(d, p)[1],), torch.uint8, "packed critic")
-    _lib.call("dppo_pack_critic_head", ctypes.byref(_dims_c(d)), p, _lib.HEAD[d.critic_head], ptr(params_flat), ptr(out),
-              stream_handle(params_flat.device))
+    _lib.call("dppo_pack_critic_ln", ctypes.byref(_dims_c(d)), p, _lib.HEAD[d.critic_head],
+              _lib.LAYERNORM[d.critic_layernorm], ptr(params_flat), ptr(out), stream_handle(params_flat.device))
     _forget_on_free(out)
     return out
 
@@ -936,12 +982,22 @@ def ppo_plan(d: ModelDims, precision, rows, mode="train"):
     dw_chunks_actor, dw_chunk_rows_actor, dw_chunks_critic, dw_chunk_rows_critic). mode: "train"
     (ppo_minibatch), "pretrain" (pretrain_minibatch) or "logprob" (rows = samples x K'); the dW fields
     are 0 where the mode has no such launch. The plan is d.activation's (dppo_ppo_plan_act): a Mish actor
-    runs the 32-row tile on 8 waves at every row count."""
+    runs the 32-row tile on 8 waves at every row count. The critic's row tile: ppo_plan_critic."""
     out = (ctypes.c_int * 6)()
     _lib.call("dppo_ppo_plan_act", ctypes.byref(d.c()), _prec(precision), _lib.ACTIVATION[d.activation], int(rows),
               _PLAN_MODES[mode], out)
     return dict(actor_tile_rows=out[0], actor_waves=out[1], dw_chunks_actor=out[2], dw_chunk_rows_actor=out[3],
                 dw_chunks_critic=out[4], dw_chunk_rows_critic=out[5])
+
+
+def ppo_plan_critic(d: ModelDims, precision):
+    """The critic's row tile for d.critic_head / d.critic_layernorm (dppo_ppo_plan_critic): dict(critic_tile_rows,
+    critic_waves, critic_tile_capped). capped = the 128-register kernel entry (two tiles per CU), which every critic
+    without layer norm runs and a layer-normed one does not."""
+    c = (ctypes.c_int * 3)()
+    _lib.call("dppo_ppo_plan_critic", ctypes.byref(d.c()), _prec(precision), _lib.HEAD[d.critic_head],
+              _lib.LAYERNORM[d.critic_layernorm], c)
+    return dict(critic_tile_rows=c[0], critic_waves=c[1], critic_tile_capped=bool(c[2]))
 
 
 def ppo_adv_stats(advantages, total, kf, perm_seed, epoch, start, rows, out, row_index=None):
@@ -1142,8 +1198,9 @@ class ClearRanges:
         self._ptrs = (ctypes.c_void_p * 4)()
         self._bytes = (ctypes.c_size_t * 4)()
         cnt = ctypes.c_int(0)
-        _lib.check(lib.dppo_ppo_clear_ranges(ctypes.byref(_dims_c(d)), _prec(precision), int(rows), ptr(workspace),
-                                             _address(metrics), int(part), self._ptrs, self._bytes, ctypes.byref(cnt)),
+        _lib.check(lib.dppo_ppo_clear_ranges_ln(ctypes.byref(_dims_c(d)), _prec(precision), _lib.HEAD[d.critic_head],
+                                                _lib.LAYERNORM[d.critic_layernorm], int(rows), ptr(workspace),
+                                                _address(metrics), int(part), self._ptrs, self._bytes, ctypes.byref(cnt)),
                    "dppo_ppo_clear_ranges")
         self.count = cnt.value
         self.args = (self._ptrs, self._bytes, self.count)

@@ -70,10 +70,25 @@ def actor_paths(prefix="", plain=False):
     return out
 
 
-def critic_paths(prefix="", plain=False):
+def _ln_sites(names):
+    """The norms of a critic from its tensor names (ln{k}_g / ln{k}_b, ops.critic_param_spec)."""
+    return len([n for n in names if re.fullmatch(r"ln\d+_g", n)])
+
+
+def critic_paths(prefix="", plain=False, ln_sites=0):
+    """flat-spec name -> dataset path (ops.critic_param_spec names). ln_sites: the norms of a layer-normed critic,
+    gamma = vars/0 and beta = vars/1 of each LayerNormalization: the plain MLP's sits in each hidden layer's
+    Sequential beside its Dense, the residual block's are its norm1 / norm2 (model/common/mlp.py:62-78, 174-176;
+    naming unpinned like the plain paths, module docstring)."""
     out = {}
     for k, v in (_plain_critic_paths if plain else _dense_paths)(prefix + "Q1/").items():
         out[f"{k}_w"], out[f"{k}_b"] = v + "/vars/0", v + "/vars/1"
+    for k in range(1, ln_sites + 1):
+        if plain:
+            v = f"{prefix}Q1/module_list/sequential{'_%d' % (k - 1) if k > 1 else ''}/layers/layer_normalization"
+        else:
+            v = f"{prefix}Q1/residual_blocks/{BLOCK}/norm{k}"
+        out[f"ln{k}_g"], out[f"ln{k}_b"] = v + "/vars/0", v + "/vars/1"
     return out
 
 
@@ -186,7 +201,9 @@ def check_critic_head(data, plain, path, prefix="critic/"):
 def load_ppo_model(path, actor_spec, critic_spec, critic_plain=False):
     """{"actor", "actor_ft", "critic"} dicts from a fine-tune checkpoint (PPODiffusion.save_weights),
     plus "eta" = {"logit", "m", "v", "step"} when the model learned eta. critic_plain: the model's critic is
-    the plain MLP (CriticObs residual_style=False)."""
+    the plain MLP (CriticObs residual_style=False). A layer-normed critic (critic_spec with ln{k}_g / ln{k}_b) reads
+    its gamma / beta from the LayerNormalization paths of critic_paths; a file whose norms are not the spec's is
+    refused: norms the model lacks are unused datasets, norms the file lacks are missing variables."""
     data = read_h5(path)
     check_critic_head(data, critic_plain, path)
     out = {}
@@ -199,7 +216,7 @@ def load_ppo_model(path, actor_spec, critic_spec, critic_plain=False):
     plain = _is_plain(n for n, _ in actor_spec)
     for key, paths, spec in (("actor", actor_paths("actor/", plain), actor_spec),
                              ("actor_ft", actor_paths("actor_ft/", plain), actor_spec),
-                             ("critic", critic_paths("critic/", critic_plain), critic_spec)):
+                             ("critic", critic_paths("critic/", critic_plain, _ln_sites(n for n, _ in critic_spec)), critic_spec)):
         got, missing = _resolve(data, paths, used)
         if missing:
             raise ValueError(f"{path}: missing {key} variables: {missing}")
@@ -243,7 +260,7 @@ def save_ppo_model(path, actor, actor_ft, critic, eta=None, critic_plain=False):
     plain = _is_plain(actor)
     for prefix, params, paths in (("actor/", actor, actor_paths("actor/", plain)),
                                   ("actor_ft/", actor_ft, actor_paths("actor_ft/", plain)),
-                                  ("critic/", critic, critic_paths("critic/", critic_plain))):
+                                  ("critic/", critic, critic_paths("critic/", critic_plain, _ln_sites(critic)))):
         for k, v in params.items():
             d[paths[k]] = np.asarray(v, np.float32)
     groups = ["vars"] + _empty_groups("actor/", "actor", plain) + _empty_groups("actor_ft/", "actor", plain) + \

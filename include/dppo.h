@@ -217,11 +217,55 @@ DPPO_API int dppo_pack_actor_head(const dppo_dims* d, int precision, int activat
  * the factored form through the out layer; the critic's last launch then only re-zeroes the stream's sample counts. */
 DPPO_API int dppo_pack_critic_head(const dppo_dims* d, int precision, int head, const float* params, void* packed,
                                    void* stream);
+/* The critic's layer normalisation (CriticObs use_layernorm, model/common/critic.py:15-38; mlp.py:64-66, 174-176,
+ * 190-202), the critic image's SECOND attribute, recorded like the head (an addition within ABI 15). With
+ * DPPO_LN_ON every hidden Dense is followed by Keras' LayerNormalization before its Mish: over the last axis,
+ * population variance, y = gamma (h - mean) rsqrt(var + eps) + beta:
+ *     plain:     y_k = LN_k(h_k), u_k = mish(y_k), k = 1..3;  V = out(u3);            eps = 1e-3 (Keras' default)
+ *     residual:  h1 = in(s); u1 = mish(LN_1(h1)); h2 = l1(u1); u2 = mish(LN_2(h2)); h3 = l2(u2) + h1; V = out(h3);
+ *                eps = 1e-6; the skip carries the un-normalised h1
+ * (no norm on the output layer). The statistics are fp32 from the fp32 accumulators at every precision; only the
+ * operands of the next product are rounded to the 2-byte type.
+ * Unlike the head this attribute LENGTHENS the critic's flat layout and image by a tail; every existing offset keeps
+ * its value (the actor's, the critic's eight tensors, and the actor | critic concatenation in `grads`, where the
+ * critic comes last):
+ *   flat   ... out_b | ln1_g ln1_b ln2_g ln2_b (residual) | ln3_g ln3_b (plain too), each [critic_hidden] fp32;
+ *          gamma is created as ones, beta as zeros
+ *   image  the same vectors, fp32 and dense, in one segment behind the image's present ones (at
+ *          dppo_critic_packed_bytes); the leading bytes equal those of a pack of the same eight tensors
+ * dppo_critic_param_count_ln / dppo_critic_packed_bytes_ln give the sizes (0 for an attribute outside its enum);
+ * with DPPO_LN_OFF they are dppo_critic_param_count / dppo_critic_packed_bytes for both heads.
+ * dppo_pack_critic_ln packs like dppo_pack_critic_head and records both attributes; dppo_pack_critic,
+ * dppo_pack_critic_head and dppo_pack_all record DPPO_LN_OFF; dppo_forget_image clears it; the optimizer steps
+ * leave it alone. An attribute outside its enum is DPPO_EINVAL, nothing enqueued, the image's attributes kept.
+ * Entries that receive the critic image read the attribute and use the longer layout: dppo_critic_forward,
+ * dppo_ppo_minibatch{,_part} (the critic's gradients end in dln1_g, dln1_b, ...: the row tiles add each tile's
+ * column sums into that tail with fp32 atomics, and the minibatch's zeroing launch covers it), and
+ * dppo_optimizer_step{,_ex,_clip}: a staged step packs the tail, DPPO_STEP_FUSED_PACK steps a critic range of
+ * dppo_critic_param_count_ln elements in one launch, DPPO_STEP_CLEAR_GRADS clears the range it steps, tail included.
+ * gamma and beta are variables like any bias: AdamW with weight decay (Keras decays every variable), a clip norm
+ * and scale each (8 + 4 or 8 + 6 critic variables, in layout order), part of the data-parallel bucket.
+ * What an entry can see of a buffer sized for the other layout it refuses with DPPO_EINVAL before anything is
+ * enqueued: an optimizer range that holds fewer elements from critic_params on than the layer-normed image's layout
+ * ("... buffers sized for the layout without the tail"), a critic-only range of a layer-normed length on an image
+ * without layer norm, a clipped range that is not exactly the networks' layouts. Raw device pointers carry no
+ * size, so the Python package checks every tensor against the spec (ops.py).
+ * Entries that see only dppo_dims have _ln forms that take the two attributes (dppo_grad_clip_workspace_bytes_ln,
+ * dppo_grad_clip_scales_ln, dppo_ppo_clear_ranges_ln); the old forms keep their meaning exactly (no layer norm).
+ * The supported-geometry table of the update entries above applies to a layer-normed critic line for line, with
+ * the same messages (critic_hidden 256; cond_steps*obs_dim <= 32 in fp32, <= 64 in bf16 / fp16): the norm adds
+ * 8,704 B (residual) or 11,008 B (plain) of LDS to the 32-row tile and no geometry-dependent limit. The layer-normed tile runs the plain 8-wave
+ * kernel form, not the 128-register one (dppo_ppo_plan_critic reports it). tests/test_critic_layernorm_gpu.py pins this. */
+enum { DPPO_LN_OFF = 0, DPPO_LN_ON = 1 };
+DPPO_API size_t dppo_critic_param_count_ln(const dppo_dims* d, int head, int layernorm);
+DPPO_API size_t dppo_critic_packed_bytes_ln(const dppo_dims* d, int precision, int head, int layernorm);
+DPPO_API int dppo_pack_critic_ln(const dppo_dims* d, int precision, int head, int layernorm, const float* params,
+                                 void* packed, void* stream);
 /* The attributes above (an actor image's activation and head, a critic image's head) live in a host table keyed
  * by the image's ADDRESS, so they outlive the buffer: memory allocated at the same address later (a copy of an
  * image, which was never packed through these entries, for one) would read the old owner's attributes instead of
  * the defaults. A caller that releases an image buffer whose attributes are not the defaults calls
- * dppo_forget_image first: the address then reads as never packed (ReLU / RESIDUAL / RESIDUAL, no pending
+ * dppo_forget_image first: the address then reads as never packed (ReLU / RESIDUAL / RESIDUAL / LN_OFF, no pending
  * sampler-table refresh). Host-only, no launch; NULL is accepted (an addition within ABI 15). The Python package
  * does this when an image tensor it packed is freed (ops.pack_actor / ops.pack_critic). */
 DPPO_API int dppo_forget_image(const void* packed);
@@ -503,6 +547,12 @@ DPPO_API int dppo_ppo_plan(const dppo_dims* d, int precision, int rows, int mode
 /* the same for an actor image of the given activation (DPPO_ACT_*; dppo_ppo_plan is the ReLU plan): a
  * Mish actor runs the 32-row tile on 8 waves at every row count (the table above) */
 DPPO_API int dppo_ppo_plan_act(const dppo_dims* d, int precision, int activation, int rows, int mode, int* out);
+/* The critic's row tile for an image of the given attributes (dppo_pack_critic_ln), which the six outputs above have
+ * no field for; host arithmetic, no image, no device work (an addition within ABI 15). out[3] = {the tile's rows (32),
+ * its waves per workgroup (8), 1 if it runs the 128-register kernel entry (two tiles per CU: every critic without
+ * layer norm) or 0 if the uncapped one (a layer-normed critic, whose TRAIN tile needs 223-253 registers)}. An
+ * attribute outside its enum is DPPO_EINVAL. */
+DPPO_API int dppo_ppo_plan_critic(const dppo_dims* d, int precision, int critic_head, int critic_layernorm, int* out);
 DPPO_API int dppo_ppo_adv_stats(const float* advantages, int64_t total, int K_ft, uint64_t perm_seed, int epoch,
                        int64_t start, int rows, const int64_t* row_index, double* adv_stats, void* stream);
 /* The adv_stats of every minibatch of an update phase in one launch: minibatch m = e * n_batch + b
@@ -549,6 +599,12 @@ DPPO_API int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const vo
  * minibatch with DPPO_PPO_PRECLEARED. */
 DPPO_API int dppo_ppo_clear_ranges(const dppo_dims* d, int precision, int batch_rows, void* workspace, double* metrics,
                                    int part, void** ptrs, size_t* bytes, int* count);
+/* The same for a critic with the given attributes (dppo_pack_critic_ln). A layer-normed critic's dgamma / dbeta
+ * are accumulated in the tail of the gradient range, which the step's DPPO_STEP_CLEAR_GRADS clears with the range
+ * it steps, so the ranges reported are dppo_ppo_clear_ranges'; an attribute outside its enum is DPPO_EINVAL. */
+DPPO_API int dppo_ppo_clear_ranges_ln(const dppo_dims* d, int precision, int critic_head, int critic_layernorm,
+                                      int batch_rows, void* workspace, double* metrics, int part, void** ptrs,
+                                      size_t* bytes, int* count);
 DPPO_API int dppo_ppo_minibatch_part(const dppo_dims* d, int precision, const dppo_ppo_hparams* hp,
                             const void* packed_ft, const void* packed_critic, const float* actor_params,
                             const float* sched, const float* obs, const float* chains, const float* lp_old_mean,
@@ -637,6 +693,13 @@ enum { DPPO_NET_ACTOR = 1, DPPO_NET_CRITIC = 2 };
 DPPO_API size_t dppo_grad_clip_workspace_bytes(const dppo_dims* d, int nets);
 DPPO_API int dppo_grad_clip_scales(const dppo_dims* d, int nets, const float* grads, float clip_norm, float* norms,
                                    float* scales, void* workspace, void* stream);
+/* The same over a critic with the given attributes (dppo_pack_critic_ln): a layer-normed critic's gamma / beta
+ * vectors are variables of their own behind out_b (8 + 4 residual, 8 + 6 plain: 12 or 14 critic entries, 24 or 26
+ * with the actor). The forms above are these with DPPO_HEAD_RESIDUAL, DPPO_LN_OFF. */
+DPPO_API size_t dppo_grad_clip_workspace_bytes_ln(const dppo_dims* d, int nets, int critic_head, int critic_layernorm);
+DPPO_API int dppo_grad_clip_scales_ln(const dppo_dims* d, int nets, int critic_head, int critic_layernorm,
+                                      const float* grads, float clip_norm, float* norms, float* scales, void* workspace,
+                                      void* stream);
 /* dppo_optimizer_step_ex whose AdamW reads each gradient as the fp32 product g[i] * clip_scales[v]
  * (rounded once, before any moment update: the step equals multiplying the gradients by the expanded
  * scale table and running dppo_optimizer_step_ex, bit for bit). clip_scales is device fp32, one per
@@ -644,7 +707,12 @@ DPPO_API int dppo_grad_clip_scales(const dppo_dims* d, int nets, const float* gr
  * host); the range must be exactly the actor, the critic or [actor | critic], as nets says. Every path
  * (staged, DPPO_STEP_FUSED_PACK, DPPO_STEP_CLEAR_GRADS, the clear ranges, the metrics copy and its tag)
  * behaves as in dppo_optimizer_step_ex. DPPO_STEP_L2_FROM_PL2 is refused (DPPO_EINVAL): the factored l2
- * gradient has no norm before it is formed. */
+ * gradient has no norm before it is formed.
+ * The critic's variables follow its image's attributes (8, or 12 / 14 for a layer-normed critic, dppo_pack_critic_ln).
+ * Without a critic image (packed_critic NULL: a step that packs nothing) there is no attribute to read, and the
+ * layout is told by n: a critic part of 8-tensor length plus 4 or 6 vectors of critic_hidden is taken as the
+ * layer-normed residual or plain layout (the three lengths differ at every accepted geometry), any other length must
+ * be the 8-tensor layout's. clip_scales must hold that layout's entries. */
 DPPO_API int dppo_optimizer_step_clip(const dppo_dims* d, int precision, float* params, float* grads, float* m,
                            float* v, int64_t n, int64_t step, float lr, float weight_decay, float beta1,
                            float beta2, float eps, int mode, const float* actor_params, void* packed_actor,

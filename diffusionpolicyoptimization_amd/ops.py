@@ -1220,7 +1220,9 @@ def q_sched_table(schedule):
 def pretrain_minibatch(d: ModelDims, precision, packed_actor, actor_params, sched, qsched, x_start, cond, t, noise,
                        workspace, grads, metrics, global_rows=None, loss_scale=1.0):
     """p_losses (diffusion.py:186-194) and its actor gradient for one batch; see include/dppo.h.
-    Returns the loss as a device scalar (metrics[0] / (global_rows * xd) * loss_scale)."""
+    Returns the loss as a device scalar (metrics[0] / (global_rows * xd) * loss_scale).
+    The workspace may hold any bytes; all 16 metrics are zeroed first; grads beyond the actor's count are not
+    touched; t is not validated (a value outside [0, denoising_steps) is the caller's error)."""
     n = x_start.shape[0]
     g = n if global_rows is None else int(global_rows)
     _check(x_start, (n, d.xd), torch.float32, "x_start")

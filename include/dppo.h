@@ -579,7 +579,14 @@ DPPO_API int dppo_ppo_minibatch(const dppo_dims* d, int precision, const dppo_pp
  * loss = loss_scale * sum((eps - noise)^2) / (global_rows * horizon*action_dim): metrics[0] (fp64,
  * device) receives the local sum of squares; grads [actor_count] fp32 are OVERWRITTEN with
  * d loss / d params. Workspace: dppo_ppo_workspace_bytes(d, precision, rows). Requires
- * time_stride == 1 and denoising_steps <= 64. ---- */
+ * time_stride == 1 and denoising_steps <= 64 (each a DPPO_EINVAL with its own message, as is
+ * global_rows < rows: "bad rows / global_rows"; outputs untouched).
+ * Buffers: the workspace need not be initialised and may hold any bytes (NaN patterns, or an earlier,
+ * larger batch's images under another row padding: the entry writes every byte it later reads). All 16
+ * metric slots are zeroed before metrics[0] is summed, whatever they held. grads beyond the actor's
+ * parameter count are not touched. t is NOT validated: a value outside [0, denoising_steps) indexes
+ * qsched and the time-embedding table out of bounds and is the caller's error.
+ * tests/test_pretrain_step_gpu.py pins this and the K lines of the geometry table above. ---- */
 DPPO_API int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const void* packed_actor, const float* actor_params,
                             const float* sched, const float* qsched, const float* x_start, const float* cond,
                             const int32_t* t, const float* noise, int rows, int64_t global_rows, float loss_scale,

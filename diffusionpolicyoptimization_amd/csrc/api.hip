@@ -47,23 +47,21 @@ extern "C" const char* dppo_last_error(void) { return g_err; }
 extern "C" size_t dppo_actor_param_count(const dppo_dims* d) {
     Dims D;
     if (dppo_check_dims(d, &D)) return 0;
-    return make_flat_offsets(D.IN, D.H, D.XD, D.TD).count;
+    return make_flat_offsets(actor_net(D)).count;
 }
 extern "C" size_t dppo_critic_param_count(const dppo_dims* d) {
-    Dims D;
-    if (dppo_check_dims(d, &D)) return 0;
-    return make_flat_offsets(D.SD, D.HC, 1, 0).count;
+    return dppo_critic_param_count_ln(d, DPPO_HEAD_RESIDUAL, DPPO_LN_OFF);
 }
 extern "C" size_t dppo_actor_packed_bytes(const dppo_dims* d, int precision) {
     Dims D;
     if (dppo_check_dims(d, &D)) return 0;
-    return make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K).total;
+    return make_mlp_layout(actor_net(D, precision)).image_bytes;
 }
 extern "C" size_t dppo_critic_packed_bytes(const dppo_dims* d, int precision) {
-    Dims D;
-    if (dppo_check_dims(d, &D)) return 0;
-    return make_mlp_layout(D.SD, D.HC, 1, 0, precision).total;
+    return dppo_critic_packed_bytes_ln(d, precision, DPPO_HEAD_RESIDUAL, DPPO_LN_OFF);
 }
+// A packing entry builds the network from its arguments, packs, and records the attributes with the image only
+// after a pack that ran: a refused pack wrote nothing and leaves the image's previous attributes
 extern "C" int dppo_pack_actor_head(const dppo_dims* d, int precision, int activation, int head, const float* params,
                                     void* packed, void* stream) {
     Dims D;
@@ -73,12 +71,10 @@ extern "C" int dppo_pack_actor_head(const dppo_dims* d, int precision, int activ
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
     DPPO_CHECK(dppo_act_ok(activation), "dppo_pack_actor_act: bad activation %d (DPPO_ACT_RELU or DPPO_ACT_MISH)", activation);
     DPPO_CHECK(dppo_head_ok(head), "dppo_pack_actor_head: bad head %d (DPPO_HEAD_RESIDUAL or DPPO_HEAD_PLAIN)", head);
-    const int old_head = dppo_actor_image_head(packed);
-    dppo_actor_image_set_head(packed, head);        // the pack's jobs and the fold launch follow the image's head
-    rc = dppo_pack_mlp(D.IN, D.H, D.XD, D.TD, precision, params, packed, (hipStream_t)stream, D.K, D.TS);
-    if (rc) { dppo_actor_image_set_head(packed, old_head); return rc; }   // refused: nothing was written
-    dppo_actor_image_set_act(packed, activation);   // the image is this activation's from here on
-    return DPPO_OK;
+    const ImageAttrs attrs{activation, head, DPPO_LN_OFF};
+    rc = dppo_pack_mlp(actor_net(D, precision, attrs), params, packed, (hipStream_t)stream);
+    if (rc == DPPO_OK) dppo_image_commit(packed, attrs);
+    return rc;
 }
 extern "C" int dppo_pack_actor_act(const dppo_dims* d, int precision, int activation, const float* params,
                                    void* packed, void* stream) {
@@ -90,14 +86,12 @@ extern "C" int dppo_pack_actor(const dppo_dims* d, int precision, const float* p
 extern "C" size_t dppo_critic_param_count_ln(const dppo_dims* d, int head, int layernorm) {
     Dims D;
     if (dppo_check_dims(d, &D) || !dppo_head_ok(head) || !dppo_ln_ok(layernorm)) return 0;
-    return make_flat_offsets(D.SD, D.HC, 1, 0).count +
-           critic_ln_flat_count(D.HC, critic_ln_sites(head == DPPO_HEAD_PLAIN, layernorm == DPPO_LN_ON));
+    return make_flat_offsets(critic_net(D, DPPO_F32, ImageAttrs{DPPO_ACT_RELU, head, layernorm})).count_all;
 }
 extern "C" size_t dppo_critic_packed_bytes_ln(const dppo_dims* d, int precision, int head, int layernorm) {
     Dims D;
     if (dppo_check_dims(d, &D) || !dppo_head_ok(head) || !dppo_ln_ok(layernorm)) return 0;
-    const int sites = critic_ln_sites(head == DPPO_HEAD_PLAIN, layernorm == DPPO_LN_ON);
-    return make_mlp_layout(D.SD, D.HC, 1, 0, precision).total + (sites ? critic_ln_image_bytes(D.HC, sites) : 0);
+    return make_mlp_layout(critic_net(D, precision, ImageAttrs{DPPO_ACT_RELU, head, layernorm})).image_bytes;
 }
 extern "C" int dppo_pack_critic_ln(const dppo_dims* d, int precision, int head, int layernorm, const float* params,
                                    void* packed, void* stream) {
@@ -108,15 +102,9 @@ extern "C" int dppo_pack_critic_ln(const dppo_dims* d, int precision, int head, 
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
     DPPO_CHECK(dppo_head_ok(head), "dppo_pack_critic_head: bad head %d (DPPO_HEAD_RESIDUAL or DPPO_HEAD_PLAIN)", head);
     DPPO_CHECK(dppo_ln_ok(layernorm), "dppo_pack_critic_ln: bad layernorm %d (DPPO_LN_OFF or DPPO_LN_ON)", layernorm);
-    // the pack's job list follows the image's attributes (the tail), so they are set before it packs
-    const int old_head = dppo_critic_image_head(packed), old_ln = dppo_critic_image_ln(packed);
-    dppo_critic_image_set_head(packed, head);
-    dppo_critic_image_set_ln(packed, layernorm);
-    rc = dppo_pack_mlp(D.SD, D.HC, 1, 0, precision, params, packed, (hipStream_t)stream);
-    if (rc) {   // refused: nothing was written, the image keeps its attributes
-        dppo_critic_image_set_head(packed, old_head);
-        dppo_critic_image_set_ln(packed, old_ln);
-    }
+    const ImageAttrs attrs{DPPO_ACT_RELU, head, layernorm};
+    rc = dppo_pack_mlp(critic_net(D, precision, attrs), params, packed, (hipStream_t)stream);
+    if (rc == DPPO_OK) dppo_image_commit(packed, attrs);
     return rc;
 }
 extern "C" int dppo_pack_critic_head(const dppo_dims* d, int precision, int head, const float* params, void* packed,

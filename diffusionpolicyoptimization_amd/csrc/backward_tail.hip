@@ -112,7 +112,7 @@ struct OutBack {
 };
 static OutBack make_out_back(const Dims& D, int precision, const float* actor_params, const float* pl2, const float* pa0,
                              float* ga) {
-    const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
+    const FlatOffsets FA = make_flat_offsets(actor_net(D));
     return OutBack{actor_params, FA, pl2, pa0, ga + FA.out_b, ga + FA.out_w, D.H, D.IN, D.XD, precision};
 }
 // (of the INSTANTIATED width l2_nq(N): the host's group count must use the same width as the kernel)
@@ -493,11 +493,11 @@ int time_bwd_check(const Dims& D, int nb) {
 // W_out's gradient (out_back) and, unless the l2 gradient stays factored, l2's from pl2, in one launch
 int launch_time_bwd(const Dims& D, int precision, const PpoWorkspace& ws, const void* packed_actor,
                     const float* actor_params, float* ga, int nb, int TS, hipStream_t s, bool l2_back, bool plain) {
-    const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
+    const FlatOffsets FA = make_flat_offsets(actor_net(D));
     const float* gseg = ws.gseg;
     const float* pl2 = l2_back ? ws.pl2 : ga + FA.l2_w;   // factored: the dW left pl2 in l2's own region
     const float* pa0 = ws.pa0;
-    const MlpLayout L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
+    const MlpLayout L = make_mlp_layout(actor_net(D, precision));
     L2Back l2b = {pl2, ga + FA.out_b, (const uint8_t*)packed_actor + L.off[SEG_W_OUT], ga + FA.l2_w, ga + FA.l2_b, D.H,
                   D.XD, precision, nullptr, nullptr, nullptr};
     DPPO_CHECK(D.XD <= L2B_MAXN, "l2_back: action horizon x dim %d > %d", D.XD, L2B_MAXN);
@@ -535,8 +535,8 @@ int launch_time_bwd(const Dims& D, int precision, const PpoWorkspace& ws, const 
 int launch_critic_l2_back(const Dims& D, int precision, const PpoWorkspace& ws, const void* packed_critic, float* gc,
                           uint32_t* zcnt, hipStream_t s, bool plain) {
     if (plain && !zcnt) return DPPO_OK;
-    const FlatOffsets FC = make_flat_offsets(D.SD, D.HC, 1, 0);
-    const MlpLayout L = make_mlp_layout(D.SD, D.HC, 1, 0, precision);
+    const FlatOffsets FC = make_flat_offsets(critic_net(D));
+    const MlpLayout L = make_mlp_layout(critic_net(D, precision));
     L2Back l2b = {ws.cpl2, gc + FC.out_b, (const uint8_t*)packed_critic + L.off[SEG_W_OUT], gc + FC.l2_w, gc + FC.l2_b,
                   D.HC, 1, precision, zcnt, ws.crow_n, ws.crow_cnt};
     DppoKtScope kt(KT_L2_BACK, s);
@@ -552,12 +552,12 @@ extern "C" int dppo_materialize_l2(const dppo_dims* d, int precision, const void
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
     DPPO_CHECK(packed_actor && grads && workspace && batch_rows > 0, "dppo_materialize_l2: bad arguments");
     // a plain-head image has no l2 layer: its minibatch deferred nothing and the l2 range is already its final zero
-    if (dppo_actor_image_head(packed_actor) == DPPO_HEAD_PLAIN) return DPPO_OK;
+    if (dppo_image_attrs(packed_actor).head == DPPO_HEAD_PLAIN) return DPPO_OK;
     hipStream_t s = (hipStream_t)stream;
     const PpoWorkspace ws = make_ppo_workspace(D, precision, batch_rows, (uint8_t*)workspace);
-    const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
+    const FlatOffsets FA = make_flat_offsets(actor_net(D));
     DPPO_HIP(hipMemcpyAsync(ws.pl2, grads + FA.l2_w, sizeof(float) * (size_t)D.H * D.XD, hipMemcpyDeviceToDevice, s));
-    const MlpLayout L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
+    const MlpLayout L = make_mlp_layout(actor_net(D, precision));
     L2Back l2b = {ws.pl2, grads + FA.out_b, (const uint8_t*)packed_actor + L.off[SEG_W_OUT], grads + FA.l2_w,
                   grads + FA.l2_b, D.H, D.XD, precision, nullptr, nullptr, nullptr};
     DPPO_CHECK(D.XD <= L2B_MAXN, "l2_back: action horizon x dim %d > %d", D.XD, L2B_MAXN);

@@ -3,24 +3,21 @@
 #include <hip/hip_runtime.h>
 #include "../../include/dppo.h"
 #include "dppo_layout.h"
+#include "image_registry.h"
 
 int dppo_set_error(int code, const char* fmt, ...);
 int dppo_hip_fail(hipError_t e, const char* what);
 
-int dppo_pack_mlp(int in_dim, int hidden, int out_dim, int time_dim, int precision, const float* params,
-                  void* packed, hipStream_t s, int temb_steps = 0, int time_stride = 1);
+// The pack takes each network as the NetSpec its ABI entry built (image_registry.h): it reads no attributes.
+// one network's image and, for an actor, its time tables and fold; a full actor pack clears a pending refresh
+int dppo_pack_mlp(const NetSpec& net, const float* params, void* packed, hipStream_t s);
 
-// derived dimensions of a dppo_dims
-struct Dims {
-    int Do, Da, Ta, To, TD, H, HC, K, KF, TS;   // K = sampling steps, TS = time stride
-    int XD, SD, IN;   // XD = Ta*Da, SD = To*Do, IN = XD + TD + SD
-};
 int dppo_check_dims(const dppo_dims* d, Dims* out);
-// the images of the given networks (either may be null) and the actor's time tables, one launch;
-// defer_sampler_tables: the actor's split-sampler tables are left stale and re-derived by the
+// the images of the given networks (either params / packed pair may be null) and the actor's time tables, one
+// launch; defer_sampler_tables: the actor's split-sampler tables are left stale and re-derived by the
 // sampler before its next launch on that image (dppo_refresh_sampler_tables, pack.hip)
 // zero_ptrs / zero_bytes: up to a few byte ranges (4-B aligned, sizes multiples of 4) the launch also zeroes
-int dppo_pack_models(const Dims& D, int precision, const float* actor_params, void* packed_actor,
+int dppo_pack_models(const NetSpec& actor, const float* actor_params, void* packed_actor, const NetSpec& critic,
                      const float* critic_params, void* packed_critic, hipStream_t s, bool defer_sampler_tables = false,
                      void* const* zero_ptrs = nullptr, const size_t* zero_bytes = nullptr, int n_zero = 0);
 
@@ -36,40 +33,15 @@ struct FuseJob {
 constexpr int FUSE_MAXJ = 12;
 // the jobs of the update-mode pack (PACK_UPDATE: no split-sampler tables) of one network whose flat
 // parameters start at element 0 of the step's range; returns the job count (<= FUSE_MAXJ) or -1
-int dppo_fuse_jobs(int in_dim, int hidden, int out_dim, int time_dim, int precision, void* packed, int temb_steps,
-                   FuseJob* jobs);
+int dppo_fuse_jobs(const NetSpec& net, void* packed, FuseJob* jobs);
 // the row tiles' fold segments (RT_*) of an actor image, alone: after a fused actor step (pack.hip)
-int dppo_pack_rt_fold(int in_dim, int hidden, int out_dim, int time_dim, int precision, const float* actor_params,
-                      void* packed_actor, int temb_steps, int time_stride, hipStream_t s);
-// temb: the TEMB table is stale too (the fused actor step), not only the split-sampler tables
-int dppo_mark_tables_stale(const Dims& D, int precision, const float* actor_params, const void* packed_actor, bool temb);
-// the activation (DPPO_ACT_*) recorded for the actor image at `packed` (dppo_pack_actor_act; pack.hip):
-// ReLU for an address no such pack recorded. Host table keyed by the address, as the stale-table list
-int dppo_actor_image_act(const void* packed);
-void dppo_actor_image_set_act(const void* packed, int activation);
+int dppo_pack_rt_fold(const NetSpec& actor, const float* actor_params, void* packed_actor, hipStream_t s);
+// the fused actor step leaves the image's split-sampler tables stale like a deferred pack; temb: the TEMB table
+// is stale too, not only the split-sampler tables
+int dppo_mark_tables_stale(const NetSpec& actor, const float* actor_params, const void* packed_actor, bool temb);
 inline bool dppo_act_ok(int a) { return a == DPPO_ACT_RELU || a == DPPO_ACT_MISH; }
-// the head (DPPO_HEAD_*) recorded the same way (dppo_pack_actor_head): RESIDUAL for an unlisted address. The
-// pack, the fold launch, the fused step's job list and the table refresh look it up by the image's address,
-// so an entry that packs sets it BEFORE it packs
-int dppo_actor_image_head(const void* packed);
-void dppo_actor_image_set_head(const void* packed, int head);
 inline bool dppo_head_ok(int h) { return h == DPPO_HEAD_RESIDUAL || h == DPPO_HEAD_PLAIN; }
-// the head of the critic image at `packed` (dppo_pack_critic_head), in the same table: RESIDUAL for an unlisted
-// address. The image's bytes do not depend on it; the row tile, the dW problem list and the critic's last
-// launch do (rowtile.hip, update.hip)
-int dppo_critic_image_head(const void* packed);
-void dppo_critic_image_set_head(const void* packed, int head);
-// the critic image's second attribute (dppo_pack_critic_ln): DPPO_LN_OFF for an unlisted address. Unlike the head
-// it lengthens the image and the flat layout by a tail (dppo_layout.h critic_ln_*); dppo_critic_ln_sites is the
-// number of norms of the image at `packed` (0 without layer norm)
-int dppo_critic_image_ln(const void* packed);
-void dppo_critic_image_set_ln(const void* packed, int layernorm);
 inline bool dppo_ln_ok(int l) { return l == DPPO_LN_OFF || l == DPPO_LN_ON; }
-inline int dppo_critic_ln_sites(const void* packed) {
-    return critic_ln_sites(dppo_critic_image_head(packed) == DPPO_HEAD_PLAIN, dppo_critic_image_ln(packed) == DPPO_LN_ON);
-}
-// the critic's jobs of a pack launch with the image's tail (pack.hip)
-int dppo_pack_critic_image(const Dims& D, int precision, const float* params, void* packed, hipStream_t s);
 // device address of mapped pinned host memory (dppo_host_alloc), cached; null if not mapped (host_staging.hip)
 void* mapped_ptr(const void* host);
 

@@ -44,6 +44,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include "../../include/dppo.h"
 
 #if defined(__HIPCC__)
 #define DPPO_HD __host__ __device__
@@ -77,11 +78,53 @@ DPPO_HD inline size_t packed_matrix_bytes(int K, int N, int KG) {
 DPPO_HD inline int rt_fold_copies(int precision) { return (precision == 1 || precision == 2) ? 2 : 1; }
 DPPO_HD inline int rt_tfold_lok(int ks_out_t, int KG) { return ks_out_t * KG / 2; }
 
-DPPO_HD inline MlpLayout make_mlp_layout(int in_dim, int hidden, int out_dim, int time_dim, int precision,
-                                         int temb_steps = 0) {
-    MlpLayout L;
+// derived dimensions of a dppo_dims (dppo_check_dims, api.hip)
+struct Dims {
+    int Do, Da, Ta, To, TD, H, HC, K, KF, TS;   // K = sampling steps, TS = time stride
+    int XD, SD, IN;   // XD = Ta*Da, SD = To*Do, IN = XD + TD + SD
+};
+
+// The attributes a pack records with an image (include/dppo.h DPPO_ACT_* / DPPO_HEAD_* / DPPO_LN_*); the defaults
+// are those of an address no pack recorded. An image is an actor's or a critic's: `head` serves both.
+struct ImageAttrs {
+    int act = DPPO_ACT_RELU, head = DPPO_HEAD_RESIDUAL, ln = DPPO_LN_OFF;
+};
+
+// One network, everything the layouts, the pack and the launch dispatch need to know about it. Built by actor_net /
+// critic_net at an ABI entry and passed down by value.
+struct NetSpec {
+    int in_dim, hidden, out_dim, time_dim;
+    int precision, temb_steps, time_stride;   // temb_steps = 0 and time_stride = 1 for a critic
+    int act, head, ln;
+    DPPO_HD bool actor() const { return time_dim > 0; }
+    DPPO_HD bool plain() const { return head == DPPO_HEAD_PLAIN; }
+    // the norms of a layer-normed critic: one per hidden layer of the plain head, the residual block's two
+    DPPO_HD int ln_sites() const { return (actor() || ln != DPPO_LN_ON) ? 0 : (plain() ? 3 : 2); }
+};
+// actor: in = XD + TD + SD, out = XD, time_dim = TD; critic: in = SD, out = 1, time_dim = 0. The flat offsets do
+// not depend on the precision
+inline NetSpec actor_net(const Dims& D, int precision = DPPO_F32, ImageAttrs a = ImageAttrs()) {
+    return NetSpec{D.IN, D.H, D.XD, D.TD, precision, D.K, D.TS, a.act, a.head, a.ln};
+}
+inline NetSpec critic_net(const Dims& D, int precision = DPPO_F32, ImageAttrs a = ImageAttrs()) {
+    return NetSpec{D.SD, D.HC, 1, 0, precision, 0, 1, a.act, a.head, a.ln};
+}
+
+// A layer-normed critic (include/dppo.h dppo_pack_critic_ln) appends a tail to both layouts; every offset before it
+// keeps its value. NetSpec::ln_sites() norms, each a gamma [hidden] then a beta [hidden]:
+//   flat   ln1_g, ln1_b, ln2_g, ln2_b(, ln3_g, ln3_b) after out_b: vector v = 2 site + (0 gamma, 1 beta) starts
+//          at NetOffsets::ln + v hidden; count_all counts them
+//   image  the same 2 sites vectors, fp32 and dense, in one segment at NetLayout::ln_off (256-B aligned);
+//          image_bytes is the image with it
+// MlpLayout and FlatOffsets are kernel arguments (by value, inside the launch argument blocks): the tail's fields
+// live in these host-side extensions, which convert to their base where a block is filled.
+struct NetLayout : MlpLayout { size_t ln_off, image_bytes; };
+
+DPPO_HD inline NetLayout make_mlp_layout(const NetSpec& s) {
+    const int in_dim = s.in_dim, hidden = s.hidden, out_dim = s.out_dim, time_dim = s.time_dim, precision = s.precision;
+    NetLayout L;
     L.in_dim = in_dim; L.hidden = hidden; L.out_dim = out_dim; L.time_dim = time_dim; L.precision = precision;
-    L.temb_steps = time_dim > 0 ? temb_steps : 0;
+    L.temb_steps = time_dim > 0 ? s.temb_steps : 0;
     L.KG = (precision == 1 || precision == 2) ? 32 : 16;     // bf16 / fp16: 32; fp32: 16
     L.ks_in = packed_ksteps(in_dim, L.KG);
     L.ks_h = packed_ksteps(hidden, L.KG);
@@ -117,7 +160,8 @@ DPPO_HD inline MlpLayout make_mlp_layout(int in_dim, int hidden, int out_dim, in
     L.off[SEG_RT_TFOLD] = o;
     o = dppo_align256(o + (rt ? packed_matrix_bytes(L.ks_out_t * L.KG, hidden, L.KG) : 0));
     L.off[SEG_RT_BOUT] = o; o = dppo_align256(o + (rt ? (size_t)4 * 16 * L.nt_out : 0));
-    L.total = o;
+    L.total = L.ln_off = o;
+    L.image_bytes = o + dppo_align256((size_t)4 * 2 * s.ln_sites() * hidden);
     return L;
 }
 
@@ -125,8 +169,10 @@ DPPO_HD inline MlpLayout make_mlp_layout(int in_dim, int hidden, int out_dim, in
 struct FlatOffsets {
     size_t time_w1, time_b1, time_w2, time_b2, in_w, in_b, l1_w, l1_b, l2_w, l2_b, out_w, out_b, count;
 };
-DPPO_HD inline FlatOffsets make_flat_offsets(int in_dim, int hidden, int out_dim, int time_dim) {
-    FlatOffsets f;
+struct NetOffsets : FlatOffsets { size_t ln, count_all; };
+DPPO_HD inline NetOffsets make_flat_offsets(const NetSpec& s) {
+    const int in_dim = s.in_dim, hidden = s.hidden, out_dim = s.out_dim, time_dim = s.time_dim;
+    NetOffsets f;
     size_t o = 0;
     f.time_w1 = o; o += (size_t)time_dim * 2 * time_dim;
     f.time_b1 = o; o += (size_t)2 * time_dim;
@@ -140,23 +186,11 @@ DPPO_HD inline FlatOffsets make_flat_offsets(int in_dim, int hidden, int out_dim
     f.l2_b = o; o += hidden;
     f.out_w = o; o += (size_t)hidden * out_dim;
     f.out_b = o; o += out_dim;
-    f.count = o;
+    f.count = f.ln = o;
+    f.count_all = o + (size_t)2 * s.ln_sites() * hidden;
     return f;
 }
 
-// A layer-normed critic (include/dppo.h dppo_pack_critic_ln) appends a tail to both layouts; every offset above
-// keeps its value. `sites` norms (3 for the plain head: one per hidden layer; 2 for the residual head: the two
-// pre-activation norms of the block), each a gamma [hidden] then a beta [hidden]:
-//   flat   ln1_g, ln1_b, ln2_g, ln2_b(, ln3_g, ln3_b) after out_b: vector v = 2 site + (0 gamma, 1 beta) starts
-//          at FlatOffsets::count + v hidden
-//   image  the same 2 sites vectors, fp32 and dense, in one segment at MlpLayout::total (256-B aligned)
-DPPO_HD inline int critic_ln_sites(bool plain_head, bool layernorm) { return layernorm ? (plain_head ? 3 : 2) : 0; }
-DPPO_HD inline size_t critic_ln_flat_count(int hidden, int sites) { return (size_t)2 * sites * hidden; }
-DPPO_HD inline size_t critic_ln_image_bytes(int hidden, int sites) { return dppo_align256((size_t)4 * 2 * sites * hidden); }
 // Keras' LayerNormalization default in the plain MLP (mlp.py:66), 1e-6 inside the residual block (mlp.py:174-176)
 DPPO_HD inline float critic_ln_eps(bool plain_head) { return plain_head ? 1e-3f : 1e-6f; }
 
-// actor: in = XD + TD + SD, out = XD, time_dim = TD; critic: in = SD, out = 1, time_dim = 0
-struct ModelDims {
-    int XD, SD, TD, H, HC, K, KF, Ta, Da;
-};

@@ -156,7 +156,9 @@ struct ActorTilePlan { int mt, waves; };
 ActorTilePlan actor_tile_plan(int precision, int H, int XD, int64_t rows, int act);
 // dry: only check that the launch has an instantiation (DPPO_EUNSUPPORTED with the dispatch's message
 // otherwise); nothing is launched and no device state is read or written
-int launch_actor_rowtile(const ActorArgs& a, int precision, hipStream_t s, bool dry = false);
-int launch_critic_rowtile(const CriticArgs& a, int precision, hipStream_t s, bool dry = false);
-// the same for a layer-normed critic image (rowtile_ln.hip; launch_critic_rowtile routes to it by the image's attribute)
-int launch_critic_rowtile_ln(const CriticArgs& a, int precision, hipStream_t s, bool dry);
+// net: the image's network (the caller's, built where it filled a.L): its precision and attributes pick the
+// instantiation. Host-only, beside the kernel's argument block
+int launch_actor_rowtile(const ActorArgs& a, const NetSpec& net, hipStream_t s, bool dry = false);
+int launch_critic_rowtile(const CriticArgs& a, const NetSpec& net, hipStream_t s, bool dry = false);
+// the same for a layer-normed critic image (rowtile_ln.hip; launch_critic_rowtile routes to it by net.ln)
+int launch_critic_rowtile_ln(const CriticArgs& a, const NetSpec& net, hipStream_t s, bool dry);

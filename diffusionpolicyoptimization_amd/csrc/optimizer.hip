@@ -410,19 +410,19 @@ struct StepCtx {
     double* mout;          // metrics_out's device address
     int mode;              // the AdamW mode, the DPPO_STEP_* flags taken out
     bool defer, l2v, fuse, clear_g;
-    FlatOffsets FA, FC;
-    int cln_sites;         // the critic's norms (its image's attributes; a clipped range without one: by its length)
-    size_t ccount;         // the critic's parameters with their tail, FC.count + 2 cln_sites HC
+    // the two networks: their images' attributes, read here once (a clipped critic range without an image: told by
+    // its length); FC.count_all is the critic's parameters with their tail
+    NetSpec anet, cnet;
+    NetOffsets FA, FC;
     L2Virt vt;
     bool clipped;
     ClipTab clip;
 };
 
 // The variables of the chosen networks (DPPO_NET_*) in layout order: end[v] = one past variable v,
-// counted from the start of the range; returns their number (12 actor, 8 critic + the 2 ln_sites vectors of a
+// counted from the start of the range; returns their number (12 actor, 8 critic + the vectors of a
 // layer-normed critic's tail, each a variable of `hidden` elements)
-static int net_var_ends(const FlatOffsets& FA, const FlatOffsets& FC, int nets, int64_t* end, int ln_sites = 0,
-                        int hidden = 0) {
+static int net_var_ends(const FlatOffsets& FA, const NetOffsets& FC, int hidden, int nets, int64_t* end) {
     int nv = 0;
     int64_t base = 0;
     if (nets & DPPO_NET_ACTOR) {
@@ -434,7 +434,7 @@ static int net_var_ends(const FlatOffsets& FA, const FlatOffsets& FC, int nets, 
     if (nets & DPPO_NET_CRITIC) {
         const size_t e[8] = {FC.in_b, FC.l1_w, FC.l1_b, FC.l2_w, FC.l2_b, FC.out_w, FC.out_b, FC.count};
         for (size_t x : e) end[nv++] = base + (int64_t)x;
-        for (int v = 1; v <= 2 * ln_sites; ++v) end[nv++] = base + (int64_t)FC.count + (int64_t)v * hidden;
+        for (size_t e = FC.ln + hidden; e <= FC.count_all; e += hidden) end[nv++] = base + (int64_t)e;
     }
     return nv;
 }
@@ -465,40 +465,41 @@ static int step_prologue(const StepArgs& a, StepCtx& c) {
     c.fuse = (a.w.mode & DPPO_STEP_FUSED_PACK) != 0;
     c.clear_g = (a.w.mode & DPPO_STEP_CLEAR_GRADS) != 0;
     c.mode = a.w.mode & ~(DPPO_STEP_DEFER_SAMPLER_TABLES | DPPO_STEP_L2_FROM_PL2 | DPPO_STEP_FUSED_PACK | DPPO_STEP_CLEAR_GRADS);
-    c.FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
-    c.FC = make_flat_offsets(D.SD, D.HC, 1, 0);
+    const auto ln_critic = [&](int head) { return critic_net(D, a.precision, ImageAttrs{DPPO_ACT_RELU, head, DPPO_LN_ON}); };
+    c.anet = actor_net(D, a.precision, a.packed_actor ? dppo_image_attrs(a.packed_actor) : ImageAttrs());
+    c.cnet = critic_net(D, a.precision, a.packed_critic ? dppo_image_attrs(a.packed_critic) : ImageAttrs());
+    c.FA = make_flat_offsets(c.anet);
     // The critic's layout follows its image's attributes. A clipped critic range without an image is told by its
     // length (the three layouts differ in it)
-    c.cln_sites = a.packed_critic ? dppo_critic_ln_sites(a.packed_critic) : 0;
     if (!a.packed_critic && a.nets >= 1 && a.nets <= 3 && (a.nets & DPPO_NET_CRITIC)) {
-        const int64_t rest = a.w.n - (int64_t)c.FC.count - ((a.nets & DPPO_NET_ACTOR) ? (int64_t)c.FA.count : 0);
-        for (int sites = 2; sites <= 3; ++sites)
-            if (rest == (int64_t)critic_ln_flat_count(D.HC, sites)) c.cln_sites = sites;
+        const int64_t ncritic = a.w.n - ((a.nets & DPPO_NET_ACTOR) ? (int64_t)c.FA.count : 0);
+        for (int head : {DPPO_HEAD_RESIDUAL, DPPO_HEAD_PLAIN})
+            if (ncritic == (int64_t)make_flat_offsets(ln_critic(head)).count_all) c.cnet = ln_critic(head);
     }
-    c.ccount = c.FC.count + critic_ln_flat_count(D.HC, c.cln_sites);
+    c.FC = make_flat_offsets(c.cnet);
     if (a.packed_critic && a.critic_params && a.w.params && a.critic_params >= a.w.params &&
         a.critic_params < a.w.params + a.w.n) {
         // the range holds the critic from critic_params on: it must hold the layout of the image's attributes
         const int64_t room = a.w.n - (int64_t)(a.critic_params - a.w.params);
-        DPPO_CHECK(c.cln_sites == 0 || room >= (int64_t)c.ccount,
+        DPPO_CHECK(c.cnet.ln_sites() == 0 || room >= (int64_t)c.FC.count_all,
                    "dppo_optimizer_step: the critic image is layer-normed (%zu parameters with its gamma / beta tail), the "
-                   "range holds %lld from critic_params on: buffers sized for the layout without the tail", c.ccount,
+                   "range holds %lld from critic_params on: buffers sized for the layout without the tail", c.FC.count_all,
                    (long long)room);
-        if (c.cln_sites == 0 && !a.packed_actor && a.critic_params == a.w.params)
-            for (int sites = 2; sites <= 3; ++sites)
-                DPPO_CHECK(a.w.n != (int64_t)(c.FC.count + critic_ln_flat_count(D.HC, sites)),
+        if (c.cnet.ln_sites() == 0 && !a.packed_actor && a.critic_params == a.w.params)
+            for (int head : {DPPO_HEAD_RESIDUAL, DPPO_HEAD_PLAIN})
+                DPPO_CHECK(a.w.n != (int64_t)make_flat_offsets(ln_critic(head)).count_all,
                            "dppo_optimizer_step: the range is a layer-normed critic's (%lld parameters), the critic image has "
                            "no layer norm (dppo_pack_critic_ln)", (long long)a.w.n);
     }
     c.vt = L2Virt{};
     if (c.l2v) {
-        DPPO_CHECK(!a.packed_actor || dppo_actor_image_head(a.packed_actor) != DPPO_HEAD_PLAIN,
+        DPPO_CHECK(!a.packed_actor || !c.anet.plain(),
                    "dppo_optimizer_step: DPPO_STEP_L2_FROM_PL2 on a plain-head actor image (it has no l2 layer)");
         DPPO_CHECK(a.packed_actor && a.actor_params == a.w.params,
                    "dppo_optimizer_step: DPPO_STEP_L2_FROM_PL2 needs the actor's image and the actor range first");
         DPPO_CHECK(a.w.n >= (int64_t)c.FA.count, "dppo_optimizer_step: DPPO_STEP_L2_FROM_PL2 needs the whole actor range");
         DPPO_CHECK(c.FA.l2_b == c.FA.l2_w + (size_t)D.H * D.H, "l2 layout");
-        const MlpLayout L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, a.precision, D.K);
+        const MlpLayout L = make_mlp_layout(c.anet);
         c.vt = L2Virt{1, (int64_t)c.FA.l2_w, (int64_t)c.FA.l2_b, (int64_t)c.FA.out_b, D.H, D.XD, a.precision,
                       (const uint8_t*)a.packed_actor + L.off[SEG_W_OUT]};
     }
@@ -508,7 +509,7 @@ static int step_prologue(const StepArgs& a, StepCtx& c) {
         DPPO_CHECK(a.nets >= 1 && a.nets <= 3, "dppo_optimizer_step_clip: nets %d outside 1..3", a.nets);
         DPPO_CHECK(a.clip_scales, "dppo_optimizer_step_clip: clip_scales is NULL");
         int64_t end[CLIP_MAXV];
-        const int nv = net_var_ends(c.FA, c.FC, a.nets, end, c.cln_sites, D.HC);
+        const int nv = net_var_ends(c.FA, c.FC, D.HC, a.nets, end);
         const float* crit = a.w.params ? a.w.params + ((a.nets & DPPO_NET_ACTOR) ? c.FA.count : 0) : nullptr;
         DPPO_CHECK(a.w.n == end[nv - 1] && ((a.nets & DPPO_NET_ACTOR) == 0 || !a.actor_params || a.actor_params == a.w.params) &&
                    ((a.nets & DPPO_NET_CRITIC) == 0 || !a.critic_params || a.critic_params == crit),
@@ -521,10 +522,9 @@ static int step_prologue(const StepArgs& a, StepCtx& c) {
 
 // the critic's step in one launch (adamw_fused_kernel)
 static int fused_critic_step(const StepArgs& a, const StepCtx& c, const AdamHP& h) {
-    const Dims& D = c.D;
     hipStream_t s = c.s;
     StepFuse f = {};
-    f.njobs = dppo_fuse_jobs(D.SD, D.HC, 1, 0, a.precision, a.packed_critic, 0, f.j);
+    f.njobs = dppo_fuse_jobs(c.cnet, a.packed_critic, f.j);
     DPPO_CHECK(f.njobs >= 0, "dppo_optimizer_step: fused pack jobs");
     f.clear_grads = c.clear_g ? 1 : 0;
     for (int r = 0; r < a.n_clear; ++r) { f.clr[r] = a.clear_ptrs[r]; f.clr_words[r] = (uint32_t)(a.clear_bytes[r] / 4); }
@@ -555,7 +555,7 @@ static int fused_critic_step(const StepArgs& a, const StepCtx& c, const AdamHP& 
 static int make_tile_step(const StepArgs& a, const StepCtx& c, TileStep& t) {
     const Dims& D = c.D;
     FuseJob jobs[FUSE_MAXJ];
-    const int nj = dppo_fuse_jobs(D.IN, D.H, D.XD, D.TD, a.precision, a.packed_actor, D.K, jobs);
+    const int nj = dppo_fuse_jobs(c.anet, a.packed_actor, jobs);
     DPPO_CHECK(nj >= 0, "dppo_optimizer_step: fused pack jobs");
     t = TileStep{};
     t.last_mat = -1;
@@ -601,7 +601,6 @@ static int make_tile_step(const StepArgs& a, const StepCtx& c, TileStep& t) {
 // split-sampler tables to the fold launch (the row tiles derive the time embeddings, the sampler
 // re-derives the tables before its next launch)
 static int fused_actor_step(const StepArgs& a, const StepCtx& c, const AdamHP& h) {
-    const Dims& D = c.D;
     hipStream_t s = c.s;
     TileStep t;
     int rc = make_tile_step(a, c, t);
@@ -627,9 +626,9 @@ static int fused_actor_step(const StepArgs& a, const StepCtx& c, const AdamHP& h
         });
     }
     DPPO_HIP(hipGetLastError());
-    rc = dppo_pack_rt_fold(D.IN, D.H, D.XD, D.TD, a.precision, a.actor_params, a.packed_actor, D.K, D.TS, s);   // cross-element: not per element
+    rc = dppo_pack_rt_fold(c.anet, a.actor_params, a.packed_actor, s);   // cross-element: not per element
     if (rc) return rc;
-    return dppo_mark_tables_stale(D, a.precision, a.actor_params, a.packed_actor, true);
+    return dppo_mark_tables_stale(c.anet, a.actor_params, a.packed_actor, true);
 }
 
 // the launch-per-stage form (any ranges and images): AdamW, then the pack, which also zeroes the
@@ -648,8 +647,8 @@ static int staged_step(const StepArgs& a, const StepCtx& c) {
     for (int r = 0; r < nz; ++r)
         DPPO_CHECK(zb[r] / 4 < ((size_t)1 << 31), "dppo_optimizer_step_ex: clear range %d too large", r);
     if (a.packed_actor || a.packed_critic)
-        return dppo_pack_models(c.D, a.precision, a.actor_params, a.packed_actor, a.critic_params, a.packed_critic, s,
-                                c.defer, zp, zb, nz);
+        return dppo_pack_models(c.anet, a.actor_params, a.packed_actor, c.cnet, a.critic_params, a.packed_critic, s, c.defer,
+                                zp, zb, nz);
     if (nz) {   // no image to pack: the clears alone
         ZeroArgs z = {};
         for (int r = 0; r < nz; ++r) {
@@ -673,7 +672,7 @@ static int optimizer_step_impl(const StepArgs& a) {
     const AdamwArgs& w = a.w;
     // the one-launch forms: a single network whose parameters are exactly the range
     const bool one_actor = a.packed_actor && !a.packed_critic && a.actor_params == w.params && w.n == (int64_t)c.FA.count;
-    const bool one_critic = a.packed_critic && !a.packed_actor && a.critic_params == w.params && w.n == (int64_t)c.ccount;
+    const bool one_critic = a.packed_critic && !a.packed_actor && a.critic_params == w.params && w.n == (int64_t)c.FC.count_all;
     if (!(c.fuse && (one_actor || one_critic) && w.n > 0)) return staged_step(a, c);
     { const int rc_ = check_metrics_copy(a.metrics, c.mout, a.n_metrics, a.metrics_tag); if (rc_) return rc_; }
     DPPO_CHECK(w.step >= 1 && (c.mode == DPPO_ADAMW_KERAS || c.mode == DPPO_ADAMW_TORCH), "dppo_adamw: bad step or mode");
@@ -820,11 +819,11 @@ __global__ __launch_bounds__(CLIP_THREADS) void grad_clip_kernel(const float* __
     }
 }
 
-static int make_clip_vars(const Dims& D, int nets, ClipVars& cv, int ln_sites = 0) {
-    const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD), FC = make_flat_offsets(D.SD, D.HC, 1, 0);
+static int make_clip_vars(const Dims& D, int nets, ClipVars& cv, ImageAttrs critic) {
+    const NetOffsets FA = make_flat_offsets(actor_net(D)), FC = make_flat_offsets(critic_net(D, DPPO_F32, critic));
     int64_t end[CLIP_MAXV];
     cv = ClipVars{};
-    cv.nv = net_var_ends(FA, FC, nets, end, ln_sites, D.HC);
+    cv.nv = net_var_ends(FA, FC, D.HC, nets, end);
     DPPO_CHECK(end[cv.nv - 1] < ((int64_t)1 << 31), "dppo_grad_clip: range too large");
     cv.cstart[0] = 0;
     for (int v = 0; v < CLIP_MAXV; ++v) {
@@ -840,7 +839,7 @@ extern "C" size_t dppo_grad_clip_workspace_bytes_ln(const dppo_dims* d, int nets
     Dims D;
     ClipVars cv;
     if (dppo_check_dims(d, &D) || nets < 1 || nets > 3 || !dppo_head_ok(critic_head) || !dppo_ln_ok(critic_layernorm) ||
-        make_clip_vars(D, nets, cv, critic_ln_sites(critic_head == DPPO_HEAD_PLAIN, critic_layernorm == DPPO_LN_ON)))
+        make_clip_vars(D, nets, cv, ImageAttrs{DPPO_ACT_RELU, critic_head, critic_layernorm}))
         return 0;
     return (size_t)cv.cstart[cv.nv] * sizeof(double);
 }
@@ -871,7 +870,7 @@ extern "C" int dppo_grad_clip_scales_ln(const dppo_dims* d, int nets, int critic
     DPPO_CHECK(workspace && ((uintptr_t)workspace & 7) == 0, "dppo_grad_clip_scales: workspace must be 8-B aligned");
     DPPO_CHECK(((uintptr_t)grads & 3) == 0, "dppo_grad_clip_scales: grads must be 4-B aligned");
     ClipVars cv;
-    rc = make_clip_vars(D, nets, cv, critic_ln_sites(critic_head == DPPO_HEAD_PLAIN, critic_layernorm == DPPO_LN_ON));
+    rc = make_clip_vars(D, nets, cv, ImageAttrs{DPPO_ACT_RELU, critic_head, critic_layernorm});
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     unsigned* ticket = nullptr;

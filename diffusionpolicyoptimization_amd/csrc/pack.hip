@@ -1,7 +1,5 @@
 // pack.hip — flat fp32 Keras parameters -> packed MFMA fragment images (dppo_layout.h).
 // Replaces the Keras variable storage of model/common/mlp.py:95-206 (kernels are [in,out]).
-#include <mutex>
-#include <vector>
 #include "dppo_common.cuh"
 #include "dppo_internal.h"
 
@@ -494,85 +492,109 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_all_kernel(PackArgs a) {
 
 static inline uint8_t* P_out(void* p) { return (uint8_t*)p; }
 
-// the jobs of one MLP image (and, for an actor, its time tables) appended to a
-// PackArgs; returns DPPO_OK or an error code. what: PACK_ALL, PACK_UPDATE (everything but the
-// split sampler's tables: W_XS, FOLD / ROUT, TIN, B_OUT2), PACK_SAMPLER (those tables only),
-// PACK_SAMPLER_TEMB (those tables and the TEMB table: after a fused actor step, any precision). Every
-// pack with the main jobs of an actor is followed by the row tiles' fold (launch_rt_fold).
-// PACK_UPDATE leaves the TEMB rows out too: the row tiles derive theirs (writing them, the r04 pack,
-// measured no different; profiles/r05h_pack_temb_ab.txt)
+// The tensors of one network's image, the one list the pack launch (add_mlp_jobs' main jobs) and the fused
+// optimizer step (dppo_fuse_jobs) both map to their job structs: where the tensor starts in the flat parameters
+// and how many elements it has, the image's [K][N] and where it goes, and in which form.
+enum { T_FWD, T_TRANS, T_COPY, T_ZERO };   // forward fragments / fragments of the transpose / fp32 copy / zero-fill
+struct ImageTensor {
+    int form;
+    size_t src, count;   // flat offset and elements (T_ZERO: none)
+    int K, N;            // fragments: the image is [K][N] (T_TRANS: of the row-major [N][K] tensor)
+    int npad;            // T_COPY: fp32 slots written, zeros past count
+    size_t dst;          // byte offset in the image
+};
+constexpr int IMG_MAXT = 13;
+static int image_tensors(const NetSpec& s, ImageTensor* t) {
+    const NetLayout L = make_mlp_layout(s);
+    const NetOffsets F = make_flat_offsets(s);
+    const int H = s.hidden, IN = s.in_dim, OUT = s.out_dim;
+    int n = 0;
+    auto mat = [&](int form, size_t src, int K, int N, int seg) { t[n++] = {form, src, (size_t)K * N, K, N, 0, L.off[seg]}; };
+    auto cpy = [&](size_t src, size_t count, size_t npad, size_t dst) { t[n++] = {T_COPY, src, count, 0, 0, (int)npad, dst}; };
+    if (s.actor()) cpy(F.time_w1, F.in_w - F.time_w1, F.in_w - F.time_w1, L.off[SEG_TIME]);
+    mat(T_FWD, F.in_w, IN, H, SEG_W_IN);
+    cpy(F.in_b, H, H, L.off[SEG_B_IN]);
+    mat(T_FWD, F.l1_w, H, H, SEG_W_L1);
+    cpy(F.l1_b, H, H, L.off[SEG_B_L1]);
+    mat(T_FWD, F.l2_w, H, H, SEG_W_L2);
+    cpy(F.l2_b, H, H, L.off[SEG_B_L2]);
+    mat(T_FWD, F.out_w, H, OUT, SEG_W_OUT);
+    cpy(F.out_b, OUT, 16 * L.nt_out, L.off[SEG_B_OUT]);
+    // transposed images: W^T viewed as a [K'=out][N'=in] weight, i.e. element (k', n') = W[n'][k']. A plain-head
+    // actor's dh3 = dy W_out^T is the skip's share of dh1: none (the whole segment is zero)
+    if (s.actor() && s.plain()) t[n++] = {T_ZERO, 0, 0, OUT, H, 0, L.off[SEG_T_OUT]};
+    else mat(T_TRANS, F.out_w, OUT, H, SEG_T_OUT);
+    mat(T_TRANS, F.l2_w, H, H, SEG_T_L2);   // the actor's: the A operand of its fold (rt_fold_kernel)
+    mat(T_TRANS, F.l1_w, H, H, SEG_T_L1);
+    // a layer-normed critic's gamma / beta tail, one dense fp32 copy
+    if (s.ln_sites()) cpy(F.ln, F.count_all - F.ln, (L.image_bytes - L.ln_off) / 4, L.ln_off);
+    return n;
+}
+
+// what: PACK_ALL, PACK_UPDATE (everything but the split sampler's tables: W_XS, FOLD / ROUT, TIN, B_OUT2),
+// PACK_SAMPLER (those tables only), PACK_SAMPLER_TEMB (those tables and the TEMB table: after a fused actor step,
+// any precision). Every pack with the main jobs of an actor is followed by the row tiles' fold (dppo_pack_rt_fold).
+// PACK_UPDATE leaves the TEMB rows out too: the row tiles derive theirs (writing them, the r04 pack, measured no
+// different; profiles/r05h_pack_temb_ab.txt)
 enum { PACK_ALL = 0, PACK_UPDATE = 1, PACK_SAMPLER = 2, PACK_SAMPLER_TEMB = 3 };
-static int add_mlp_jobs(PackArgs& a, int in_dim, int hidden, int out_dim, int time_dim, int precision,
-                        const float* params, void* packed, int temb_steps, int time_stride, int what = PACK_ALL) {
-    const MlpLayout L = make_mlp_layout(in_dim, hidden, out_dim, time_dim, precision, temb_steps);
-    const FlatOffsets F = make_flat_offsets(in_dim, hidden, out_dim, time_dim);
-    const int KG = dppo_prec_2b(precision) ? 32 : 16;
-    const bool actor = time_dim > 0;
-    const bool plain = actor && dppo_actor_image_head(packed) == DPPO_HEAD_PLAIN;
-    // the split sampler's tables (every precision since r06: fp32 runs the split kernel at P = 4, its fold
-    // from RT_FOLD and its residual from W_OUT, so only the 2-byte images carry FOLD / ROUT)
-    const bool split_tables = actor && L.temb_steps > 0;
+// the split sampler's tables (every precision since r06: fp32 runs the split kernel at P = 4, its fold
+// from RT_FOLD and its residual from W_OUT, so only the 2-byte images carry FOLD / ROUT)
+static bool packs_sampler_tables(const NetSpec& s, int what) {
+    return s.actor() && s.temb_steps > 0 && (what == PACK_ALL || what == PACK_SAMPLER || what == PACK_SAMPLER_TEMB);
+}
+// the jobs add_mlp_jobs appends for a network: its tensors and the split sampler's W_XS
+static int mlp_job_count(const NetSpec& s, int what) {
+    ImageTensor t[IMG_MAXT];
+    return ((what == PACK_ALL || what == PACK_UPDATE) ? image_tensors(s, t) : 0) + (packs_sampler_tables(s, what) ? 1 : 0);
+}
+
+// the jobs of one MLP image (and, for an actor, its time tables) appended to a PackArgs; returns DPPO_OK or an
+// error code
+static int add_mlp_jobs(PackArgs& a, const NetSpec& s, const float* params, void* packed, int what = PACK_ALL) {
+    const NetLayout L = make_mlp_layout(s);
+    const NetOffsets F = make_flat_offsets(s);
     const bool main_jobs = what == PACK_ALL || what == PACK_UPDATE;
-    const bool sampler_tables = split_tables && (what == PACK_ALL || what == PACK_SAMPLER || what == PACK_SAMPLER_TEMB);
+    const bool sampler_tables = packs_sampler_tables(s, what);
     const bool temb_rows = L.temb_steps > 0 && what != PACK_UPDATE;
-    // a layer-normed critic image (dppo_pack_critic_ln): its gamma / beta tail, one dense fp32 copy
-    const int ln_sites = actor ? 0 : dppo_critic_ln_sites(packed);
-    const int jobs = (main_jobs ? 11 + (actor ? 1 : 0) + (ln_sites ? 1 : 0) : 0) + (sampler_tables ? 1 : 0);
-    if (a.njobs + jobs > PACK_MAXJ) return dppo_set_error(DPPO_EINVAL, "pack: too many images in one launch");
-    auto mat = [&](size_t src, int K, int N, bool tr, int seg) {
+    if (a.njobs + mlp_job_count(s, what) > PACK_MAXJ) return dppo_set_error(DPPO_EINVAL, "pack: too many images in one launch");
+    auto mat = [&](size_t src, int K, int N, bool tr, size_t dst) -> PackJob& {
         PackJob& J = a.j[a.njobs++];
-        J.kind = 0; J.K = K; J.N = N; J.transposed = tr ? 1 : 0; J.src = params + src; J.dst = P_out(packed) + L.off[seg];
+        J.kind = 0; J.K = K; J.N = N; J.transposed = tr ? 1 : 0; J.src = params + src; J.dst = P_out(packed) + dst;
         J.k_split = K; J.k_skip = 0;
-        J.threads = dppo_cdiv(N, 16) * packed_ksteps(K, KG) * 64;
-    };
-    auto cpy = [&](size_t src, int n, int npad, int seg) {
-        PackJob& J = a.j[a.njobs++];
-        J.kind = 1; J.n = n; J.npad = npad; J.src = params + src; J.dst = P_out(packed) + L.off[seg]; J.threads = npad;
+        J.threads = dppo_cdiv(N, 16) * packed_ksteps(K, L.KG) * 64;
+        return J;
     };
     if (main_jobs) {
-        if (actor) cpy(F.time_w1, (int)(F.in_w - F.time_w1), (int)(F.in_w - F.time_w1), SEG_TIME);
-        mat(F.in_w, in_dim, hidden, false, SEG_W_IN);
-        cpy(F.in_b, hidden, hidden, SEG_B_IN);
-        mat(F.l1_w, hidden, hidden, false, SEG_W_L1);
-        cpy(F.l1_b, hidden, hidden, SEG_B_L1);
-        mat(F.l2_w, hidden, hidden, false, SEG_W_L2);
-        cpy(F.l2_b, hidden, hidden, SEG_B_L2);
-        mat(F.out_w, hidden, out_dim, false, SEG_W_OUT);
-        cpy(F.out_b, out_dim, 16 * L.nt_out, SEG_B_OUT);
-        // transposed images: W^T viewed as a [K'=out][N'=in] weight, i.e. element (k', n') = W[n'][k']
-        if (plain) {   // dh3 = dy W_out^T is the skip's share of dh1: none (the whole segment is zero)
+        ImageTensor t[IMG_MAXT];
+        const int nt = image_tensors(s, t);
+        for (int i = 0; i < nt; ++i) {
+            const ImageTensor& T = t[i];
+            if (T.form == T_FWD || T.form == T_TRANS) { mat(T.src, T.K, T.N, T.form == T_TRANS, T.dst); continue; }
             PackJob& J = a.j[a.njobs++];
-            J.kind = 2; J.dst = P_out(packed) + L.off[SEG_T_OUT];
-            J.n = (int)(packed_matrix_bytes(out_dim, hidden, KG) / 4); J.threads = (J.n + 3) / 4;
-        } else {
-            mat(F.out_w, out_dim, hidden, true, SEG_T_OUT);
-        }
-        mat(F.l2_w, hidden, hidden, true, SEG_T_L2);   // the actor's: the A operand of its fold (rt_fold_kernel)
-        mat(F.l1_w, hidden, hidden, true, SEG_T_L1);
-        if (ln_sites) {
-            cpy(F.count, (int)critic_ln_flat_count(hidden, ln_sites), (int)(critic_ln_image_bytes(hidden, ln_sites) / 4), SEG_TIME);
-            a.j[a.njobs - 1].dst = P_out(packed) + L.total;
+            J.dst = P_out(packed) + T.dst;
+            if (T.form == T_COPY) { J.kind = 1; J.n = (int)T.count; J.npad = T.npad; J.src = params + T.src; J.threads = T.npad; }
+            else { J.kind = 2; J.n = (int)(packed_matrix_bytes(T.K, T.N, L.KG) / 4); J.threads = (J.n + 3) / 4; }
         }
     }
     if (sampler_tables) {   // split sampler: W_in rows [x ; state] (skipping the TD time-embedding rows)
-        mat(F.in_w, in_dim - time_dim, hidden, false, SEG_W_XS);
-        a.j[a.njobs - 1].k_split = out_dim;
-        a.j[a.njobs - 1].k_skip = time_dim;
+        PackJob& J = mat(F.in_w, s.in_dim - s.time_dim, s.hidden, false, L.off[SEG_W_XS]);
+        J.k_split = s.out_dim;
+        J.k_skip = s.time_dim;
     }
     // PACK_UPDATE leaves TEMB to its consumers too: the row tiles derive their time embeddings from the
     // fp32 time MLP (rowtile.hip), the sampler's table refresh re-derives the table (r05: the TEMB
     // blocks were the pack launch's long pole on every minibatch)
-    if (actor && (temb_rows || sampler_tables)) {
-        if (time_dim > 64 || out_dim > 32)
+    if (s.actor() && (temb_rows || sampler_tables)) {
+        if (s.time_dim > 64 || s.out_dim > 32)
             return dppo_set_error(DPPO_EUNSUPPORTED, "time table: time_dim <= 64 and out_dim <= 32");
         if (a.tb.params) return dppo_set_error(DPPO_EINVAL, "pack: one actor per launch");
         TembArgs& b = a.tb;
-        b.params = params; b.F = F; b.TD = time_dim; b.stride = time_stride; b.R = L.temb_steps; b.XD = out_dim;
-        b.H = hidden; b.nout = 16 * L.nt_out; b.plain = plain ? 1 : 0;
+        b.params = params; b.F = F; b.TD = s.time_dim; b.stride = s.time_stride; b.R = L.temb_steps; b.XD = s.out_dim;
+        b.H = s.hidden; b.nout = 16 * L.nt_out; b.plain = s.plain() ? 1 : 0;
         b.temb = (float*)(P_out(packed) + L.off[SEG_TEMB]);
         b.tin = (float*)(P_out(packed) + L.off[SEG_TIN]);
         b.bout2 = (float*)(P_out(packed) + L.off[SEG_B_OUT2]);
-        const bool fold2b = sampler_tables && dppo_prec_2b(precision);
+        const bool fold2b = sampler_tables && dppo_prec_2b(s.precision);
         b.fold = fold2b ? P_out(packed) + L.off[SEG_FOLD] : nullptr;
         b.rout = fold2b ? P_out(packed) + L.off[SEG_ROUT] : nullptr;
         b.nfold = fold2b ? L.nt_h : 0;
@@ -583,40 +605,24 @@ static int add_mlp_jobs(PackArgs& a, int in_dim, int hidden, int out_dim, int ti
     return DPPO_OK;
 }
 
-// add_mlp_jobs' main jobs (PACK_UPDATE) as element ranges of the flat parameters, same segments and
-// geometry; the TEMB table is derived separately (the fused step's last workgroup)
-int dppo_fuse_jobs(int in_dim, int hidden, int out_dim, int time_dim, int precision, void* packed, int temb_steps,
-                   FuseJob* jobs) {
-    // a plain-head actor image keeps T_OUT zero (add_mlp_jobs): W_out has no transposed slots to rewrite
-    const bool plain = time_dim > 0 && dppo_actor_image_head(packed) == DPPO_HEAD_PLAIN;
-    const MlpLayout L = make_mlp_layout(in_dim, hidden, out_dim, time_dim, precision, temb_steps);
-    const FlatOffsets F = make_flat_offsets(in_dim, hidden, out_dim, time_dim);
-    const int KG = dppo_prec_2b(precision) ? 32 : 16;
+// the network's tensors (PACK_UPDATE's main jobs) as element ranges of the flat parameters, same segments and
+// geometry; a zero-filled segment stays as the pack left it (a plain-head actor's T_OUT: W_out has no transposed
+// slots to rewrite) and the TEMB table is derived separately (the fold launch)
+int dppo_fuse_jobs(const NetSpec& s, void* packed, FuseJob* jobs) {
+    const int KG = dppo_prec_2b(s.precision) ? 32 : 16;
+    ImageTensor t[IMG_MAXT];
+    const int nt = image_tensors(s, t);
     int n = 0;
-    auto job = [&](int kind, size_t src, size_t count, int IK, int IN, int seg) {
-        if (n >= FUSE_MAXJ) { n = FUSE_MAXJ + 1; return; }
+    for (int i = 0; i < nt; ++i) {
+        const ImageTensor& T = t[i];
+        if (T.form == T_ZERO) continue;
+        if (n == FUSE_MAXJ) return -1;
         FuseJob& J = jobs[n++];
-        J.kind = kind; J.IK = IK; J.IN = IN; J.KS = kind == 2 ? 0 : packed_ksteps(IK, KG);
-        J.lo = (int64_t)src; J.hi = (int64_t)(src + count); J.dst = P_out(packed) + L.off[seg];
-    };
-    const size_t hh = (size_t)hidden * hidden, ho = (size_t)hidden * out_dim;
-    if (time_dim > 0) job(2, F.time_w1, F.in_w - F.time_w1, 0, 0, SEG_TIME);
-    job(0, F.in_w, (size_t)in_dim * hidden, in_dim, hidden, SEG_W_IN);
-    job(2, F.in_b, hidden, 0, 0, SEG_B_IN);
-    job(0, F.l1_w, hh, hidden, hidden, SEG_W_L1);
-    job(1, F.l1_w, hh, hidden, hidden, SEG_T_L1);
-    job(2, F.l1_b, hidden, 0, 0, SEG_B_L1);
-    job(0, F.l2_w, hh, hidden, hidden, SEG_W_L2);
-    job(1, F.l2_w, hh, hidden, hidden, SEG_T_L2);
-    job(2, F.l2_b, hidden, 0, 0, SEG_B_L2);
-    job(0, F.out_w, ho, hidden, out_dim, SEG_W_OUT);
-    if (!plain) job(1, F.out_w, ho, out_dim, hidden, SEG_T_OUT);
-    job(2, F.out_b, out_dim, 0, 0, SEG_B_OUT);
-    if (const int ln_sites = time_dim > 0 ? 0 : dppo_critic_ln_sites(packed)) {   // the layer norms' tail, as add_mlp_jobs
-        job(2, F.count, critic_ln_flat_count(hidden, ln_sites), 0, 0, SEG_TIME);
-        if (n <= FUSE_MAXJ) jobs[n - 1].dst = P_out(packed) + L.total;
+        J.kind = T.form == T_FWD ? 0 : T.form == T_TRANS ? 1 : 2;
+        J.IK = T.K; J.IN = T.N; J.KS = T.form == T_COPY ? 0 : packed_ksteps(T.K, KG);
+        J.lo = (int64_t)T.src; J.hi = (int64_t)(T.src + T.count); J.dst = P_out(packed) + T.dst;
     }
-    return n <= FUSE_MAXJ ? n : -1;
+    return n;
 }
 
 static int launch_pack(PackArgs& a, int precision, hipStream_t s) {
@@ -636,143 +642,62 @@ static int launch_pack(PackArgs& a, int precision, hipStream_t s) {
     return DPPO_OK;
 }
 
-
-// Actor images whose split-sampler tables are stale (packed with PACK_UPDATE by an optimizer
-// step that deferred them): the sampler re-derives them on its own stream before its next launch
-// that reads the image (dppo_refresh_sampler_tables). The PPO row tiles never read those tables, so
-// a run of minibatches packs each actor image without them and the rollout after the update pays
-// for them once. Keyed by the image's address; stream order is the caller's, as for every launch.
-namespace {
-struct StaleTables { const void* packed; const float* params; Dims D; int precision; bool temb; };
-constexpr int MAX_STALE = 32;
-std::mutex g_stale_mu;
-StaleTables g_stale[MAX_STALE];
-int g_nstale = 0;
-
-void clear_stale(const void* packed) {
-    std::lock_guard<std::mutex> lk(g_stale_mu);
-    for (int i = 0; i < g_nstale; ++i)
-        if (g_stale[i].packed == packed) { g_stale[i] = g_stale[--g_nstale]; return; }
+// Actor images whose split-sampler tables are stale (packed with PACK_UPDATE by an optimizer step that deferred
+// them, or stepped by the fused actor step): the sampler re-derives them on its own stream before its next launch
+// that reads the image (dppo_refresh_sampler_tables). The PPO row tiles never read those tables, so a run of
+// minibatches packs each actor image without them and the rollout after the update pays for them once. The record
+// lives in the image's registry entry; stream order is the caller's. The latest update of an image decides what is
+// stale: since r05 neither a PACK_UPDATE pack nor a fused actor step rewrites TEMB (temb = true)
+int dppo_mark_tables_stale(const NetSpec& actor, const float* actor_params, const void* packed_actor, bool temb) {
+    if (dppo_image_mark_stale(packed_actor, StaleTables{actor, actor_params, temb})) return DPPO_OK;
+    return dppo_set_error(DPPO_EINVAL, "deferred sampler tables: more than %d stale images", DPPO_MAX_STALE);
 }
 
-// the latest update of an image decides what is stale: since r05 neither a PACK_UPDATE pack nor a
-// fused actor step rewrites TEMB (temb = true); the flag stays for callers that do
-int mark_stale(const Dims& D, int precision, const float* params, const void* packed, bool temb) {
-    std::lock_guard<std::mutex> lk(g_stale_mu);
-    for (int i = 0; i < g_nstale; ++i)
-        if (g_stale[i].packed == packed) { g_stale[i] = {packed, params, D, precision, temb}; return DPPO_OK; }
-    if (g_nstale == MAX_STALE) return dppo_set_error(DPPO_EINVAL, "deferred sampler tables: more than %d stale images", MAX_STALE);
-    g_stale[g_nstale++] = {packed, params, D, precision, temb};
-    return DPPO_OK;
-}
-}  // namespace
-
-// The attributes of an actor image (include/dppo.h, dppo_pack_actor_act / dppo_pack_actor_head): its
-// activation and its head, and of a critic image (dppo_pack_critic_head): its head, chead. Only images with a
-// non-default attribute are listed (ReLU / RESIDUAL, the defaults of an unlisted address, erase the entry),
-// keyed by the image's address like g_stale.
-namespace {
-struct ImageAttr { const void* packed; int act, head, chead, cln; };
-std::mutex g_attr_mu;
-std::vector<ImageAttr> g_attr;
-ImageAttr image_attr(const void* packed) {
-    std::lock_guard<std::mutex> lk(g_attr_mu);
-    for (const ImageAttr& e : g_attr)
-        if (e.packed == packed) return e;
-    return ImageAttr{packed, DPPO_ACT_RELU, DPPO_HEAD_RESIDUAL, DPPO_HEAD_RESIDUAL, DPPO_LN_OFF};
-}
-void set_image_attr(const ImageAttr& a) {
-    std::lock_guard<std::mutex> lk(g_attr_mu);
-    const bool dflt = a.act == DPPO_ACT_RELU && a.head == DPPO_HEAD_RESIDUAL && a.chead == DPPO_HEAD_RESIDUAL &&
-                      a.cln == DPPO_LN_OFF;
-    for (size_t i = 0; i < g_attr.size(); ++i)
-        if (g_attr[i].packed == a.packed) {
-            if (dflt) { g_attr[i] = g_attr.back(); g_attr.pop_back(); }
-            else g_attr[i] = a;
-            return;
-        }
-    if (!dflt) g_attr.push_back(a);
-}
-}  // namespace
-int dppo_actor_image_act(const void* packed) { return image_attr(packed).act; }
-int dppo_actor_image_head(const void* packed) { return image_attr(packed).head; }
-void dppo_actor_image_set_act(const void* packed, int activation) {
-    ImageAttr a = image_attr(packed);
-    a.act = activation;
-    set_image_attr(a);
-}
-void dppo_actor_image_set_head(const void* packed, int head) {
-    ImageAttr a = image_attr(packed);
-    a.head = head;
-    set_image_attr(a);
-}
-// the image's memory is being released: its address reads as never packed from here on (defaults, no
-// pending table refresh), whatever is allocated there next
 extern "C" int dppo_forget_image(const void* packed) {
-    if (!packed) return DPPO_OK;
-    set_image_attr(ImageAttr{packed, DPPO_ACT_RELU, DPPO_HEAD_RESIDUAL, DPPO_HEAD_RESIDUAL, DPPO_LN_OFF});
-    clear_stale(packed);
+    if (packed) dppo_image_forget(packed);
     return DPPO_OK;
 }
-int dppo_critic_image_head(const void* packed) { return image_attr(packed).chead; }
-void dppo_critic_image_set_head(const void* packed, int head) {
-    ImageAttr a = image_attr(packed);
-    a.chead = head;
-    set_image_attr(a);
-}
 
-int dppo_critic_image_ln(const void* packed) { return image_attr(packed).cln; }
-void dppo_critic_image_set_ln(const void* packed, int layernorm) {
-    ImageAttr a = image_attr(packed);
-    a.cln = layernorm;
-    set_image_attr(a);
-}
-
-// the fused step leaves the actor image's split-sampler tables stale like a PACK_UPDATE pack
-int dppo_mark_tables_stale(const Dims& D, int precision, const float* actor_params, const void* packed_actor, bool temb) {
-    return mark_stale(D, precision, actor_params, packed_actor, temb);
-}
-
-int dppo_pack_mlp(int in_dim, int hidden, int out_dim, int time_dim, int precision, const float* params,
-                  void* packed, hipStream_t s, int temb_steps, int time_stride) {
+int dppo_pack_mlp(const NetSpec& net, const float* params, void* packed, hipStream_t s) {
     PackArgs a = {};
-    int rc = add_mlp_jobs(a, in_dim, hidden, out_dim, time_dim, precision, params, packed, temb_steps, time_stride);
+    int rc = add_mlp_jobs(a, net, params, packed);
     if (rc) return rc;
-    if (temb_steps > 0) clear_stale(packed);
-    rc = launch_pack(a, precision, s);
+    if (net.temb_steps > 0) dppo_image_clear_stale(packed);
+    rc = launch_pack(a, net.precision, s);
     if (rc) return rc;
-    return dppo_pack_rt_fold(in_dim, hidden, out_dim, time_dim, precision, params, packed, temb_steps, time_stride, s);
+    return dppo_pack_rt_fold(net, params, packed, s);
 }
 
-int dppo_pack_critic_image(const Dims& D, int precision, const float* params, void* packed, hipStream_t s) {
+// the critic's jobs in a pack launch of their own
+static int dppo_pack_critic_image(const NetSpec& critic, const float* params, void* packed, hipStream_t s) {
     PackArgs a = {};
-    const int rc = add_mlp_jobs(a, D.SD, D.HC, 1, 0, precision, params, packed, 0, 1);
-    return rc ? rc : launch_pack(a, precision, s);
+    const int rc = add_mlp_jobs(a, critic, params, packed);
+    return rc ? rc : launch_pack(a, critic.precision, s);
 }
 
 // the row tiles' fold segments of an actor image whose W_OUT / T_L2 slots are final on stream s (after
 // its pack launch or a fused optimizer step): rt_fold_kernel, one wave per tile
-int dppo_pack_rt_fold(int in_dim, int hidden, int out_dim, int time_dim, int precision, const float* actor_params,
-                      void* packed_actor, int temb_steps, int time_stride, hipStream_t s) {
-    const MlpLayout L = make_mlp_layout(in_dim, hidden, out_dim, time_dim, precision, temb_steps);
-    if (time_dim <= 0) return DPPO_OK;
+int dppo_pack_rt_fold(const NetSpec& net, const float* actor_params, void* packed_actor, hipStream_t s) {
+    const int hidden = net.hidden, out_dim = net.out_dim, time_dim = net.time_dim, precision = net.precision;
+    const NetLayout L = make_mlp_layout(net);
+    if (!net.actor()) return DPPO_OK;
     if (out_dim > 32 || (dppo_prec_2b(precision) && out_dim > rt_tfold_lok(L.ks_out_t, L.KG)))
         return dppo_set_error(DPPO_EUNSUPPORTED, "row-tile fold: out_dim %d > 32", out_dim);
-    const FlatOffsets F = make_flat_offsets(in_dim, hidden, out_dim, time_dim);
+    const NetOffsets F = make_flat_offsets(net);
     if (F.in_w % 4 || F.in_b % 4 || F.l2_b % 4 || hidden % 8)
         return dppo_set_error(DPPO_EUNSUPPORTED, "row-tile fold: W_in / biases not 16-B aligned (time_dim %d)", time_dim);
     RtFoldArgs a = {};
     a.img = (uint8_t*)packed_actor; a.params = actor_params;
-    a.F = make_flat_offsets(in_dim, hidden, out_dim, time_dim);
+    a.F = F;
     a.off_wout = L.off[SEG_W_OUT]; a.off_tl2 = L.off[SEG_T_L2]; a.off_fold = L.off[SEG_RT_FOLD];
     a.off_fold0 = L.off[SEG_RT_FOLD0]; a.off_tfold = L.off[SEG_RT_TFOLD]; a.off_bout = L.off[SEG_RT_BOUT];
-    a.H = hidden; a.XD = out_dim; a.IN = in_dim; a.nt_out = L.nt_out; a.ks_h = L.ks_h; a.ks_in = L.ks_in;
+    a.H = hidden; a.XD = out_dim; a.IN = net.in_dim; a.nt_out = L.nt_out; a.ks_h = L.ks_h; a.ks_in = L.ks_in;
     a.ks_out_t = L.ks_out_t;
     a.nm = L.nt_h;
     a.nm0 = L.ks_in * L.KG / 16;   // RT_FOLD0's padded k range, 16 rows per tile
     // and the TEMB table (one block per row): the row tiles read their time embeddings from it
-    a.off_temb = L.off[SEG_TEMB]; a.TD = time_dim; a.TS = time_stride; a.R = L.temb_steps;
-    a.plain = dppo_actor_image_head(packed_actor) == DPPO_HEAD_PLAIN ? 1 : 0;
+    a.off_temb = L.off[SEG_TEMB]; a.TD = time_dim; a.TS = net.time_stride; a.R = L.temb_steps;
+    a.plain = net.plain() ? 1 : 0;
     if (time_dim > 32) return dppo_set_error(DPPO_EUNSUPPORTED, "row-tile fold: time_dim %d > 32", time_dim);
     const dim3 grid(a.nm + a.nm0 + 1 + a.R);
     DppoKtScope kt(KT_PACK_ALL, s);
@@ -783,73 +708,56 @@ int dppo_pack_rt_fold(int in_dim, int hidden, int out_dim, int time_dim, int pre
     return DPPO_OK;
 }
 
+// the record carries the NetSpec its step built from the image's attributes, which only a pack changes
 extern "C" int dppo_refresh_sampler_tables(const void* packed, void* stream) {
-    if (!packed) return DPPO_OK;
-    hipStream_t s = (hipStream_t)stream;
     StaleTables e;
-    {
-        std::lock_guard<std::mutex> lk(g_stale_mu);
-        int i = 0;
-        while (i < g_nstale && g_stale[i].packed != packed) ++i;
-        if (i == g_nstale) return DPPO_OK;
-        e = g_stale[i];
-        g_stale[i] = g_stale[--g_nstale];
-    }
+    if (!packed || !dppo_image_take_stale(packed, &e)) return DPPO_OK;
     PackArgs a = {};
-    int rc = add_mlp_jobs(a, e.D.IN, e.D.H, e.D.XD, e.D.TD, e.precision, e.params, (void*)e.packed, e.D.K, e.D.TS,
-                          e.temb ? PACK_SAMPLER_TEMB : PACK_SAMPLER);
+    const int rc = add_mlp_jobs(a, e.net, e.params, (void*)packed, e.temb ? PACK_SAMPLER_TEMB : PACK_SAMPLER);
     if (rc) return rc;
-    return launch_pack(a, e.precision, s);
+    return launch_pack(a, e.net.precision, (hipStream_t)stream);
 }
 
-int dppo_pack_models(const Dims& D, int precision, const float* actor_params, void* packed_actor,
+static void add_zero_job(PackArgs& a, void* p, size_t bytes) {
+    PackJob& J = a.j[a.njobs++];
+    J.kind = 2; J.dst = (uint8_t*)p; J.n = (int)(bytes / 4); J.threads = (J.n + 3) / 4;
+}
+
+int dppo_pack_models(const NetSpec& actor, const float* actor_params, void* packed_actor, const NetSpec& critic,
                      const float* critic_params, void* packed_critic, hipStream_t s, bool defer_sampler_tables,
                      void* const* zero_ptrs, const size_t* zero_bytes, int n_zero) {
     PackArgs a = {};
     int rc;
-    // byte ranges zeroed by the same launch (4-byte words, < 2^33 bytes each): jobs of their own. Both
-    // networks' images fill the job table on their own (13 + 11 jobs): ranges that would not fit beside
-    // the images are zeroed by a launch of their own first (the caller, staged_step, has already run
-    // AdamW, so refusing here would leave stepped parameters under stale images)
-    const int critic_jobs = critic_params && packed_critic ? 11 + (dppo_critic_ln_sites(packed_critic) ? 1 : 0) : 0;
-    const int actor_jobs = actor_params && packed_actor ? (defer_sampler_tables ? 12 : 13) : 0;
-    const int img_jobs = actor_jobs + critic_jobs;   // add_mlp_jobs' counts
-    // a layer-normed critic's 12 jobs do not fit beside the actor's 13: its image goes in a launch of its own
+    const bool has_actor = actor_params && packed_actor, has_critic = critic_params && packed_critic;
+    const int actor_what = defer_sampler_tables ? PACK_UPDATE : PACK_ALL;
+    // byte ranges zeroed by the same launch (4-byte words, < 2^33 bytes each): jobs of their own. Both networks'
+    // images fill the job table on their own: ranges that would not fit beside them are zeroed by a launch of their
+    // own first (the caller, staged_step, has already run AdamW: refusing would leave stale images)
+    const int img_jobs = (has_actor ? mlp_job_count(actor, actor_what) : 0) + (has_critic ? mlp_job_count(critic, PACK_ALL) : 0);
+    // a layer-normed critic's jobs do not fit beside the actor's: its image goes in a launch of its own
     const bool critic_alone = img_jobs > PACK_MAXJ;
+    if (n_zero > PACK_MAXJ) return dppo_set_error(DPPO_EINVAL, "pack: too many jobs in one launch");
     if (n_zero > 0 && n_zero + img_jobs > PACK_MAXJ) {
         PackArgs z = {};
-        for (int r = 0; r < n_zero; ++r) {
-            if (z.njobs == PACK_MAXJ) return dppo_set_error(DPPO_EINVAL, "pack: too many jobs in one launch");
-            PackJob& J = z.j[z.njobs++];
-            J.kind = 2; J.dst = (uint8_t*)zero_ptrs[r]; J.n = (int)(zero_bytes[r] / 4); J.threads = (J.n + 3) / 4;
-        }
-        rc = launch_pack(z, precision, s);
+        for (int r = 0; r < n_zero; ++r) add_zero_job(z, zero_ptrs[r], zero_bytes[r]);
+        rc = launch_pack(z, actor.precision, s);
         if (rc) return rc;
         n_zero = 0;
     }
-    for (int r = 0; r < n_zero; ++r) {
-        if (a.njobs == PACK_MAXJ) return dppo_set_error(DPPO_EINVAL, "pack: too many jobs in one launch");
-        PackJob& J = a.j[a.njobs++];
-        J.kind = 2; J.dst = (uint8_t*)zero_ptrs[r]; J.n = (int)(zero_bytes[r] / 4); J.threads = (J.n + 3) / 4;
-    }
-    if (actor_params && packed_actor) {
-        const bool defer = defer_sampler_tables && D.TD > 0;
-        rc = add_mlp_jobs(a, D.IN, D.H, D.XD, D.TD, precision, actor_params, packed_actor, D.K, D.TS,
-                          defer ? PACK_UPDATE : PACK_ALL);
+    for (int r = 0; r < n_zero; ++r) add_zero_job(a, zero_ptrs[r], zero_bytes[r]);
+    if (has_actor) {
+        rc = add_mlp_jobs(a, actor, actor_params, packed_actor, actor_what);
         if (rc) return rc;
-        if (defer) rc = mark_stale(D, precision, actor_params, packed_actor, true);
-        else clear_stale(packed_actor);   // a full pack makes a pending refresh moot
+        if (defer_sampler_tables) rc = dppo_mark_tables_stale(actor, actor_params, packed_actor, true);
+        else dppo_image_clear_stale(packed_actor);   // a full pack makes a pending refresh moot
         if (rc) return rc;
     }
-    if (critic_params && packed_critic && !critic_alone) {
-        rc = add_mlp_jobs(a, D.SD, D.HC, 1, 0, precision, critic_params, packed_critic, 0, 1);
+    if (has_critic) {
+        rc = critic_alone ? dppo_pack_critic_image(critic, critic_params, packed_critic, s)
+                          : add_mlp_jobs(a, critic, critic_params, packed_critic);
         if (rc) return rc;
     }
-    if (critic_alone) {
-        rc = dppo_pack_critic_image(D, precision, critic_params, packed_critic, s);
-        if (rc) return rc;
-    }
-    rc = launch_pack(a, precision, s);
-    if (rc || !(actor_params && packed_actor)) return rc;
-    return dppo_pack_rt_fold(D.IN, D.H, D.XD, D.TD, precision, actor_params, packed_actor, D.K, D.TS, s);
+    rc = launch_pack(a, actor.precision, s);
+    if (rc || !has_actor) return rc;
+    return dppo_pack_rt_fold(actor, actor_params, packed_actor, s);
 }

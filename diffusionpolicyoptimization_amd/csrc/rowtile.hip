@@ -685,10 +685,10 @@ static int launch_actor_2b(const ActorArgs& a, const ActorTilePlan& p, int act, 
     return dppo_set_error(DPPO_EUNSUPPORTED, "actor: no %d-row tile on %d waves", 16 * p.mt, p.waves);
 }
 
-int launch_actor_rowtile(const ActorArgs& a, int precision, hipStream_t s, bool dry) {
+int launch_actor_rowtile(const ActorArgs& a, const NetSpec& net, hipStream_t s, bool dry) {
     // TRAIN modes cover the 64-padded images (launch_actor_t), the others the rows given
     const int64_t rows = (a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN) ? (int64_t)a.ws.ldm : a.nrows;
-    const int act = dppo_actor_image_act(a.packed);   // the image's activation picks the instantiation
+    const int precision = net.precision, act = net.act;   // the image's activation picks the instantiation
     const ActorTilePlan p = actor_tile_plan(precision, a.H, a.XD, rows, act);
     if (precision == DPPO_BF16) return launch_actor_2b<PolicyBF16>(a, p, act, s, dry);
     if (precision == DPPO_F16) return launch_actor_2b<PolicyF16>(a, p, act, s, dry);
@@ -708,20 +708,20 @@ static int dispatch_critic_h(const CriticArgs& a, hipStream_t s, bool dry) {
 }
 // the image's head (dppo_pack_critic_head) picks the instantiation, in the dry check too
 template <class P, int MT, int WAVES, bool O4>
-static int dispatch_critic(const CriticArgs& a, hipStream_t s, bool dry) {
-    return dppo_critic_image_head(a.packed) == DPPO_HEAD_PLAIN ? dispatch_critic_h<P, MT, WAVES, O4, DPPO_HEAD_PLAIN>(a, s, dry)
-                                                               : dispatch_critic_h<P, MT, WAVES, O4, DPPO_HEAD_RESIDUAL>(a, s, dry);
+static int dispatch_critic(const CriticArgs& a, bool plain, hipStream_t s, bool dry) {
+    return plain ? dispatch_critic_h<P, MT, WAVES, O4, DPPO_HEAD_PLAIN>(a, s, dry)
+                 : dispatch_critic_h<P, MT, WAVES, O4, DPPO_HEAD_RESIDUAL>(a, s, dry);
 }
 
 // 16-row MFMA tiles per critic row tile: 2 (4, a 64-row tile, measured slower at N = 1 and equal on
 // the emulated 8-rank line; profiles/r04t_critic_tile64_ab.txt, profiles/r06n_rowtile_qd_ab.txt)
 constexpr int CRITIC_MT = 2;
-int launch_critic_rowtile(const CriticArgs& a, int precision, hipStream_t s, bool dry) {
+int launch_critic_rowtile(const CriticArgs& a, const NetSpec& net, hipStream_t s, bool dry) {
     // the image's second attribute: a layer-normed critic runs the LN axis, instantiated in rowtile_ln.hip
-    if (dppo_critic_image_ln(a.packed) == DPPO_LN_ON) return launch_critic_rowtile_ln(a, precision, s, dry);
-    return precision == DPPO_BF16 ? dispatch_critic<PolicyBF16, CRITIC_MT, 8, true>(a, s, dry)
-         : precision == DPPO_F16  ? dispatch_critic<PolicyF16, CRITIC_MT, 8, true>(a, s, dry)
-                                  : dispatch_critic<PolicyF32, CRITIC_MT, 8, true>(a, s, dry);
+    if (net.ln == DPPO_LN_ON) return launch_critic_rowtile_ln(a, net, s, dry);
+    return net.precision == DPPO_BF16 ? dispatch_critic<PolicyBF16, CRITIC_MT, 8, true>(a, net.plain(), s, dry)
+         : net.precision == DPPO_F16  ? dispatch_critic<PolicyF16, CRITIC_MT, 8, true>(a, net.plain(), s, dry)
+                                      : dispatch_critic<PolicyF32, CRITIC_MT, 8, true>(a, net.plain(), s, dry);
 }
 
 // =============================================================================================
@@ -738,9 +738,10 @@ extern "C" int dppo_logprob(const dppo_dims* d, int precision, const void* packe
     if (n == 0) return DPPO_OK;
     DPPO_CHECK(packed_ft && sched && cond && chains && (lp_elem || lp_mean), "dppo_logprob: null pointer");
     DPPO_CHECK(reward_horizon >= 1, "dppo_logprob: reward_horizon < 1");
+    const NetSpec net = actor_net(D, precision, dppo_image_attrs(packed_ft));
     ActorArgs a = {};
     a.packed = (const uint8_t*)packed_ft;
-    a.L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
+    a.L = make_mlp_layout(net);
     a.sched = sched; a.obs = cond; a.chains = chains;
     a.XD = D.XD; a.SD = D.SD; a.TD = D.TD; a.IN = D.IN; a.H = D.H; a.KF = D.KF; a.Da = D.Da; a.TS = D.TS;
     a.mode = ROWS_LOGPROB;
@@ -748,7 +749,7 @@ extern "C" int dppo_logprob(const dppo_dims* d, int precision, const void* packe
     a.lp_elem = lp_elem; a.lp_mean = lp_mean;
     a.hp.min_lp_std = min_logprob_std;
     a.hp.reward_horizon = reward_horizon;
-    return launch_actor_rowtile(a, precision, (hipStream_t)stream);
+    return launch_actor_rowtile(a, net, (hipStream_t)stream);
 }
 
 extern "C" int dppo_critic_forward(const dppo_dims* d, int precision, const void* packed_critic, const float* cond,
@@ -760,10 +761,11 @@ extern "C" int dppo_critic_forward(const dppo_dims* d, int precision, const void
     DPPO_CHECK(n >= 0, "dppo_critic_forward: n < 0");
     if (n == 0) return DPPO_OK;
     DPPO_CHECK(packed_critic && cond && values, "dppo_critic_forward: null pointer");
+    const NetSpec net = critic_net(D, precision, dppo_image_attrs(packed_critic));
     CriticArgs a = {};
     a.packed = (const uint8_t*)packed_critic;
-    a.L = make_mlp_layout(D.SD, D.HC, 1, 0, precision);
+    a.L = make_mlp_layout(net);
     a.obs = cond; a.SD = D.SD; a.HC = D.HC; a.KF = D.KF;
     a.mode = ROWS_VALUE; a.nrows = n; a.values = values;
-    return launch_critic_rowtile(a, precision, (hipStream_t)stream);
+    return launch_critic_rowtile(a, net, (hipStream_t)stream);
 }

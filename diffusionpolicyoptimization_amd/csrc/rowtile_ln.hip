@@ -12,9 +12,8 @@ static int dispatch_critic_ln(const CriticArgs& a, hipStream_t s, bool dry) {
                                 : launch_critic_t<P, MT, 2, false, WAVES, false, HEAD, true>(a, s, dry);
 }
 template <class P>
-static int dispatch_critic_ln_head(const CriticArgs& a, hipStream_t s, bool dry) {
-    return dppo_critic_image_head(a.packed) == DPPO_HEAD_PLAIN ? dispatch_critic_ln<P, DPPO_HEAD_PLAIN>(a, s, dry)
-                                                               : dispatch_critic_ln<P, DPPO_HEAD_RESIDUAL>(a, s, dry);
+static int dispatch_critic_ln_head(const CriticArgs& a, bool plain, hipStream_t s, bool dry) {
+    return plain ? dispatch_critic_ln<P, DPPO_HEAD_PLAIN>(a, s, dry) : dispatch_critic_ln<P, DPPO_HEAD_RESIDUAL>(a, s, dry);
 }
 
 // dppo_ppo_plan's field for the critic's row tile, which that query (six outputs, no image) does not have: host
@@ -34,8 +33,8 @@ extern "C" int dppo_ppo_plan_critic(const dppo_dims* d, int precision, int criti
     return DPPO_OK;
 }
 
-int launch_critic_rowtile_ln(const CriticArgs& a, int precision, hipStream_t s, bool dry) {
-    return precision == DPPO_BF16 ? dispatch_critic_ln_head<PolicyBF16>(a, s, dry)
-         : precision == DPPO_F16  ? dispatch_critic_ln_head<PolicyF16>(a, s, dry)
-                                  : dispatch_critic_ln_head<PolicyF32>(a, s, dry);
+int launch_critic_rowtile_ln(const CriticArgs& a, const NetSpec& net, hipStream_t s, bool dry) {
+    return net.precision == DPPO_BF16 ? dispatch_critic_ln_head<PolicyBF16>(a, net.plain(), s, dry)
+         : net.precision == DPPO_F16  ? dispatch_critic_ln_head<PolicyF16>(a, net.plain(), s, dry)
+                                      : dispatch_critic_ln_head<PolicyF32>(a, net.plain(), s, dry);
 }

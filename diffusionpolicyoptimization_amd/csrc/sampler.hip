@@ -470,7 +470,7 @@ extern "C" int dppo_sampler_stream_bytes(const dppo_dims* d, int precision, int6
     if (rc) return rc;
     DPPO_CHECK(bytes_per_tile, "dppo_sampler_stream_bytes: null output");
     DPPO_CHECK(dppo_prec_ok(precision), "dppo_sampler_stream_bytes: bad precision %d", precision);
-    const MlpLayout L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
+    const MlpLayout L = make_mlp_layout(actor_net(D, precision));
     const StreamGeom& g = stream_geom(dppo_prec_2b(precision), D.H);
     const int64_t ntot = D.H / 16, no = dppo_cdiv(D.XD, 16);
     const int64_t in_f = (int64_t)L.ks_in * ntot, out_f = (int64_t)L.ks_h * no;
@@ -502,25 +502,20 @@ static int dispatch_stream(const SampleArgs& a, int precision, int act, int head
                                    : dispatch_stream_h<DPPO_HEAD_RESIDUAL>(a, precision, act, s, dry);
 }
 
-// The activation of a sampler launch: its two images' (ReLU where none was recorded), which must agree:
-// one instantiation runs both actors' steps
-static int sample_act(const void* packed_base, const void* packed_ft, int* act, int* head) {
-    *act = dppo_actor_image_act(packed_ft);
-    DPPO_CHECK(dppo_actor_image_act(packed_base) == *act,
-               "dppo_sample: the base and the fine-tuned actor images carry different activations");
-    *head = dppo_actor_image_head(packed_ft);
-    DPPO_CHECK(dppo_actor_image_head(packed_base) == *head,
-               "dppo_sample: the base and the fine-tuned actor images carry different heads");
+// The network of a sampler launch: its two images' attributes (ReLU / RESIDUAL where none was recorded), which
+// must agree: one instantiation runs both actors' steps. Fills a's dimension fields and layout from it
+static int sample_net(const Dims& D, int precision, const void* packed_base, const void* packed_ft, SampleArgs& a,
+                      int* act, int* head) {
+    const ImageAttrs ft = dppo_image_attrs(packed_ft), base = dppo_image_attrs(packed_base);
+    DPPO_CHECK(base.act == ft.act, "dppo_sample: the base and the fine-tuned actor images carry different activations");
+    DPPO_CHECK(base.head == ft.head, "dppo_sample: the base and the fine-tuned actor images carry different heads");
+    *act = ft.act; *head = ft.head;
+    a.XD = D.XD; a.SD = D.SD; a.TD = D.TD; a.H = D.H; a.K = D.K; a.KF = D.KF; a.IN = D.IN;
+    a.L = make_mlp_layout(actor_net(D, precision, ft));
     return DPPO_OK;
 }
 
-// a's dimension fields and layout from the checked dims
-static void sample_geometry(const Dims& D, int precision, SampleArgs& a) {
-    a.XD = D.XD; a.SD = D.SD; a.TD = D.TD; a.H = D.H; a.K = D.K; a.KF = D.KF; a.IN = D.IN;
-    a.L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
-}
-
-// Does a kernel take the shape (a: sample_geometry's fields and E)? The split kernel where its plan
+// Does a kernel take the shape (a: sample_net's fields and E)? The split kernel where its plan
 // does, else the streaming kernel's instantiation checks (dry); launches and enqueues nothing.
 static int sample_supported(const SampleArgs& a, int precision, int act, int head, bool* split) {
     *split = sampler_cfg() == 'x' && split_plan(precision, a.H, a.XD, a.SD, a.E, a.K, a.KF).P > 0;
@@ -539,9 +534,8 @@ static int sample_impl(const dppo_dims* d, int precision, SampleArgs a, void* st
     if (a.E == 0) return DPPO_OK;
     DPPO_CHECK(a.packed_base && a.packed_ft && a.sched && (a.cond || a.cond_tagged) && a.actions,
                "dppo_sample: null pointer argument");
-    sample_geometry(D, precision, a);
     int act = DPPO_ACT_RELU, head = DPPO_HEAD_RESIDUAL;
-    rc = sample_act(a.packed_base, a.packed_ft, &act, &head);
+    rc = sample_net(D, precision, a.packed_base, a.packed_ft, a, &act, &head);
     if (rc) return rc;
     bool split = false;
     rc = sample_supported(a, precision, act, head, &split);
@@ -660,9 +654,8 @@ extern "C" int dppo_sample_step(const dppo_dims* d, int precision, const void* p
         DPPO_CHECK(dppo_prec_ok(precision), "dppo_sample: bad precision %d", precision);
         SampleArgs q = {};
         q.E = n_envs;
-        sample_geometry(D, precision, q);
         int act = DPPO_ACT_RELU, head = DPPO_HEAD_RESIDUAL;
-        rc = sample_act(packed_base, packed_ft, &act, &head);
+        rc = sample_net(D, precision, packed_base, packed_ft, q, &act, &head);
         if (rc) return rc;
         bool split = false;
         rc = sample_supported(q, precision, act, head, &split);

@@ -214,17 +214,13 @@ extern "C" int dppo_pack_all(const dppo_dims* d, int precision, const float* act
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
     DPPO_CHECK(!packed_actor == !actor_params && !packed_critic == !critic_params,
                "dppo_pack_all: a packed image needs its parameters");
-    const int old_head = packed_actor ? dppo_actor_image_head(packed_actor) : DPPO_HEAD_RESIDUAL;
-    if (packed_actor) dppo_actor_image_set_head(packed_actor, DPPO_HEAD_RESIDUAL);   // = dppo_pack_actor, before the pack
-    // no layer norm either (the critic's pack jobs follow it, so before the pack like the actor's head)
-    const int old_ln = packed_critic ? dppo_critic_image_ln(packed_critic) : DPPO_LN_OFF;
-    if (packed_critic) dppo_critic_image_set_ln(packed_critic, DPPO_LN_OFF);
-    rc = dppo_pack_models(D, precision, actor_params, packed_actor, critic_params, packed_critic, (hipStream_t)stream);
-    if (rc != DPPO_OK && packed_critic) dppo_critic_image_set_ln(packed_critic, old_ln);
-    if (rc == DPPO_OK && packed_actor) dppo_actor_image_set_act(packed_actor, DPPO_ACT_RELU);
-    if (rc == DPPO_OK && packed_critic) dppo_critic_image_set_head(packed_critic, DPPO_HEAD_RESIDUAL);   // = dppo_pack_critic
-    if (rc != DPPO_OK && packed_actor) dppo_actor_image_set_head(packed_actor, old_head);
-    return rc;
+    // = dppo_pack_actor + dppo_pack_critic: ReLU / RESIDUAL for the actor, RESIDUAL / no layer norm for the critic
+    rc = dppo_pack_models(actor_net(D, precision), actor_params, packed_actor, critic_net(D, precision), critic_params,
+                          packed_critic, (hipStream_t)stream);
+    if (rc != DPPO_OK) return rc;
+    if (packed_actor) dppo_image_commit(packed_actor, ImageAttrs());
+    if (packed_critic) dppo_image_commit(packed_critic, ImageAttrs());
+    return DPPO_OK;
 }
 
 extern "C" int dppo_feistel_permute(int64_t first, int64_t count, int64_t n, uint64_t seed, int epoch, int64_t* out,
@@ -286,29 +282,27 @@ enum MbPart { MB_ACTOR = 1, MB_CRITIC = 2, MB_WHOLE = 3, MB_ACTOR_TILES = 4, MB_
 // the atomically accumulated outputs a minibatch half (or the whole) zeroes first: gradients (entry
 // 0), metrics (actor: 0, 2..15; critic: 1), pl2 | bucket sums, cpl2 | stats | crow_cnt. Entries 1..3
 // are what dppo_ppo_clear_ranges reports (the gradients are cleared by the optimizer step's AdamW)
-// ln_sites: the norms of a layer-normed critic image, whose gradient tail (dgamma / dbeta, added by the row
-// tiles) follows the critic's eight tensors in `grads` and is zeroed with them
-static ZeroArgs minibatch_zero_args(const Dims& D, const PpoWorkspace& ws, float* grads, double* metrics, MbPart part,
-                                    int ln_sites = 0) {
-    const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
-    FlatOffsets FC = make_flat_offsets(D.SD, D.HC, 1, 0);
-    FC.count += critic_ln_flat_count(D.HC, ln_sites);
+// A layer-normed critic's gradient tail (dgamma / dbeta, added by the row tiles) follows the critic's eight tensors
+// in `grads` and is zeroed with them
+static ZeroArgs minibatch_zero_args(const Dims& D, const NetSpec& critic, const PpoWorkspace& ws, float* grads,
+                                    double* metrics, MbPart part) {
+    const size_t na = make_flat_offsets(actor_net(D)).count, nc = make_flat_offsets(critic).count_all;
     ZeroArgs z = {};
     // pl2 | pa0 | gseg: the bucket rows the dW adds into, whole wave rows of 16 (K' <= 64)
     const size_t actor_acc = (size_t)((const uint8_t*)(ws.gseg + (size_t)dppo_cdiv(D.KF, 16) * 16 * D.H) - (const uint8_t*)ws.pl2);
     const size_t critic_acc = (size_t)((const uint8_t*)(ws.crow_cnt + 1) - (const uint8_t*)ws.cpl2);
     if (part == MB_WHOLE) {
-        z.p[0] = grads; z.n[0] = (FA.count + FC.count) * sizeof(float);
+        z.p[0] = grads; z.n[0] = (na + nc) * sizeof(float);
         z.p[1] = metrics; z.n[1] = 16 * sizeof(double);
         z.p[2] = ws.pl2; z.n[2] = actor_acc;
         z.p[3] = ws.cpl2; z.n[3] = critic_acc;
     } else if (part == MB_ACTOR || part == MB_ACTOR_TILES) {
-        z.p[0] = grads; z.n[0] = FA.count * sizeof(float);
+        z.p[0] = grads; z.n[0] = na * sizeof(float);
         z.p[1] = metrics; z.n[1] = sizeof(double);
         z.p[2] = metrics + 2; z.n[2] = 14 * sizeof(double);
         z.p[3] = ws.pl2; z.n[3] = actor_acc;
     } else if (part == MB_CRITIC) {
-        z.p[0] = grads ? grads + FA.count : nullptr; z.n[0] = FC.count * sizeof(float);
+        z.p[0] = grads ? grads + na : nullptr; z.n[0] = nc * sizeof(float);
         z.p[1] = metrics + 1; z.n[1] = sizeof(double);
         z.p[2] = ws.cpl2; z.n[2] = critic_acc;
     }
@@ -325,7 +319,7 @@ extern "C" int dppo_ppo_clear_ranges(const dppo_dims* d, int precision, int batc
     DPPO_CHECK(part == 1 || part == 2 || part == 3 || part == 4, "dppo_ppo_clear_ranges: part must be 1, 2, 3 or 4");
     DPPO_CHECK(D.KF <= PPO_MAX_BUCKETS, "dppo_ppo_clear_ranges: ft_denoising_steps %d > %d", D.KF, PPO_MAX_BUCKETS);
     const PpoWorkspace ws = make_ppo_workspace(D, precision, batch_rows, (uint8_t*)workspace);
-    const ZeroArgs z = minibatch_zero_args(D, ws, nullptr, metrics, (MbPart)part);
+    const ZeroArgs z = minibatch_zero_args(D, critic_net(D), ws, nullptr, metrics, (MbPart)part);
     int n = 0;
     for (int r = 1; r < 4; ++r)
         if (z.p[r]) { ptrs[n] = z.p[r]; bytes[n] = z.n[r]; ++n; }
@@ -360,7 +354,7 @@ static float* grad_at(float* g, size_t off) { return g ? g + off : nullptr; }
 // keeps the zeros of the minibatch's zeroing (no factored form to defer)
 static void actor_dw_items(const Dims& D, const PpoWorkspace& ws, float* ga, bool pretrain, bool l2_def, DWItem (&it)[4],
                            bool plain = false) {
-    const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
+    const FlatOffsets FA = make_flat_offsets(actor_net(D));
     it[0] = pretrain ? DWItem{ws.a0T, D.IN, ws.dh1T, D.H, grad_at(ga, FA.in_w), EXTRA_NONE, nullptr}
                      : DWItem{ws.a0T, D.IN, ws.dh1T, D.H, grad_at(ga, FA.in_w), EXTRA_ONEHOT, ws.gseg, D.KF};
     it[1] = DWItem{ws.u1T, D.H, ws.dh2T, D.H, grad_at(ga, FA.l1_w), EXTRA_ONES, grad_at(ga, FA.l1_b)};
@@ -374,7 +368,7 @@ static void actor_dw_items(const Dims& D, const PpoWorkspace& ws, float* ga, boo
 // sums -> l2_b, an HC x HC problem like problem 1 (cpl2 is not written: the out layer reads mish(h3), so there is
 // no factored form), and ch3T holds u3
 static void critic_dw_items(const Dims& D, const PpoWorkspace& ws, float* gc, DWItem (&it)[4], bool plain = false) {
-    const FlatOffsets FC = make_flat_offsets(D.SD, D.HC, 1, 0);
+    const FlatOffsets FC = make_flat_offsets(critic_net(D));
     it[0] = DWItem{ws.csT, D.SD, ws.cdh1T, D.HC, grad_at(gc, FC.in_w), EXTRA_ONES, grad_at(gc, FC.in_b)};
     it[1] = DWItem{ws.cu1T, D.HC, ws.cdh2T, D.HC, grad_at(gc, FC.l1_w), EXTRA_ONES, grad_at(gc, FC.l1_b)};
     it[2] = plain ? DWItem{ws.cu2T, D.HC, ws.cdh3T, D.HC, grad_at(gc, FC.l2_w), EXTRA_ONES, grad_at(gc, FC.l2_b)}
@@ -455,7 +449,10 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     hipStream_t s = (hipStream_t)m.stream;
     const PpoWorkspace ws = make_ppo_workspace(D, precision, rows, (uint8_t*)m.workspace);
     DPPO_CHECK(ws.total < ((size_t)1 << 31), "dppo_ppo_minibatch: workspace for %d rows exceeds 2 GiB", rows);
-    const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
+    // the images' attributes, read once: everything below follows these two values
+    const NetSpec anet = actor_net(D, precision, dppo_image_attrs(m.packed_ft));
+    const NetSpec cnet = critic_net(D, precision, dppo_image_attrs(m.packed_critic));
+    const FlatOffsets FA = make_flat_offsets(anet);
     float* ga = m.grads;
     float* gc = m.grads + FA.count;
     DPPO_CHECK(part >= MB_ACTOR && part <= MB_ACTOR_DW, "dppo_ppo_minibatch: bad part %d", (int)part);
@@ -478,14 +475,14 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     lh.clip_vloss = hp->clip_vloss_coef > 0.f && hp->old_values ? hp->clip_vloss_coef : 0.f;
     lh.old_values = lh.clip_vloss > 0.f ? hp->old_values : nullptr;
     // the actor's l2 gradient left factored in its own grads region (include/dppo.h)
-    const bool plain = dppo_actor_image_head(m.packed_ft) == DPPO_HEAD_PLAIN;   // no l2: nothing to defer
+    const bool plain = anet.plain();   // no l2: nothing to defer
     const bool l2_def = (hp->flags & DPPO_PPO_L2_DEFERRED) != 0 && !plain;
-    const bool cplain = dppo_critic_image_head(m.packed_critic) == DPPO_HEAD_PLAIN;
-    const int cln_sites = dppo_critic_ln_sites(m.packed_critic);   // > 0: the critic's gradients end in the norms' tail
+    const bool cplain = cnet.plain();
+    const int cln_sites = cnet.ln_sites();   // > 0: the critic's gradients end in the norms' tail
 
     ActorArgs aa = {};
     aa.packed = (const uint8_t*)m.packed_ft;
-    aa.L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
+    aa.L = make_mlp_layout(anet);
     aa.sched = m.sched; aa.obs = m.obs; aa.chains = m.chains;
     aa.XD = D.XD; aa.SD = D.SD; aa.TD = D.TD; aa.IN = D.IN; aa.H = D.H; aa.KF = D.KF; aa.Da = D.Da; aa.TS = D.TS;
     aa.mode = ROWS_TRAIN; aa.nrows = rows; aa.fk = fk; aa.start = m.start; aa.row_index = m.row_index;
@@ -493,22 +490,22 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
 
     CriticArgs ca = {};
     ca.packed = (const uint8_t*)m.packed_critic;
-    ca.L = make_mlp_layout(D.SD, D.HC, 1, 0, precision);
+    ca.L = make_mlp_layout(cnet);
     ca.obs = m.obs; ca.SD = D.SD; ca.HC = D.HC; ca.KF = D.KF; ca.mode = ROWS_TRAIN; ca.nrows = rows;
     ca.fk = fk; ca.start = m.start; ca.row_index = m.row_index; ca.returns = m.returns; ca.hp = lh; ca.ws = ws;
     ca.metrics = m.metrics;
-    ca.gln = cln_sites ? gc + make_flat_offsets(D.SD, D.HC, 1, 0).count : nullptr;
+    ca.gln = cln_sites ? gc + make_flat_offsets(cnet).ln : nullptr;
     ca.ln_unscale = 1.f / gscale;
 
     // Every row tile this part runs must have an instantiation before anything is launched: a geometry
     // the dispatch rejects leaves the gradients, the metrics and the stream's sample counts (which the
     // critic's last launch re-zeroes) as they were
     if (part != MB_CRITIC && part != MB_ACTOR_DW) {
-        rc = launch_actor_rowtile(aa, precision, s, true);
+        rc = launch_actor_rowtile(aa, anet, s, true);
         if (rc) return rc;
     }
     if (part == MB_CRITIC || part == MB_WHOLE) {
-        rc = launch_critic_rowtile(ca, precision, s, true);
+        rc = launch_critic_rowtile(ca, cnet, s, true);
         if (rc) return rc;
     }
     if (part != MB_CRITIC && part != MB_ACTOR_TILES) {   // the parts that end in the time-MLP backward
@@ -522,7 +519,7 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     // MB_ACTOR_TILES zeroed its outputs
     if (part != MB_ACTOR_DW && !(hp->flags & DPPO_PPO_PRECLEARED)) {
         DppoKtScope kt(KT_ZERO, s);
-        rc = launch_zero(minibatch_zero_args(D, ws, m.grads, m.metrics, part, cln_sites), 16, s);
+        rc = launch_zero(minibatch_zero_args(D, cnet, ws, m.grads, m.metrics, part), 16, s);
         if (rc) return rc;
     }
     const double* stats = m.adv_stats;
@@ -550,7 +547,7 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
             DPPO_HIP(hipGetLastError());
             ca.crow_n = ws.crow_n; ca.crow_mult = crit_cnt; ca.crow_cnt = ws.crow_cnt;
         }
-        int rc_ = launch_critic_rowtile(ca, precision, st);
+        int rc_ = launch_critic_rowtile(ca, cnet, st);
         if (rc_) return rc_;
         DWItem items[4];
         critic_dw_items(D, ws, gc, items, cplain);
@@ -577,7 +574,7 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     if (part == MB_CRITIC) return critic_half(s);
     if (part != MB_WHOLE) {   // the actor's half, or its row tiles / its weight gradients alone
         if (part != MB_ACTOR_DW) {
-            rc = launch_actor_rowtile(aa, precision, s);
+            rc = launch_actor_rowtile(aa, anet, s);
             if (rc) return rc;
         }
         if (part == MB_ACTOR_TILES) return DPPO_OK;
@@ -595,13 +592,13 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
         rc = critic_half(side->stream);
         if (rc) return rc;
         DPPO_HIP(hipEventRecord(side->join, side->stream));
-        rc = launch_actor_rowtile(aa, precision, s);
+        rc = launch_actor_rowtile(aa, anet, s);
         if (rc) return rc;
         rc = actor_grads();
         if (rc) return rc;
         DPPO_HIP(hipStreamWaitEvent(s, side->join, 0));
     } else {
-        rc = launch_actor_rowtile(aa, precision, s);
+        rc = launch_actor_rowtile(aa, anet, s);
         if (rc) return rc;
         rc = critic_half(s);
         if (rc) return rc;
@@ -675,11 +672,12 @@ extern "C" int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const 
     hipStream_t s = (hipStream_t)stream;
     const PpoWorkspace ws = make_ppo_workspace(D, precision, rows, (uint8_t*)workspace);
     DPPO_CHECK(ws.total < ((size_t)1 << 31), "dppo_pretrain_minibatch: workspace for %d rows exceeds 2 GiB", rows);
-    const FlatOffsets FA = make_flat_offsets(D.IN, D.H, D.XD, D.TD);
+    const NetSpec anet = actor_net(D, precision, dppo_image_attrs(packed_actor));
+    const FlatOffsets FA = make_flat_offsets(anet);
     float* ga = grads;
     ActorArgs aa = {};
     aa.packed = (const uint8_t*)packed_actor;
-    aa.L = make_mlp_layout(D.IN, D.H, D.XD, D.TD, precision, D.K);
+    aa.L = make_mlp_layout(anet);
     aa.sched = sched; aa.obs = cond; aa.chains = x_start;
     aa.XD = D.XD; aa.SD = D.SD; aa.TD = D.TD; aa.IN = D.IN; aa.H = D.H; aa.KF = D.K; aa.Da = D.Da; aa.TS = 1;
     aa.mode = ROWS_PRETRAIN; aa.nrows = rows; aa.ws = ws; aa.metrics = metrics;
@@ -687,7 +685,7 @@ extern "C" int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const 
     // loss = mean over global_rows * XD elements of (eps - noise)^2 (diffusion.py:192)
     const float gscale = dppo_grad_scale_rows(precision, global_rows);
     aa.pre_scale = 2.f * loss_scale / ((float)global_rows * (float)D.XD) * gscale;
-    rc = launch_actor_rowtile(aa, precision, s, true);   // rejected geometries leave the outputs untouched
+    rc = launch_actor_rowtile(aa, anet, s, true);   // rejected geometries leave the outputs untouched
     if (rc) return rc;
     ZeroArgs z = {};
     z.p[0] = grads; z.n[0] = FA.count * sizeof(float);
@@ -695,12 +693,12 @@ extern "C" int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const 
     z.p[2] = ws.pl2; z.n[2] = (size_t)((const uint8_t*)ws.gseg - (const uint8_t*)ws.pl2);   // pl2 | pa0
     rc = launch_zero(z, 256, s);
     if (rc) return rc;
-    rc = launch_actor_rowtile(aa, precision, s);
+    rc = launch_actor_rowtile(aa, anet, s);
     if (rc) return rc;
 
     // the in-layer's bias and time-MLP gradients come from K bucket sums (seg_reduce + time_bwd)
     DWItem items[4];
-    const bool plain = dppo_actor_image_head(packed_actor) == DPPO_HEAD_PLAIN;
+    const bool plain = anet.plain();
     actor_dw_items(D, ws, ga, true, false, items, plain);
     rc = launch_dw(DWTile::ACTOR, precision, items, 4, ws, 1.f / gscale, nullptr, PRETRAIN_MIN_CHUNK_ROWS, s);
     if (rc) return rc;

@@ -69,6 +69,8 @@ _SIGNATURES = {
     "dppo_pack_critic": (_I, [_DIMS, _I, _P, _P, _P]),
     "dppo_pack_critic_head": (_I, [_DIMS, _I, _I, _P, _P, _P]),
     "dppo_forget_image": (_I, [_P]),
+    "dppo_sched_set_params": (_I, [_P, _F, _I]),
+    "dppo_forget_sched": (_I, [_P]),
     "dppo_pack_critic_ln": (_I, [_DIMS, _I, _I, _I, _P, _P, _P]),
     "dppo_critic_param_count_ln": (_SZ, [_DIMS, _I, _I]),
     "dppo_critic_packed_bytes_ln": (_SZ, [_DIMS, _I, _I, _I]),

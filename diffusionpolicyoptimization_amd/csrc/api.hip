@@ -1,6 +1,7 @@
 // api.hip — C-ABI plumbing of libdppo_hip.so: errors, dimension checks, sizes, packing entry points.
 #include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
 #include <mutex>
 #include <vector>
 #include "dppo_common.cuh"
@@ -113,6 +114,44 @@ extern "C" int dppo_pack_critic_head(const dppo_dims* d, int precision, int head
 }
 extern "C" int dppo_pack_critic(const dppo_dims* d, int precision, const float* params, void* packed, void* stream) {
     return dppo_pack_critic_head(d, precision, DPPO_HEAD_RESIDUAL, params, packed, stream);
+}
+
+// ---- the schedule table's attributes (include/dppo.h, the schedule table) ----
+extern "C" int dppo_sched_set_params(const float* sched, float denoised_clip, int predict_x0) {
+    DPPO_CHECK(sched, "dppo_sched_set_params: null schedule table");
+    DPPO_CHECK(denoised_clip == denoised_clip, "dppo_sched_set_params: denoised_clip is NaN");
+    DPPO_CHECK(!(denoised_clip < 0.f) || __builtin_isinf(denoised_clip),
+               "dppo_sched_set_params: negative denoised_clip %g (0 or an infinity: no clip)", (double)denoised_clip);
+    DPPO_CHECK(predict_x0 == 0 || predict_x0 == 1, "dppo_sched_set_params: predict_x0 must be 0 or 1");
+    if (predict_x0) {
+        // a DDIM table has eval_floor 0 in every row, a DDPM table 1e-3 (the table's columns, include/dppo.h);
+        // setup-time and blocking: the row is read back before the record changes (a table in plain host
+        // memory, which no kernel can take but a host-only caller may describe, is read in place)
+        float row0[DPPO_SCHED_COLS];
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, sched) == hipSuccess && at.type != hipMemoryTypeUnregistered) {
+            DPPO_HIP(hipMemcpy(row0, sched, sizeof(row0), hipMemcpyDefault));
+        } else {
+            (void)hipGetLastError();
+            memcpy(row0, sched, sizeof(row0));
+        }
+        DPPO_CHECK(row0[5] != 0.f, "dppo_sched_set_params: DDIM requires predicting epsilon (the table holds DDIM rows)");
+    }
+    SchedParams p;
+    p.clip = denoised_clip > 0.f && !__builtin_isinf(denoised_clip) ? denoised_clip : __builtin_inff();
+    p.predict_x0 = predict_x0;
+    dppo_sched_commit(sched, p);
+    return DPPO_OK;
+}
+extern "C" int dppo_forget_sched(const float* sched) {
+    if (sched) dppo_sched_forget(sched);
+    return DPPO_OK;
+}
+int dppo_sched_lookup(const Dims& D, const float* sched, const char* who, SchedParams* out) {
+    *out = dppo_sched_params(sched);
+    DPPO_CHECK(!(out->predict_x0 && D.TS > 1),
+               "%s: DDIM requires predicting epsilon (an x0-prediction schedule table with time_stride %d)", who, D.TS);
+    return DPPO_OK;
 }
 
 // ---- kernel timer: (start, end) event pairs per launch of a timed kernel, summed on read ----

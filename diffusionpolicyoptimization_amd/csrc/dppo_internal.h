@@ -64,6 +64,11 @@ inline float dppo_grad_scale_rows(int p, int64_t global_rows) {
 }
 
 #define DPPO_CHECK(cond, ...) do { if (!(cond)) return dppo_set_error(DPPO_EINVAL, __VA_ARGS__); } while (0)
+// The schedule table's record (image_registry.h), read once by an extern "C" entry `who`, and the refusal every
+// entry shares: x0-prediction has no DDIM form (the reference asserts "DDIM requires predicting epsilon").
+// DPPO_EINVAL before anything is enqueued
+int dppo_sched_lookup(const Dims& D, const float* sched, const char* who, SchedParams* out);
+
 #define DPPO_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return dppo_hip_fail(e_, #x); } while (0)
 
 // ---- kernel timer (ABI 10, dppo_kernel_timing*): HIP events around the launches of the kernels

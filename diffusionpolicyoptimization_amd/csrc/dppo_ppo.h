@@ -117,7 +117,11 @@ struct ActorArgs {
     const int* tsteps;     // [rows] t in [0, K)
     const float* noise;    // [rows][XD]
     const float* qsched;   // [K][2] sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod)
-    float pre_scale;       // d loss / d eps = pre_scale * (eps - noise)
+    float pre_scale;       // d loss / d eps = pre_scale * (eps - target)
+    // the schedule table's attributes (SchedParams): the clip bound of x_recon (+inf = none) in the LOGPROB and
+    // TRAIN modes; the pretraining target, x_start instead of the noise (predict_epsilon=False)
+    float x0_clip;
+    int x0_target;
     // tile range of one launch: image rows [row0, row_end); row_end = 0: all rows of the mode
     int64_t row0, row_end;
 };

@@ -36,6 +36,7 @@ struct SampleArgs {
     uint32_t call_id;
     int E, env_offset, deterministic;
     float min_std, randn_clip, final_clip;
+    float x0_clip;        // the table's denoised_clip_value (SchedParams; +inf = none), filled by sample_impl
     int XD, SD, TD, H, K, KF, IN;
     MlpLayout L;          // same layout for base and ft
 };

@@ -7,6 +7,8 @@ namespace {
 struct Entry { const void* packed; ImageAttrs attrs; bool stale; StaleTables rec; };
 std::mutex g_mu;
 std::vector<Entry> g_images;
+struct SchedEntry { const void* sched; SchedParams p; };
+std::vector<SchedEntry> g_scheds;   // only tables whose parameters are not the defaults
 
 Entry* find(const void* packed) {
     for (Entry& e : g_images)
@@ -77,4 +79,34 @@ void dppo_image_forget(const void* packed) {
         *e = g_images.back();
         g_images.pop_back();
     }
+}
+
+SchedParams dppo_sched_params(const void* sched) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (const SchedEntry& e : g_scheds)
+        if (e.sched == sched) return e.p;
+    return SchedParams();
+}
+
+namespace {
+void sched_erase_locked(const void* sched) {
+    for (SchedEntry& e : g_scheds)
+        if (e.sched == sched) {
+            e = g_scheds.back();
+            g_scheds.pop_back();
+            return;
+        }
+}
+}  // namespace
+
+void dppo_sched_forget(const void* sched) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    sched_erase_locked(sched);
+}
+
+void dppo_sched_commit(const void* sched, SchedParams p) {
+    std::lock_guard<std::mutex> lk(g_mu);   // one critical section: no reader sees the defaults in between
+    sched_erase_locked(sched);
+    if (p.clip == 1.f && !p.predict_x0) return;
+    g_scheds.push_back(SchedEntry{sched, p});
 }

@@ -23,3 +23,14 @@ bool dppo_image_take_stale(const void* packed, StaleTables* rec);
 void dppo_image_clear_stale(const void* packed);
 // the image's memory is being released: its address reads as never packed from here on
 void dppo_image_forget(const void* packed);
+
+// A schedule table's attributes, keyed by the table's device address like an image's (include/dppo.h, the schedule
+// table): the clip bound of x_recon (+inf: none) and whether the network predicts x0 instead of epsilon. The same
+// rule: an extern "C" entry reads the record once and passes it down by value.
+struct SchedParams { float clip = 1.f; int predict_x0 = 0; };
+// defaults ({1.0, epsilon}) for an address nobody recorded
+SchedParams dppo_sched_params(const void* sched);
+// all-default parameters erase the entry
+void dppo_sched_commit(const void* sched, SchedParams p);
+// the table's memory is being released: its address reads as never recorded from here on
+void dppo_sched_forget(const void* sched);

@@ -77,6 +77,28 @@ struct ActorSmem {
     }
 };
 
+
+// The epilogue's x_recon and posterior mean with their roundings stated, not left to FMA contraction: the clip bound
+// became a kernel argument (the table's denoised_clip_value), and the contraction the compiler picks moves with the
+// code around it. These are the forms every instantiation compiled to while the bound was the literal 1:
+//   x_recon = rnd(c0 x) - rnd(c1 eps);  mu = fma(c3, x, rnd(c2 x_recon));
+//   the learnable-eta term's x0 = fma(c0, x, -rnd(c1 eps))
+__device__ inline float rt_xrecon(float c0, float c1, float x, float eps) {
+#pragma clang fp contract(off)
+    const float p0 = c0 * x, p1 = c1 * eps;
+    return p0 - p1;
+}
+__device__ inline float rt_mu(float c2, float c3, float xr, float x) {
+#pragma clang fp contract(off)
+    const float t = c2 * xr;
+    return __builtin_fmaf(c3, x, t);
+}
+__device__ inline float rt_xrecon_eta(float c0, float c1, float x, float eps) {
+#pragma clang fp contract(off)
+    const float t = c1 * eps;
+    return __builtin_fmaf(c0, x, -t);
+}
+
 // ACT (DPPO_ACT_RELU / DPPO_ACT_MISH): the image's activation at the block's two sites, u1 = act(h1) and
 // a = act(h2) (mlp.py:192-193, 202-203). relu' is read off the activation's sign (one bit per element);
 // mish is not monotone, so a Mish TRAIN tile keeps h1 and h2 themselves in registers until the
@@ -193,11 +215,12 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
         const int r = i / XD, q = i % XD, n = rn[r];
         float vp = 0.f, vn = 0.f;
         if (n >= 0 && pre) {
-            // q_sample (diffusion.py:196-202): x_t = sqrt(ac_t) x_0 + sqrt(1 - ac_t) noise; xn keeps the noise
+            // q_sample (diffusion.py:196-202): x_t = sqrt(ac_t) x_0 + sqrt(1 - ac_t) noise; xn keeps the loss's target
             const int t = KF - 1 - rj[r];
             const float z = a.noise[(size_t)n * XD + q];
-            vp = a.qsched[2 * t] * a.chains[(size_t)n * XD + q] + a.qsched[2 * t + 1] * z;
-            vn = z;
+            const float x0 = a.chains[(size_t)n * XD + q];
+            vp = a.qsched[2 * t] * x0 + a.qsched[2 * t + 1] * z;
+            vn = a.x0_target ? x0 : z;   // the loss's target: x_start or the noise
         } else if (n >= 0) {
             const float* c = a.chains + ((size_t)n * (KF + 1) + rj[r]) * XD + q;
             vp = c[0]; vn = c[XD];   // chains_prev = chains[:, j], chains_next = chains[:, j+1]
@@ -377,10 +400,10 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) eps += part[(w * ROWS + r) * (16 * NO) + q];
         const float x = xp[r * XD + q];
-        float xr = sc[0] * x - sc[1] * eps;
-        e_uc[idx] = fabsf(xr) <= 1.f ? 1.f : 0.f;
-        xr = fminf(fmaxf(xr, -1.f), 1.f);
-        const float mu = sc[2] * xr + sc[3] * x;
+        float xr = rt_xrecon(sc[0], sc[1], x, eps);
+        e_uc[idx] = fabsf(xr) <= a.x0_clip ? 1.f : 0.f;
+        xr = __builtin_amdgcn_fmed3f(xr, -a.x0_clip, a.x0_clip);
+        const float mu = rt_mu(sc[2], sc[3], xr, x);
         const float z = (xn[r * XD + q] - mu) / sd;
         const float lp = -0.5f * z * z - logf(sd) - LOG_2PI_HALF;
         e_lp[idx] = lp;
@@ -455,7 +478,7 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
         const int q = dup ? qa - LOK : qa;
         float d = 0.f;
         if (pre) {
-            // p_losses, predict_epsilon (diffusion.py:186-194): mean((eps - noise)^2)
+            // p_losses (diffusion.py:186-194): mean((out - target)^2), target = noise (predict_epsilon) or x_start
             if (q < XD && rn[r] >= 0) {
                 float eps = bo[q];
 #pragma unroll
@@ -484,7 +507,7 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
                 float eps = bo[q];   // the out-layer partials in tB are still live (as in the pretrain branch)
 #pragma unroll
                 for (int w = 0; w < WAVES; ++w) eps += part[(w * ROWS + r) * (16 * NO) + q];
-                const float x0 = fminf(fmaxf(sc[0] * x - sc[1] * eps, -1.f), 1.f);
+                const float x0 = __builtin_amdgcn_fmed3f(rt_xrecon_eta(sc[0], sc[1], x, eps), -a.x0_clip, a.x0_clip);
                 const float ep2 = (x - x0 / sc[0]) * sc[0] / sc[1];
                 const float dd = sc[3] * sc[1] / sc[0];
                 const bool free_sig = sig > 1e-10f * 1.0001f;
@@ -739,7 +762,11 @@ extern "C" int dppo_logprob(const dppo_dims* d, int precision, const void* packe
     DPPO_CHECK(packed_ft && sched && cond && chains && (lp_elem || lp_mean), "dppo_logprob: null pointer");
     DPPO_CHECK(reward_horizon >= 1, "dppo_logprob: reward_horizon < 1");
     const NetSpec net = actor_net(D, precision, dppo_image_attrs(packed_ft));
+    SchedParams sp;
+    rc = dppo_sched_lookup(D, sched, "dppo_logprob", &sp);
+    if (rc) return rc;
     ActorArgs a = {};
+    a.x0_clip = sp.clip;
     a.packed = (const uint8_t*)packed_ft;
     a.L = make_mlp_layout(net);
     a.sched = sched; a.obs = cond; a.chains = chains;

@@ -367,7 +367,7 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
             const float* sc = sch + t * DPPO_SCHED_COLS;
             const float x = xs[tid];
             const float sd = sampler_noise_std(a, sc);
-            float xn = ddpm_post(sc[0], sc[1], sc[2], sc[3], sd, x, eps, zt[i * 16 * XD + tid]);   // (:198-242, :301-320)
+            float xn = ddpm_post(sc[0], sc[1], sc[2], sc[3], sd, x, eps, zt[i * 16 * XD + tid], a.x0_clip);   // (:198-242, :301-320)
             if (a.final_clip > 0.f && i == K - 1) xn = fminf(fmaxf(xn, -a.final_clip), a.final_clip);
             xs[tid] = xn;
             a0[r * lda0 + q] = P::cvt(xn);                      // next step's input
@@ -525,7 +525,8 @@ static int sample_supported(const SampleArgs& a, int precision, int act, int hea
 // The one launch path: `a` carries the caller's pointers and scalars (fields it does not use are
 // zero); the dimension fields and the layout are filled here, a shape no kernel takes is refused,
 // tables an optimizer step deferred are refreshed, and the split kernel or the streaming kernel runs.
-static int sample_impl(const dppo_dims* d, int precision, SampleArgs a, void* stream) {
+// known: the table's record when the entry has read it already (the read-once rule)
+static int sample_impl(const dppo_dims* d, int precision, SampleArgs a, void* stream, const SchedParams* known = nullptr) {
     Dims D;
     int rc = dppo_check_dims(d, &D);
     if (rc) return rc;
@@ -534,6 +535,10 @@ static int sample_impl(const dppo_dims* d, int precision, SampleArgs a, void* st
     if (a.E == 0) return DPPO_OK;
     DPPO_CHECK(a.packed_base && a.packed_ft && a.sched && (a.cond || a.cond_tagged) && a.actions,
                "dppo_sample: null pointer argument");
+    SchedParams sp;
+    if (known) sp = *known;
+    else if ((rc = dppo_sched_lookup(D, a.sched, "dppo_sample", &sp)) != DPPO_OK) return rc;
+    a.x0_clip = sp.clip;
     int act = DPPO_ACT_RELU, head = DPPO_HEAD_RESIDUAL;
     rc = sample_net(D, precision, a.packed_base, a.packed_ft, a, &act, &head);
     if (rc) return rc;
@@ -654,6 +659,9 @@ extern "C" int dppo_sample_step(const dppo_dims* d, int precision, const void* p
         DPPO_CHECK(dppo_prec_ok(precision), "dppo_sample: bad precision %d", precision);
         SampleArgs q = {};
         q.E = n_envs;
+        SchedParams sp;
+        rc = dppo_sched_lookup(D, sched, "dppo_sample", &sp);   // read once here, handed to sample_impl below
+        if (rc) return rc;
         int act = DPPO_ACT_RELU, head = DPPO_HEAD_RESIDUAL;
         rc = sample_net(D, precision, packed_base, packed_ft, q, &act, &head);
         if (rc) return rc;
@@ -661,8 +669,12 @@ extern "C" int dppo_sample_step(const dppo_dims* d, int precision, const void* p
         rc = sample_supported(q, precision, act, head, &split);
         if (rc) return rc;
         DPPO_HIP(hipMemcpyAsync(cond, cond_host, sizeof(float) * (size_t)n_envs * D.SD, hipMemcpyHostToDevice, s));
-        rc = dppo_sample(d, precision, packed_base, packed_ft, sched, cond, n_envs, nullptr, nullptr, seed, call_id,
-                         env_offset, deterministic, min_sampling_std, randn_clip, final_clip, actions, chains, stream);
+        rc = sample_impl(d, precision,
+                         {.packed_base = (const uint8_t*)packed_base, .packed_ft = (const uint8_t*)packed_ft, .sched = sched,
+                          .cond = cond, .actions = actions, .chains = chains, .seed = seed, .call_id = (uint32_t)call_id,
+                          .E = n_envs, .env_offset = env_offset, .deterministic = deterministic,
+                          .min_std = min_sampling_std, .randn_clip = randn_clip, .final_clip = final_clip},
+                         stream, &sp);
         if (rc) return rc;
         DPPO_HIP(hipMemcpyAsync(actions_host, actions, sizeof(float) * (size_t)n_envs * D.XD, hipMemcpyDeviceToHost, s));
     }

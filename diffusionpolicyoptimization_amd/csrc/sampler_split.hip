@@ -723,7 +723,7 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
                 const int v = ve, r = re, q = qe, row = row0 + r;
                 ep += be;
                 const float x = xe;
-                float y = ddpm_post(c0, c1, c2, c3, sd, x, ep, ze);   // (:198-242, :301-320)
+                float y = ddpm_post(c0, c1, c2, c3, sd, x, ep, ze, a.x0_clip);   // (:198-242, :301-320)
                 if (a.final_clip > 0.f && i == K - 1) y = fminf(fmaxf(y, -a.final_clip), a.final_clip);
                 if (failed) y = __builtin_nanf("");
                 xe = y;

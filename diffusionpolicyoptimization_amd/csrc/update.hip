@@ -452,6 +452,11 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     // the images' attributes, read once: everything below follows these two values
     const NetSpec anet = actor_net(D, precision, dppo_image_attrs(m.packed_ft));
     const NetSpec cnet = critic_net(D, precision, dppo_image_attrs(m.packed_critic));
+    SchedParams sp;
+    rc = dppo_sched_lookup(D, m.sched, "dppo_ppo_minibatch", &sp);
+    if (rc) return rc;
+    DPPO_CHECK(!(sp.predict_x0 && (hp->flags & DPPO_PPO_LEARN_ETA)),
+               "dppo_ppo_minibatch: DPPO_PPO_LEARN_ETA on an x0-prediction schedule table (DDIM requires predicting epsilon)");
     const FlatOffsets FA = make_flat_offsets(anet);
     float* ga = m.grads;
     float* gc = m.grads + FA.count;
@@ -487,6 +492,7 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     aa.XD = D.XD; aa.SD = D.SD; aa.TD = D.TD; aa.IN = D.IN; aa.H = D.H; aa.KF = D.KF; aa.Da = D.Da; aa.TS = D.TS;
     aa.mode = ROWS_TRAIN; aa.nrows = rows; aa.fk = fk; aa.start = m.start; aa.row_index = m.row_index;
     aa.lp_old = m.lp_old_mean; aa.adv = m.advantages; aa.hp = lh; aa.ws = ws; aa.metrics = m.metrics;
+    aa.x0_clip = sp.clip;
 
     CriticArgs ca = {};
     ca.packed = (const uint8_t*)m.packed_critic;
@@ -673,6 +679,9 @@ extern "C" int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const 
     const PpoWorkspace ws = make_ppo_workspace(D, precision, rows, (uint8_t*)workspace);
     DPPO_CHECK(ws.total < ((size_t)1 << 31), "dppo_pretrain_minibatch: workspace for %d rows exceeds 2 GiB", rows);
     const NetSpec anet = actor_net(D, precision, dppo_image_attrs(packed_actor));
+    SchedParams sp;
+    rc = dppo_sched_lookup(D, sched, "dppo_pretrain_minibatch", &sp);
+    if (rc) return rc;
     const FlatOffsets FA = make_flat_offsets(anet);
     float* ga = grads;
     ActorArgs aa = {};
@@ -682,6 +691,8 @@ extern "C" int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const 
     aa.XD = D.XD; aa.SD = D.SD; aa.TD = D.TD; aa.IN = D.IN; aa.H = D.H; aa.KF = D.K; aa.Da = D.Da; aa.TS = 1;
     aa.mode = ROWS_PRETRAIN; aa.nrows = rows; aa.ws = ws; aa.metrics = metrics;
     aa.tsteps = t; aa.noise = noise; aa.qsched = qsched;
+    // pretraining never clips (p_losses has no x_recon); the table's record picks the target
+    aa.x0_clip = sp.clip; aa.x0_target = sp.predict_x0;
     // loss = mean over global_rows * XD elements of (eps - noise)^2 (diffusion.py:192)
     const float gscale = dppo_grad_scale_rows(precision, global_rows);
     aa.pre_scale = 2.f * loss_scale / ((float)global_rows * (float)D.XD) * gscale;

@@ -22,10 +22,8 @@ class DiffusionModel:
                  denoised_clip_value=1.0, randn_clip_value=10.0, final_action_clip_value=None, eps_clip_value=None,
                  denoising_steps=100, predict_epsilon=True, use_ddim=False, ddim_discretize="uniform", ddim_steps=None,
                  precision="fp32", seed=42, ddim_eta=1.0, **kwargs):
-        if not predict_epsilon:
-            raise NotImplementedError("predict_epsilon=False is not used by the DPPO cfgs")
-        if denoised_clip_value != 1.0:
-            raise NotImplementedError("the sampler epilogue implements denoised_clip_value = 1.0 (diffusion.py:28)")
+        if use_ddim:
+            assert predict_epsilon, "DDIM requires predicting epsilon for now."
         if eps_clip_value is not None:
             # DDIM: the reference computes the clip and discards it (diffusion_vpg.py:213-214)
             log.info("eps_clip_value has no effect (the reference discards the clipped eps)")
@@ -36,7 +34,7 @@ class DiffusionModel:
         self.obs_dim = obs_dim
         self.action_dim = action_dim
         self.denoising_steps = int(denoising_steps)
-        self.predict_epsilon = predict_epsilon
+        self.predict_epsilon = bool(predict_epsilon)
         self.use_ddim = use_ddim
         self.ddim_steps = ddim_steps
         self.ddim_eta = float(ddim_eta)
@@ -63,8 +61,12 @@ class DiffusionModel:
                                            device=self.device)
         else:
             self.sampling_steps, self.time_stride = self.denoising_steps, 1
-            self.sched = torch.tensor(ops.sched_table(buf), device=self.device)
+            self.sched = torch.tensor(ops.sched_table(buf, self.predict_epsilon), device=self.device)
             self.sched_eval = self.sched
+        # denoised_clip_value (None = no clip, diffusion_vpg.py:183-209) and the parameterisation are attributes of
+        # the tables: every launch that takes one reads them there
+        for tab in {id(t): t for t in (self.sched, self.sched_eval)}.values():
+            ops.sched_set_params(tab, self.denoised_clip_value, self.predict_epsilon)
 
     def sched_for(self, deterministic):
         """The schedule table of a sampling call (DDIM eval sampling runs eta = 0)."""
@@ -104,7 +106,8 @@ class DiffusionModel:
         # q_sample buffers and the DDPM table over all K training steps (DDIM only changes sampling)
         ddpm = ddpm_buffers(self.denoising_steps)
         self.q_sched = torch.tensor(ops.q_sched_table(ddpm), device=dev)
-        self.pre_sched = torch.tensor(ops.sched_table(ddpm), device=dev)
+        self.pre_sched = ops.sched_set_params(torch.tensor(ops.sched_table(ddpm, self.predict_epsilon), device=dev),
+                                              self.denoised_clip_value, self.predict_epsilon)
         self.pre_metrics = torch.zeros(16, dtype=torch.float64, device=dev)
         self._pre_gen = torch.Generator(device=dev).manual_seed(self.seed)
         self._pre_ws, self._pre_ws_rows = None, 0
@@ -121,8 +124,9 @@ class DiffusionModel:
         return q[:, 0].reshape(shape) * x_start + q[:, 1].reshape(shape) * noise
 
     def p_losses(self, x_start, cond, t, noise=None, global_rows=None, loss_scale=1.0):
-        """diffusion.py:186-194 (predict_epsilon): loss = mean((network(q_sample(x_0, t, noise), t, cond)
-        - noise)^2) on the device; d loss / d params lands in self.pre_grads (dppo_pretrain_minibatch).
+        """diffusion.py:186-194: loss = mean((network(q_sample(x_0, t, noise), t, cond) - target)^2) on the device,
+        target = noise (predict_epsilon) or x_start (the record of self.pre_sched picks it); d loss / d params
+        lands in self.pre_grads (dppo_pretrain_minibatch).
         x_start [B, Ta, Da] or [B, Ta*Da]; cond [B, To, Do] or a dict with "state"; t [B] int."""
         self._pretrain_init()
         d = self.pre_dims

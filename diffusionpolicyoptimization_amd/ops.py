@@ -1253,10 +1253,36 @@ def adamw(params, grads, m, v, step, lr, weight_decay=0.004, beta1=0.9, beta2=0.
               _lib.DPPO_ADAMW_KERAS if mode == "keras" else _lib.DPPO_ADAMW_TORCH, stream_handle(params.device))
 
 
-def sched_table(schedule):
+def _forget_sched(address):
+    try:
+        _lib.call("dppo_forget_sched", ctypes.c_void_p(address))
+    except Exception:   # interpreter shutdown: the library may be gone, and so is its table
+        pass
+
+
+def sched_set_params(sched, denoised_clip_value=1.0, predict_epsilon=True):
+    """Record a schedule table's attributes (dppo_sched_set_params, include/dppo.h): the clip bound of x_recon
+    (None = no clip) and the parameterisation. The library keys the record by the table's ADDRESS, so it is erased
+    when the tensor is freed (dppo_forget_sched), as an image's attributes are. Returns sched."""
+    if (not isinstance(sched, torch.Tensor) or sched.dtype != torch.float32 or sched.dim() != 2
+            or sched.shape[1] != _lib.SCHED_COLS or not sched.is_contiguous()):
+        raise ValueError(f"sched: expected a contiguous float32 [rows, {_lib.SCHED_COLS}] tensor")   # host or device
+    clip = 0.0 if denoised_clip_value is None else float(denoised_clip_value)
+    _lib.call("dppo_sched_set_params", ptr(sched), clip, int(not predict_epsilon))
+    fin = getattr(sched, "_dppo_forget", None)
+    if fin is None or not fin.alive:
+        sched._dppo_forget = weakref.finalize(sched, _forget_sched, sched.data_ptr())
+        sched._dppo_forget.atexit = False
+    return sched
+
+
+def sched_table(schedule, predict_epsilon=True):
     """[rows][8] fp32 table (include/dppo.h) from the fp32 DDPM buffers, or from the DDIM
-    sub-sequence coefficients (model/diffusion/sampling.py: ddpm_buffers / ddim_buffers)."""
+    sub-sequence coefficients (model/diffusion/sampling.py: ddpm_buffers / ddim_buffers).
+    predict_epsilon=False (diffusion.py:117-134, x_recon = the network's output): the x0 rows c0 = 0, c1 = -1, the
+    rest as for DDPM; the table's record must say so too (sched_set_params)."""
     if "ddim_c0" in schedule:
+        assert predict_epsilon, "DDIM requires predicting epsilon for now."
         tab = np.zeros((len(schedule["ddim_c0"]), _lib.SCHED_COLS), np.float32)
         for j, k in enumerate(("ddim_c0", "ddim_c1", "ddim_c2", "ddim_c3", "ddim_logvar")):
             tab[:, j] = schedule[k]
@@ -1266,8 +1292,11 @@ def sched_table(schedule):
         return tab
     K = len(schedule["betas"])
     tab = np.zeros((K, _lib.SCHED_COLS), np.float32)
-    tab[:, 0] = schedule["sqrt_recip_alphas_cumprod"]
-    tab[:, 1] = schedule["sqrt_recipm1_alphas_cumprod"]
+    if predict_epsilon:
+        tab[:, 0] = schedule["sqrt_recip_alphas_cumprod"]
+        tab[:, 1] = schedule["sqrt_recipm1_alphas_cumprod"]
+    else:
+        tab[:, 1] = -1.0
     tab[:, 2] = schedule["ddpm_mu_coef1"]
     tab[:, 3] = schedule["ddpm_mu_coef2"]
     tab[:, 4] = schedule["ddpm_logvar_clipped"]

@@ -137,11 +137,43 @@ typedef struct dppo_dims {
  *     c0 = 1 / sqrt(abar), c1 = sqrt(1/abar - 1); logvar = log(sigma^2), sigma = max(eta sqrt((1 - abar_prev)
  *     / (1 - abar) (1 - abar / abar_prev)), 1e-10); eval_floor 0, eval_zero 1; column 7 = s =
  *     sqrt((1 - abar_prev) / (1 - abar) (1 - abar / abar_prev)) (sigma / eta: read only by the
- *     learnable-eta gradient, DPPO_PPO_LEARN_ETA; ABI 9; 0 for DDPM rows). */
+ *     learnable-eta gradient, DPPO_PPO_LEARN_ETA; ABI 9; 0 for DDPM rows).
+ *   x0-prediction (predict_epsilon=False, diffusion.py:117-134: x_recon is the network's output): the same
+ *     affine form with c0 = 0, c1 = -1 in every row, c2 .. eval_zero as for DDPM: x0 = clip(out), and the update's
+ *     d loss / d out = -c1 c2 dmu = c2 dmu under the same mask.
+ *
+ * The table's ATTRIBUTES (an addition within ABI 15) are {denoised_clip, predict_x0}: the bound c of
+ * x0 = clip(c0 x - c1 out, -c, c) (diffusion_vpg.py:183-209 clips only `if denoised_clip_value is not None`) and
+ * whether the network's output is x0. They live in a host table keyed by the table's device ADDRESS, like a
+ * packed image's; an address nobody recorded reads as {1.0, epsilon}, which is every launch before this addition,
+ * bit for bit. dppo_sched_set_params records them (host-only but for one blocking 32-byte read of row 0 when
+ * predict_x0 is set, no launch: the caller has the table complete and visible to a blocking copy by then, i.e.
+ * filled on the null stream or its stream synchronised, and passes the address of memory HIP allocated, or
+ * plain host memory for a host-only description); denoised_clip 0 or an infinity of either sign means None (no clip: the kernels
+ * take +inf as the bound). dppo_forget_sched erases the record (NULL is accepted) and is called before the
+ * table's memory is released, as dppo_forget_image is for an image; the Python package does it when the tensor
+ * is freed (ops.sched_set_params). dppo_eta_step rewrites a table in place and leaves its record alone.
+ *   reads the record (once per call): dppo_sample, dppo_sample_step, dppo_rollout_enqueue{,_tagged} (the bound,
+ *     in every sampler kernel), dppo_logprob and dppo_ppo_minibatch{,_part} (the bound: the same value clips
+ *     x_recon, masks the backward and re-derives x0 in the learnable-eta term), dppo_pretrain_minibatch
+ *     (predict_x0 picks the target: loss = mean((out - x_start)^2) instead of (out - noise)^2; pretraining never
+ *     clips, so the bound changes nothing there).
+ *   accepted: any bound > 0 or None, with epsilon-prediction on DDPM and DDIM tables; predict_x0 on a DDPM table
+ *     (the caller gives it the x0 rows above).
+ *   refused with DPPO_EINVAL and a message of its own, before anything is enqueued, outputs (or the record)
+ *   untouched:
+ *     dppo_sched_set_params: a NaN bound; a negative finite bound; predict_x0 outside {0, 1}; predict_x0 on a table
+ *       whose row 0 has eval_floor 0, i.e. DDIM rows ("DDIM requires predicting epsilon", the reference's assert);
+ *     every reading entry: predict_x0 with time_stride > 1;
+ *     dppo_ppo_minibatch{,_part}: predict_x0 together with DPPO_PPO_LEARN_ETA.
+ * tests/test_diffusion_param_gpu.py pins this. */
 #define DPPO_SCHED_COLS 8
 
 DPPO_API int         dppo_abi_version(void);
 DPPO_API const char* dppo_last_error(void);
+/* the schedule table's attributes (above) */
+DPPO_API int dppo_sched_set_params(const float* sched, float denoised_clip, int predict_x0);
+DPPO_API int dppo_forget_sched(const float* sched);
 
 /* ---- parameter packing (replaces Keras variable storage; model/common/mlp.py:95-206) ---- */
 DPPO_API size_t dppo_actor_param_count(const dppo_dims* d);
@@ -569,7 +601,8 @@ DPPO_API int dppo_ppo_minibatch(const dppo_dims* d, int precision, const dppo_pp
                        void* workspace, float* grads, double* metrics, void* stream);
 
 /* ---- §8(f) row 3: the pretraining loss DiffusionModel.c_loss -> p_losses / q_sample
- * (model/diffusion/diffusion.py:179-202; predict_epsilon = True), loss and actor gradients.
+ * (model/diffusion/diffusion.py:179-202), loss and actor gradients; the target is the noise, or x_start when
+ * the schedule table's record says predict_x0 (dppo_sched_set_params; then read (eps - noise) below as (out - x_start)).
  * Replaces the TF tape over `self.model.c_loss(**batch)` in agent/pretrain/train_diffusion_agent.py.
  * Row r is sample r: x_start [rows][horizon*action_dim], cond [rows][cond_steps*obs_dim],
  * t [rows] int32 in [0, denoising_steps), noise [rows][horizon*action_dim] (the host draws t and

@@ -27,6 +27,9 @@ SCHED_COLS = 8
 PRECISION = {"fp32": DPPO_F32, "f32": DPPO_F32, "bf16": DPPO_BF16, "fp16": DPPO_F16, "f16": DPPO_F16}
 # the actor's activation_type (DPPO_ACT_*): an attribute of a packed actor image (dppo_pack_actor_act)
 ACTIVATION = {"ReLU": 0, "Mish": 1}
+# every activation the actor kernels run: ACTIVATION (the pair ABI 15 began with, which tests/test_actor_mish_cpu.py
+# pins as it stands) and ELU, GELU (the erf form), Softplus. Value 2 is reserved for Tanh and refused by the library
+ACTOR_ACTIVATION = {**ACTIVATION, "ELU": 3, "GELU": 4, "Softplus": 5}
 # the actor's head (DPPO_HEAD_*), the image's second attribute (dppo_pack_actor_head): "residual" is
 # ResidualMLP (residual_style=True), "plain" the reference's MLP([in, h, h, out]) (residual_style=False)
 HEAD = {"residual": 0, "plain": 1}

@@ -70,7 +70,7 @@ extern "C" int dppo_pack_actor_head(const dppo_dims* d, int precision, int activ
     if (rc) return rc;
     DPPO_CHECK(params && packed, "dppo_pack_actor: null pointer");
     DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
-    DPPO_CHECK(dppo_act_ok(activation), "dppo_pack_actor_act: bad activation %d (DPPO_ACT_RELU or DPPO_ACT_MISH)", activation);
+    DPPO_CHECK(dppo_act_ok(activation), "dppo_pack_actor_act: bad activation %d (DPPO_ACT_RELU, _MISH, _ELU, _GELU or _SOFTPLUS)", activation);
     DPPO_CHECK(dppo_head_ok(head), "dppo_pack_actor_head: bad head %d (DPPO_HEAD_RESIDUAL or DPPO_HEAD_PLAIN)", head);
     const ImageAttrs attrs{activation, head, DPPO_LN_OFF};
     rc = dppo_pack_mlp(actor_net(D, precision, attrs), params, packed, (hipStream_t)stream);

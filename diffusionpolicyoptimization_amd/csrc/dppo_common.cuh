@@ -362,6 +362,116 @@ __device__ inline float mish_gradf(float x) {
     return x > 15.f ? 1.f : n * r + 4.f * x * e * (e + 1.f) * r * r;
 }
 
+// The actor's other smooth activations (Keras: elu with alpha = 1, gelu with approximate=False,
+// tf.math.softplus), fp32 and finite for every finite input: each exponential takes a non-positive (or
+// clamped) argument. Like mishf they are one v_exp and at most one v_rcp / v_log beside a few fma, and the
+// derivatives are functions of the pre-activation x (none can be read off the stored output after its
+// 2-byte rounding), behind the same opaque copy as mish_gradf. Errors below are against float64 over
+// [-20, 20] and at +-1e4, +-3e38.
+//
+// elu(x) = x (x > 0), expm1(x) (x <= 0). e^x - 1 cancels near 0, so (-0.5, 0] takes expm1's Taylor series
+// to x^8 (truncation 1.4e-8 relative at -0.5) and x <= -0.5 takes v_exp's e^x - 1 (result <= -0.39: the
+// subtraction rounds once). Relative error <= 2e-7.
+__device__ inline float eluf(float x) {
+    const float t = fminf(x, 0.f);
+    float p = 1.f / 40320.f;
+    p = __builtin_fmaf(p, t, 1.f / 5040.f);
+    p = __builtin_fmaf(p, t, 1.f / 720.f);
+    p = __builtin_fmaf(p, t, 1.f / 120.f);
+    p = __builtin_fmaf(p, t, 1.f / 24.f);
+    p = __builtin_fmaf(p, t, 1.f / 6.f);
+    p = __builtin_fmaf(p, t, 0.5f);
+    p = __builtin_fmaf(p, t, 1.f);
+    const float m = t > -0.5f ? p * t : __expf(t) - 1.f;
+    return x > 0.f ? x : m;
+}
+__device__ inline float elu_gradf(float x) {
+    asm volatile("" : "+v"(x));   // opaque copy (mish_gradf)
+    return x > 0.f ? 1.f : __expf(fminf(x, 0.f));
+}
+
+// Phi(-|x|) = erfc(|x| / sqrt 2) / 2 by Abramowitz & Stegun 7.1.26: (a1 t + ... + a5 t^5) e^{-z^2} / 2 with
+// z = |x| / sqrt 2, t = 1 / (1 + p z); |error| <= 1.5e-7 on erf in exact arithmetic, and the form decays with
+// e^{-z^2}, so the tail keeps no floor. *g receives e^{-x^2 / 2} (sqrt(2 pi) phi(x)), the derivative's other
+// term. |x| is clamped at 15, where e^{-112.5} is 0 in fp32: Phi(-|x|) is exactly 0 from there, so x Phi(x)
+// is -0 or x, and x^2 never overflows.
+__device__ inline float gelu_tailf(float x, float* g) {
+    const float z = fminf(fabsf(x), 15.f) * 0.70710678f;
+    const float e = __expf(-z * z);
+    const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f, z, 1.f));
+    float p = 1.061405429f;
+    p = __builtin_fmaf(p, t, -1.453152027f);
+    p = __builtin_fmaf(p, t, 1.421413741f);
+    p = __builtin_fmaf(p, t, -0.284496736f);
+    p = __builtin_fmaf(p, t, 0.254829592f);
+    *g = e;
+    return 0.5f * p * t * e;
+}
+// gelu(x) = x Phi(x), the erf form (not the tanh approximation): Phi(x) = q (x <= 0), 1 - q (x > 0) with
+// q = Phi(-|x|) above, so the negative tail is a product, not 1 + erf's cancellation.
+// |error| <= 5e-7 absolute, <= 2.5e-7 (1 + |gelu|).
+__device__ inline float geluf(float x) {
+    float g;
+    const float q = gelu_tailf(x, &g);
+    return x * (x > 0.f ? 1.f - q : q);
+}
+// gelu'(x) = Phi(x) + x phi(x), phi(x) = e^{-x^2 / 2} / sqrt(2 pi); |error| <= 3e-7
+__device__ inline float gelu_gradf(float x) {
+    asm volatile("" : "+v"(x));   // opaque copy (mish_gradf)
+    float g;
+    const float q = gelu_tailf(x, &g);
+    return (x > 0.f ? 1.f - q : q) + x * (0.39894228f * g);
+}
+
+// softplus(x) = log1p(e^x) = max(x, 0) + log1p(u), u = e^{-|x|} in (0, 1]. log1p(u) = log(s) + (u - (s - 1)) / s
+// with s = rnd(1 + u): the second term returns what rounding 1 + u dropped (for u < 2^-24 it is u itself).
+// Relative error <= 4e-7.
+__device__ inline float softplusf(float x) {
+    const float u = __expf(-fabsf(x));
+    const float s = 1.f + u;
+    const float l = __logf(s) + (u - (s - 1.f)) * __builtin_amdgcn_rcpf(s);
+    return fmaxf(x, 0.f) + l;
+}
+// softplus'(x) = sigmoid(x) = 1 / (1 + u) (x >= 0), u / (1 + u) (x < 0); relative error <= 3e-7
+__device__ inline float softplus_gradf(float x) {
+    asm volatile("" : "+v"(x));   // opaque copy (mish_gradf)
+    const float u = __expf(-fabsf(x));
+    const float r = __builtin_amdgcn_rcpf(1.f + u);
+    return x >= 0.f ? r : u * r;
+}
+
+// The actor's smooth activations by the image's attribute (DPPO_ACT_*; ReLU is each kernel's own form: its
+// derivative is a sign bit, not a function of the pre-activation). Value 2 is reserved and has no case.
+template <int ACT>
+__device__ inline float smooth_actf(float x) {
+    static_assert(ACT == DPPO_ACT_MISH || ACT == DPPO_ACT_ELU || ACT == DPPO_ACT_GELU || ACT == DPPO_ACT_SOFTPLUS,
+                  "not a smooth activation");
+    if constexpr (ACT == DPPO_ACT_MISH) return mishf(x);
+    else if constexpr (ACT == DPPO_ACT_ELU) return eluf(x);
+    else if constexpr (ACT == DPPO_ACT_GELU) return geluf(x);
+    else return softplusf(x);
+}
+// The samplers hold some seventy instantiations per activation. ELU, GELU and Softplus share ONE set there,
+// DPPO_ACT_BY_ARG (no value of the enum), which picks among the three by the launch's argument: the same value
+// in every lane, so a scalar branch around the same fp32 functions. ReLU and Mish keep their own sets.
+constexpr int DPPO_ACT_BY_ARG = -1;
+__device__ inline float smooth_act_by_arg(int act, float x) {
+    switch (act) {
+        case DPPO_ACT_ELU: return eluf(x);
+        case DPPO_ACT_GELU: return geluf(x);
+        default: return softplusf(x);
+    }
+}
+template <int ACT>
+__device__ inline float smooth_act_gradf(float x) {
+    static_assert(ACT == DPPO_ACT_MISH || ACT == DPPO_ACT_ELU || ACT == DPPO_ACT_GELU || ACT == DPPO_ACT_SOFTPLUS,
+                  "not a smooth activation");
+    if constexpr (ACT == DPPO_ACT_MISH) return mish_gradf(x);
+    else if constexpr (ACT == DPPO_ACT_ELU) return elu_gradf(x);
+    else if constexpr (ACT == DPPO_ACT_GELU) return gelu_gradf(x);
+    else return softplus_gradf(x);
+}
+
 // ------------------------------------------------------------------------------------------------
 // t_emb(t) = Dense(2TD->TD)(mish(Dense(TD->2TD)(SinusoidalPosEmb(t)))) (mlp_diffusion.py:40-45,
 // modules.py:4-15), element by element. p: the actor's flat parameters (time_w1 [TD][2TD], time_b1,

@@ -39,7 +39,10 @@ int dppo_pack_rt_fold(const NetSpec& actor, const float* actor_params, void* pac
 // the fused actor step leaves the image's split-sampler tables stale like a deferred pack; temb: the TEMB table
 // is stale too, not only the split-sampler tables
 int dppo_mark_tables_stale(const NetSpec& actor, const float* actor_params, const void* packed_actor, bool temb);
-inline bool dppo_act_ok(int a) { return a == DPPO_ACT_RELU || a == DPPO_ACT_MISH; }
+// value 2 (reserved for Tanh, include/dppo.h) is refused like any value outside the enum
+inline bool dppo_act_ok(int a) {
+    return a == DPPO_ACT_RELU || a == DPPO_ACT_MISH || a == DPPO_ACT_ELU || a == DPPO_ACT_GELU || a == DPPO_ACT_SOFTPLUS;
+}
 inline bool dppo_head_ok(int h) { return h == DPPO_HEAD_RESIDUAL || h == DPPO_HEAD_PLAIN; }
 inline bool dppo_ln_ok(int l) { return l == DPPO_LN_OFF || l == DPPO_LN_ON; }
 // device address of mapped pinned host memory (dppo_host_alloc), cached; null if not mapped (host_staging.hip)

@@ -155,7 +155,8 @@ struct CriticArgs {
 
 // the actor row tile of a launch over `rows` rows (the 64-padded image rows in the TRAIN modes):
 // mt 16-row MFMA tiles per row tile (2 = 32 rows, 4 = 64 rows) on `waves` waves
-// act (DPPO_ACT_*): a Mish actor's tile carries h1, h2 to its backward and runs 32 rows on 8 waves always
+// act (DPPO_ACT_*): a smooth actor's tile (Mish, ELU, GELU, Softplus: every activation but ReLU) carries h1, h2 to
+// its backward and runs 32 rows on 8 waves always
 struct ActorTilePlan { int mt, waves; };
 ActorTilePlan actor_tile_plan(int precision, int H, int XD, int64_t rows, int act);
 // dry: only check that the launch has an instantiation (DPPO_EUNSUPPORTED with the dispatch's message

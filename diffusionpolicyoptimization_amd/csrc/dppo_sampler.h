@@ -32,6 +32,8 @@ struct SampleArgs {
     // polled until every tag equals cond_tag (then cond is unused); null = cond / go as above
     const uint64_t* cond_tagged;
     uint32_t cond_tag;
+    int act;              // the images' activation (DPPO_ACT_*), filled by sample_impl: read by the DPPO_ACT_BY_ARG
+                          // instantiations only. It sits in the hole before `seed`: no other field moves
     uint64_t seed;
     uint32_t call_id;
     int E, env_offset, deterministic;
@@ -208,5 +210,6 @@ struct SplitPlan { int P; bool dual; int blocks; int cus; };
 SplitPlan split_plan(int precision, int H, int XD, int SD, int E, int K, int KF);
 // returns DPPO_OK after launching, DPPO_EUNSUPPORTED (without touching the error message) when
 // split_plan does not take the shape, or another error code
-// act: the images' activation (DPPO_ACT_*), one instantiation each
+// act: the images' activation (DPPO_ACT_*): ReLU and Mish have an instantiation each, ELU / GELU / Softplus share
+// DPPO_ACT_BY_ARG's (dppo_common.cuh) and follow a.act
 int launch_sample_split(const SampleArgs& a, int precision, int act, hipStream_t s);

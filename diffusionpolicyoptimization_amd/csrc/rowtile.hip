@@ -99,15 +99,18 @@ __device__ inline float rt_xrecon_eta(float c0, float c1, float x, float eps) {
     return __builtin_fmaf(c0, x, -t);
 }
 
-// ACT (DPPO_ACT_RELU / DPPO_ACT_MISH): the image's activation at the block's two sites, u1 = act(h1) and
+// ACT (DPPO_ACT_*): the image's activation at the block's two sites, u1 = act(h1) and
 // a = act(h2) (mlp.py:192-193, 202-203). relu' is read off the activation's sign (one bit per element);
-// mish is not monotone, so a Mish TRAIN tile keeps h1 and h2 themselves in registers until the
+// mish is not monotone, and no smooth activation's derivative (Mish, ELU, GELU, Softplus) survives the
+// stored output's rounding, so a smooth TRAIN tile keeps h1 and h2 themselves in registers until the
 // backward, as the critic tile does (8 MT NT VGPRs: the 8-wave tiles have them, the 16-wave ones do not)
+template <int ACT> __device__ __forceinline__ float act_f(float x) { return smooth_actf<ACT>(x); }
+template <int ACT> __device__ __forceinline__ float act_grad_f(float x) { return smooth_act_gradf<ACT>(x); }
 template <class P, int MT, int NT, int NO, int KSI, bool TRAIN, int WAVES, int ACT>
 __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
     using AT = typename P::AT;
-    constexpr bool MISH = ACT == DPPO_ACT_MISH;
-    constexpr bool CARRY = MISH && TRAIN;
+    constexpr bool SMOOTH = ACT != DPPO_ACT_RELU;
+    constexpr bool CARRY = SMOOTH && TRAIN;
     constexpr int THREADS = 64 * WAVES;
     constexpr int ROWS = 16 * MT;
     static_assert(ROWS <= 64, "the epilogue maps one row per lane of wave 0");
@@ -260,7 +263,7 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
     using MaskT = typename std::conditional<(MT * NT * 4 > 32), uint64_t, uint32_t>::type;
     static_assert(MT * NT * 4 <= 64, "relu masks are at most 64-bit");
     MaskT mask1 = 0, mask2 = 0;
-    f32x4 hk1[CARRY ? MT : 1][CARRY ? NT : 1], hk2[CARRY ? MT : 1][CARRY ? NT : 1];   // Mish TRAIN: h1, h2
+    f32x4 hk1[CARRY ? MT : 1][CARRY ? NT : 1], hk2[CARRY ? MT : 1][CARRY ? NT : 1];   // smooth TRAIN: h1, h2
     // The weight stream is one QD-deep queue per wave through every layer of the kernel:
     //   in -> l1 -> [train] out^T -> M^T -> l1^T. The l2 layer never runs as a GEMM: the residual block
     //   is linear from the l2 product to the out-Dense (mlp.py:186-206), so
@@ -281,16 +284,16 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if constexpr (MISH) {
+                if constexpr (SMOOTH) {
                     if constexpr (CARRY) hk1[m][n][r] = acc[m][n][r];
-                    acc[m][n][r] = mishf(acc[m][n][r]);
+                    acc[m][n][r] = act_f<ACT>(acc[m][n][r]);
                 } else {
                     if (acc[m][n][r] > 0.f) mask1 |= MaskT(1) << ((m * NT + n) * 4 + r);
                     acc[m][n][r] = fmaxf(acc[m][n][r], 0.f);
                 }
             }
     // materialise the mask now (otherwise hipcc keeps the 8*MT*NT floats alive until the backward)
-    if constexpr (!MISH) asm volatile("" : "+v"(mask1));
+    if constexpr (!SMOOTH) asm volatile("" : "+v"(mask1));
     store_acc_lds<P, MT, NT>(tA, ldh, ntile0, lane, acc);
     if constexpr (train) store_accT<P, MT, NT>(wsr, ws_off(a.ws, a.ws.u1T), ldm32, ntile0, grow32, lane, acc);
     lds_sync();
@@ -312,15 +315,15 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if constexpr (MISH) {
+                if constexpr (SMOOTH) {
                     if constexpr (CARRY) hk2[m][n][r] = acc[m][n][r];
-                    acc[m][n][r] = mishf(acc[m][n][r]);
+                    acc[m][n][r] = act_f<ACT>(acc[m][n][r]);
                 } else {
                     if (acc[m][n][r] > 0.f) mask2 |= MaskT(1) << ((m * NT + n) * 4 + r);
                     acc[m][n][r] = fmaxf(acc[m][n][r], 0.f);
                 }
             }
-    if constexpr (!MISH) asm volatile("" : "+v"(mask2));
+    if constexpr (!SMOOTH) asm volatile("" : "+v"(mask2));
     store_acc_lds<P, MT, NT>(tB, ldh, ntile0, lane, acc);
     if constexpr (train) store_accT<P, MT, NT>(wsr, ws_off(a.ws, a.ws.u2T), ldm32, ntile0, grow32, lane, acc);
     // the folded out-Dense's fragments: fetched after the l1 result's stores (held
@@ -550,7 +553,7 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if constexpr (CARRY) acc[m][n][r] *= mish_gradf(hk2[m][n][r]);
+                if constexpr (CARRY) acc[m][n][r] *= act_grad_f<ACT>(hk2[m][n][r]);
                 else if (!((mask2 >> ((m * NT + n) * 4 + r)) & 1u)) acc[m][n][r] = 0.f;
             }
     store_acc_lds<P, MT, NT>(tA, ldh, ntile0, lane, acc);
@@ -568,7 +571,7 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
             for (int r = 0; r < 4; ++r) {
                 const float dh3 = P::tof(tB[(m * 16 + crow(lane, r)) * ldh + (ntile0 + n) * 16 + ccol(lane)]);
                 if constexpr (CARRY) {
-                    acc[m][n][r] = dh3 + acc[m][n][r] * mish_gradf(hk1[m][n][r]);
+                    acc[m][n][r] = dh3 + acc[m][n][r] * act_grad_f<ACT>(hk1[m][n][r]);
                 } else {
                     const bool on = (mask1 >> ((m * NT + n) * 4 + r)) & 1u;
                     acc[m][n][r] = dh3 + (on ? acc[m][n][r] : 0.f);
@@ -637,7 +640,7 @@ static int launch_actor_m(const ActorArgs& a, hipStream_t s, bool dry) {
 }
 
 // bf16: 64-row tiles, 16 waves (half the weight stream per row of 32-row tiles; LDS-limited);
-// fp32: 32-row tiles, 16 waves (a Mish actor: 8 waves, whose 256 registers hold h1 and h2; the same widths)
+// fp32: 32-row tiles, 16 waves (a smooth actor: 8 waves, whose 256 registers hold h1 and h2; the same widths)
 template <class P, int MT, int WAVES, bool O4 = false, int ACT = DPPO_ACT_RELU>
 static int dispatch_actor(const ActorArgs& a, hipStream_t s, bool dry) {
     const int NT = a.H / (16 * WAVES), NO = dppo_cdiv(a.XD, 16), KSI = a.L.ks_in;
@@ -648,7 +651,7 @@ static int dispatch_actor(const ActorArgs& a, hipStream_t s, bool dry) {
     } else if constexpr (P::KG == 32) {           // bf16, 8 waves: the in-layer is 2 k-steps up to 64 inputs, 4 up to 128
         DPPO_ACTOR_CASE(4, 1, 2) DPPO_ACTOR_CASE(4, 2, 2) DPPO_ACTOR_CASE(4, 1, 4) DPPO_ACTOR_CASE(4, 2, 4)
         DPPO_ACTOR_CASE(2, 1, 2) DPPO_ACTOR_CASE(2, 2, 2) DPPO_ACTOR_CASE(2, 1, 4) DPPO_ACTOR_CASE(2, 2, 4)
-    } else if constexpr (WAVES == 8) {   // fp32 Mish, H = 512 on 8 waves
+    } else if constexpr (WAVES == 8) {   // fp32 smooth activations, H = 512 on 8 waves
         DPPO_ACTOR_CASE(4, 1, 4) DPPO_ACTOR_CASE(4, 2, 4)
     } else {                       // fp32: 33..64 inputs -> 4 k-steps
         DPPO_ACTOR_CASE(4, 1, 4) DPPO_ACTOR_CASE(4, 2, 4) DPPO_ACTOR_CASE(2, 1, 4) DPPO_ACTOR_CASE(2, 2, 4)
@@ -671,10 +674,11 @@ static int64_t actor_device_cus() {
 // The tile decision, host arithmetic only: launch_actor_rowtile and the plan query (dppo_ppo_plan)
 // both take it from here. The 2-byte operand policies (bf16, fp16) share the tile configurations
 ActorTilePlan actor_tile_plan(int precision, int H, int XD, int64_t rows, int act) {
-    // Mish: the TRAIN tile carries h1 and h2 (8 MT NT registers) from the forward to the backward. The
-    // 16-wave tiles (128 registers per lane: the 64-row 2-byte tile already spills a little, the fp32 tile
-    // sits at 108) have no room for them, so a Mish actor runs 32 rows on 8 waves whatever the row count
-    if (act == DPPO_ACT_MISH) return ActorTilePlan{2, 8};
+    // Smooth activations (every one but ReLU): the TRAIN tile carries h1 and h2 (8 MT NT registers) from the
+    // forward to the backward. The 16-wave tiles (128 registers per lane: the 64-row 2-byte tile already spills
+    // a little, the fp32 tile sits at 108) have no room for them, so such an actor runs 32 rows on 8 waves
+    // whatever the row count
+    if (act != DPPO_ACT_RELU) return ActorTilePlan{2, 8};
     // fp32: 32-row tiles on 16 waves (four per SIMD behind the 16x16x4 MFMA chains): update 41.5 ->
     // 40.5 ms per iteration against 8 waves (profiles/r06zz_f32_tile_16wave_ab.txt)
     if (!dppo_prec_2b(precision)) return ActorTilePlan{2, 16};
@@ -703,6 +707,9 @@ ActorTilePlan actor_tile_plan(int precision, int H, int XD, int64_t rows, int ac
 template <class P2>
 static int launch_actor_2b(const ActorArgs& a, const ActorTilePlan& p, int act, hipStream_t s, bool dry) {
     if (act == DPPO_ACT_MISH && p.mt == 2 && p.waves == 8) return dispatch_actor<P2, 2, 8, false, DPPO_ACT_MISH>(a, s, dry);
+    if (act == DPPO_ACT_ELU && p.mt == 2 && p.waves == 8) return dispatch_actor<P2, 2, 8, false, DPPO_ACT_ELU>(a, s, dry);
+    if (act == DPPO_ACT_GELU && p.mt == 2 && p.waves == 8) return dispatch_actor<P2, 2, 8, false, DPPO_ACT_GELU>(a, s, dry);
+    if (act == DPPO_ACT_SOFTPLUS && p.mt == 2 && p.waves == 8) return dispatch_actor<P2, 2, 8, false, DPPO_ACT_SOFTPLUS>(a, s, dry);
     if (act == DPPO_ACT_RELU && p.mt == 4 && p.waves == 16) return dispatch_actor<P2, 4, 16>(a, s, dry);
     if (act == DPPO_ACT_RELU && p.mt == 2 && p.waves == 8) return dispatch_actor<P2, 2, 8>(a, s, dry);
     return dppo_set_error(DPPO_EUNSUPPORTED, "actor: no %d-row tile on %d waves", 16 * p.mt, p.waves);
@@ -716,6 +723,9 @@ int launch_actor_rowtile(const ActorArgs& a, const NetSpec& net, hipStream_t s, 
     if (precision == DPPO_BF16) return launch_actor_2b<PolicyBF16>(a, p, act, s, dry);
     if (precision == DPPO_F16) return launch_actor_2b<PolicyF16>(a, p, act, s, dry);
     if (act == DPPO_ACT_MISH && p.mt == 2 && p.waves == 8) return dispatch_actor<PolicyF32, 2, 8, false, DPPO_ACT_MISH>(a, s, dry);
+    if (act == DPPO_ACT_ELU && p.mt == 2 && p.waves == 8) return dispatch_actor<PolicyF32, 2, 8, false, DPPO_ACT_ELU>(a, s, dry);
+    if (act == DPPO_ACT_GELU && p.mt == 2 && p.waves == 8) return dispatch_actor<PolicyF32, 2, 8, false, DPPO_ACT_GELU>(a, s, dry);
+    if (act == DPPO_ACT_SOFTPLUS && p.mt == 2 && p.waves == 8) return dispatch_actor<PolicyF32, 2, 8, false, DPPO_ACT_SOFTPLUS>(a, s, dry);
     if (act != DPPO_ACT_RELU || p.mt != 2 || p.waves != 16)
         return dppo_set_error(DPPO_EUNSUPPORTED, "actor: no fp32 %d-row tile on %d waves", 16 * p.mt, p.waves);
     return dispatch_actor<PolicyF32, 2, 16>(a, s, dry);

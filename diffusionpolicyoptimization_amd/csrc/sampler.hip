@@ -133,12 +133,13 @@ static size_t stream_lds_total(const SampleArgs& a, int NO, int SW) {
     return o;
 }
 
-// the block's activation (ACT: DPPO_ACT_RELU or DPPO_ACT_MISH, the images' attribute) in fp32, rounded by
-// the caller where relu's result is rounded
+// the block's activation (ACT: DPPO_ACT_RELU, DPPO_ACT_MISH or DPPO_ACT_BY_ARG, which follows by_arg = the
+// launch's a.act among ELU / GELU / Softplus) in fp32, rounded by the caller where relu's result is rounded
 template <int ACT>
-__device__ inline float stream_act(float x) {
-    if constexpr (ACT == DPPO_ACT_MISH) return mishf(x);
-    else return fmaxf(x, 0.f);
+__device__ inline float stream_act(float x, int by_arg) {
+    if constexpr (ACT == DPPO_ACT_RELU) return fmaxf(x, 0.f);
+    else if constexpr (ACT == DPPO_ACT_BY_ARG) return smooth_act_by_arg(by_arg, x);
+    else return smooth_actf<ACT>(x);
 }
 
 template <class P, int NT, int NO, int KSI, bool INJ, int QD, int SW, int RK, bool RES, int ACT, int HEAD>
@@ -304,7 +305,7 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 h1[0][n][r] += bv;
-                tA[crow(lane, r) * ldh + col] = P::cvt(stream_act<ACT>(h1[0][n][r]));
+                tA[crow(lane, r) * ldh + col] = P::cvt(stream_act<ACT>(h1[0][n][r], a.act));
             }
         }
         lds_sync();
@@ -321,10 +322,10 @@ __global__ __launch_bounds__(SW * 64) void sample_kernel(SampleArgs a) {
                 if constexpr (HEAD == DPPO_HEAD_PLAIN) {
                     // plain head (no l2 layer, no skip): the out-Dense's input is act(h2) itself, kept in the
                     // skip's registers past the l2 product, whose result this instantiation drops
-                    h1[0][n][r] = stream_act<ACT>(acc[0][n][r] + bv);
+                    h1[0][n][r] = stream_act<ACT>(acc[0][n][r] + bv, a.act);
                     tB[crow(lane, r) * ldh + col] = P::cvt(h1[0][n][r]);
                 } else {
-                    tB[crow(lane, r) * ldh + col] = P::cvt(stream_act<ACT>(acc[0][n][r] + bv));
+                    tB[crow(lane, r) * ldh + col] = P::cvt(stream_act<ACT>(acc[0][n][r] + bv, a.act));
                 }
             }
         }
@@ -494,8 +495,13 @@ static int dispatch_stream_a(const SampleArgs& a, int precision, hipStream_t s, 
 // code they were before the plain head existed
 template <int HEAD>
 static int dispatch_stream_h(const SampleArgs& a, int precision, int act, hipStream_t s, bool dry) {
-    return act == DPPO_ACT_MISH ? dispatch_stream_a<DPPO_ACT_MISH, HEAD>(a, precision, s, dry)
-                                : dispatch_stream_a<DPPO_ACT_RELU, HEAD>(a, precision, s, dry);
+    switch (act) {   // dppo_act_ok's five values: the image registry holds no other
+        case DPPO_ACT_RELU: return dispatch_stream_a<DPPO_ACT_RELU, HEAD>(a, precision, s, dry);
+        case DPPO_ACT_MISH: return dispatch_stream_a<DPPO_ACT_MISH, HEAD>(a, precision, s, dry);
+        case DPPO_ACT_ELU: case DPPO_ACT_GELU: case DPPO_ACT_SOFTPLUS:   // one set, which follows a.act
+            return dispatch_stream_a<DPPO_ACT_BY_ARG, HEAD>(a, precision, s, dry);
+    }
+    return dppo_set_error(DPPO_EINVAL, "dppo_sample: bad activation %d", act);
 }
 static int dispatch_stream(const SampleArgs& a, int precision, int act, int head, hipStream_t s, bool dry) {
     return head == DPPO_HEAD_PLAIN ? dispatch_stream_h<DPPO_HEAD_PLAIN>(a, precision, act, s, dry)
@@ -509,7 +515,7 @@ static int sample_net(const Dims& D, int precision, const void* packed_base, con
     const ImageAttrs ft = dppo_image_attrs(packed_ft), base = dppo_image_attrs(packed_base);
     DPPO_CHECK(base.act == ft.act, "dppo_sample: the base and the fine-tuned actor images carry different activations");
     DPPO_CHECK(base.head == ft.head, "dppo_sample: the base and the fine-tuned actor images carry different heads");
-    *act = ft.act; *head = ft.head;
+    *act = a.act = ft.act; *head = ft.head;
     a.XD = D.XD; a.SD = D.SD; a.TD = D.TD; a.H = D.H; a.K = D.K; a.KF = D.KF; a.IN = D.IN;
     a.L = make_mlp_layout(actor_net(D, precision, ft));
     return DPPO_OK;

@@ -131,12 +131,14 @@ constexpr int S4_L1D = 1;
 // relu as one v_max_i32 on the bits (fmaxf(x, 0) canonicalises its MFMA-produced input first: two
 // VALU ops per element); negative values and -0 map to +0, as fmaxf(x, 0) does up to the sign of 0
 __device__ inline float relu_f(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
-// the block's activation at its two sites (ACT: DPPO_ACT_RELU or DPPO_ACT_MISH, the images' attribute),
-// in fp32; the caller rounds it where relu's result is rounded
+// the block's activation at its two sites (ACT: DPPO_ACT_RELU, DPPO_ACT_MISH or DPPO_ACT_BY_ARG, which follows
+// by_arg = the launch's a.act among ELU / GELU / Softplus), in fp32; the caller rounds it where relu's result is
+// rounded
 template <int ACT>
-__device__ inline float act_f(float x) {
-    if constexpr (ACT == DPPO_ACT_MISH) return mishf(x);
-    else return relu_f(x);
+__device__ inline float act_f(float x, int by_arg) {
+    if constexpr (ACT == DPPO_ACT_RELU) return relu_f(x);
+    else if constexpr (ACT == DPPO_ACT_BY_ARG) return smooth_act_by_arg(by_arg, x);
+    else return smooth_actf<ACT>(x);
 }
 // LDS_READY(...): an empty asm statement that "uses" its operands: every one of them is loaded
 // before it, so their loads issue together and pay one LDS round trip (left alone, hipcc sank each
@@ -186,6 +188,7 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
     // 16x16x4 MFMAs, the fold from RT_FOLD and the residual from W_OUT, exact fp32 operands)
     constexpr bool TWO = sizeof(AT) == 2;
     constexpr int KGP = Pol::KG;
+    const int by_arg = sa.a.act;           // read by act_f<DPPO_ACT_BY_ARG> only
     auto pack_bf16x2 = [](float lo, float hi) {
         if constexpr (TWO) return Pol::pack2(lo, hi);
         else return 0u;
@@ -566,11 +569,11 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
                 const int f = 16 * (NTI * wave + n) + 4 * jq;
                 if constexpr (TWO) {
                     u32x2 pk;
-                    pk[0] = pack_bf16x2(act_f<ACT>(h1[n][0]), act_f<ACT>(h1[n][1]));
-                    pk[1] = pack_bf16x2(act_f<ACT>(h1[n][2]), act_f<ACT>(h1[n][3]));
+                    pk[0] = pack_bf16x2(act_f<ACT>(h1[n][0], by_arg), act_f<ACT>(h1[n][1], by_arg));
+                    pk[1] = pack_bf16x2(act_f<ACT>(h1[n][2], by_arg), act_f<ACT>(h1[n][3], by_arg));
                     *(u32x2*)(u1 + env * ldh + f) = pk;
                 } else {
-                    *(f32x4*)(u1 + env * ldh + f) = f32x4{act_f<ACT>(h1[n][0]), act_f<ACT>(h1[n][1]), act_f<ACT>(h1[n][2]), act_f<ACT>(h1[n][3])};
+                    *(f32x4*)(u1 + env * ldh + f) = f32x4{act_f<ACT>(h1[n][0], by_arg), act_f<ACT>(h1[n][1], by_arg), act_f<ACT>(h1[n][2], by_arg), act_f<ACT>(h1[n][3], by_arg)};
                 }
             }
         }
@@ -630,13 +633,13 @@ __global__ __launch_bounds__(SWV * 64) void sample_split4_kernel(SplitArgs sa) {
             for (int tt = 0; tt < NL1; ++tt) {
                 u32x4 ba;
                 if constexpr (TWO) {
-                    ba[0] = pack_bf16x2(act_f<ACT>(acc[tt][0]), act_f<ACT>(acc[tt][1]));
-                    ba[1] = pack_bf16x2(act_f<ACT>(acc[tt][2]), act_f<ACT>(acc[tt][3]));
+                    ba[0] = pack_bf16x2(act_f<ACT>(acc[tt][0], by_arg), act_f<ACT>(acc[tt][1], by_arg));
+                    ba[1] = pack_bf16x2(act_f<ACT>(acc[tt][2], by_arg), act_f<ACT>(acc[tt][3], by_arg));
                     ba[2] = ba[0];
                     ba[3] = ba[1];
                 } else {
-                    ba = __builtin_bit_cast(u32x4, f32x4{act_f<ACT>(acc[tt][0]), act_f<ACT>(acc[tt][1]), act_f<ACT>(acc[tt][2]),
-                                                         act_f<ACT>(acc[tt][3])});
+                    ba = __builtin_bit_cast(u32x4, f32x4{act_f<ACT>(acc[tt][0], by_arg), act_f<ACT>(acc[tt][1], by_arg), act_f<ACT>(acc[tt][2], by_arg),
+                                                         act_f<ACT>(acc[tt][3], by_arg)});
                 }
 #pragma unroll
                 for (int n = 0; n < NO; ++n) po[n] = Pol::mma(rfold[tt][n], ba, po[n]);
@@ -997,6 +1000,11 @@ int launch_sample_split_a(const SampleArgs& a, int precision, hipStream_t s) {
 }  // namespace
 
 int launch_sample_split(const SampleArgs& a, int precision, int act, hipStream_t s) {
-    return act == DPPO_ACT_MISH ? launch_sample_split_a<DPPO_ACT_MISH>(a, precision, s)
-                                : launch_sample_split_a<DPPO_ACT_RELU>(a, precision, s);
+    switch (act) {   // dppo_act_ok's five values: the image registry holds no other
+        case DPPO_ACT_RELU: return launch_sample_split_a<DPPO_ACT_RELU>(a, precision, s);
+        case DPPO_ACT_MISH: return launch_sample_split_a<DPPO_ACT_MISH>(a, precision, s);
+        case DPPO_ACT_ELU: case DPPO_ACT_GELU: case DPPO_ACT_SOFTPLUS:   // one set, which follows a.act
+            return launch_sample_split_a<DPPO_ACT_BY_ARG>(a, precision, s);
+    }
+    return dppo_set_error(DPPO_EINVAL, "dppo_sample: bad activation %d", act);
 }

@@ -8,7 +8,9 @@ import math
 
 import numpy as np
 
-SUPPORTED_ACTIVATIONS = ("ReLU", "Mish")
+# the actor's activations (include/dppo.h DPPO_ACT_*; GELU is the erf form). The critic's shapes below require Mish
+# themselves (_critic_ln_shape, MLP.layers4; CriticObs refuses every other name before it gets here)
+SUPPORTED_ACTIVATIONS = ("ReLU", "Mish", "ELU", "GELU", "Softplus")
 # layer normalisation is implemented for the critic's shape only: [in, 256, 256, 256, 1] with Mish, the one hidden
 # width the critic row tile instantiates (csrc/rowtile.hip; include/dppo.h dppo_pack_critic_ln)
 LAYERNORM_HIDDEN = 256
@@ -52,7 +54,7 @@ class ResidualMLP:
             raise NotImplementedError("out_activation_type must be Identity")
         self.use_layernorm = bool(use_layernorm)
         if activation_type not in SUPPORTED_ACTIVATIONS:
-            raise NotImplementedError(f"activation {activation_type} not implemented")
+            raise NotImplementedError(f"activation {activation_type} not implemented (the kernels implement {', '.join(SUPPORTED_ACTIVATIONS)})")
         self.dim_list = dim_list
         self.activation_type = activation_type
 
@@ -102,7 +104,7 @@ class MLP:
         if out_activation_type != "Identity":
             raise NotImplementedError(f"MLP out_activation_type {out_activation_type!r}: the kernels implement {self.SHAPE}")
         if activation_type not in SUPPORTED_ACTIVATIONS:
-            raise NotImplementedError(f"activation {activation_type} not implemented")
+            raise NotImplementedError(f"activation {activation_type} not implemented (the kernels implement {', '.join(SUPPORTED_ACTIVATIONS)})")
         self.dim_list = dim_list
         self.activation_type = activation_type
         self.use_layernorm = bool(use_layernorm)

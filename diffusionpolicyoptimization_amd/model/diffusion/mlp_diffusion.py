@@ -7,7 +7,7 @@ only inside the fused HIP kernels (sampler / logprob / PPO update), so this clas
 configuration + parameter container."""
 import numpy as np
 
-from ..common.mlp import MLP, ResidualMLP, glorot_uniform
+from ..common.mlp import MLP, SUPPORTED_ACTIVATIONS, ResidualMLP, glorot_uniform
 
 
 class DiffusionMLP:
@@ -15,8 +15,9 @@ class DiffusionMLP:
                  activation_type="Mish", out_activation_type="Identity", use_layernorm=False, residual_style=False):
         if cond_mlp_dims is not None:
             raise NotImplementedError("cond_mlp_dims (obs encoder) is not used by the gym fine-tune cfgs")
-        if activation_type not in ("ReLU", "Mish"):
-            raise NotImplementedError(f"activation_type {activation_type!r}: the actor kernels implement ReLU and Mish")
+        if activation_type not in SUPPORTED_ACTIVATIONS:
+            raise NotImplementedError(f"activation_type {activation_type!r}: the actor kernels implement "
+                                      f"{', '.join(SUPPORTED_ACTIVATIONS)}")
         if use_layernorm:   # the critic's kernels have the norm (CriticObs); the actor's folded image does not
             raise NotImplementedError("DiffusionMLP(use_layernorm=True): layer normalisation is implemented for the critic only")
         self.action_dim, self.horizon_steps, self.cond_dim, self.time_dim = action_dim, horizon_steps, cond_dim, time_dim

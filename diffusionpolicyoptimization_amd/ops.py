@@ -31,7 +31,8 @@ class ModelDims:
     denoising_steps: int = 20       # sampling steps (DDIM: ddim_steps)
     ft_denoising_steps: int = 10
     time_stride: int = 1            # diffusion time of sampling row r is r * time_stride (DDIM: K / S)
-    # the actor's activation_type, "ReLU" or "Mish". Python-only: it is no field of dppo_dims; pack_actor
+    # the actor's activation_type, a key of _lib.ACTOR_ACTIVATION ("ReLU", "Mish", "ELU", "GELU", "Softplus").
+    # Python-only: it is no field of dppo_dims; pack_actor
     # records it with the packed image (dppo_pack_actor_act) and every kernel launch follows the image
     activation: str = "ReLU"
     # the actor's head, "residual" (ResidualMLP) or "plain" (MLP([in, h, h, out]), residual_style=False).
@@ -48,8 +49,8 @@ class ModelDims:
     critic_layernorm: bool = False
 
     def __post_init__(self):
-        if self.activation not in _lib.ACTIVATION:
-            raise ValueError(f"activation must be one of {sorted(_lib.ACTIVATION)}, got {self.activation!r}")
+        if self.activation not in _lib.ACTOR_ACTIVATION:
+            raise ValueError(f"activation must be one of {sorted(_lib.ACTOR_ACTIVATION)}, got {self.activation!r}")
         if self.head not in _lib.HEAD:
             raise ValueError(f"head must be one of {sorted(_lib.HEAD)}, got {self.head!r}")
         if self.critic_head not in _lib.HEAD:
@@ -540,7 +541,7 @@ def pack_actor(d: ModelDims, params_flat, precision, out=None):
         out = torch.empty(_packed_bytes(d, p)[0], dtype=torch.uint8, device=params_flat.device)
     else:
         _check(out, (_packed_bytes(d, p)[0],), torch.uint8, "packed actor")
-    _lib.call("dppo_pack_actor_head", ctypes.byref(_dims_c(d)), p, _lib.ACTIVATION[d.activation], _lib.HEAD[d.head],
+    _lib.call("dppo_pack_actor_head", ctypes.byref(_dims_c(d)), p, _lib.ACTOR_ACTIVATION[d.activation], _lib.HEAD[d.head],
               ptr(params_flat), ptr(out), stream_handle(params_flat.device))
     _forget_on_free(out)
     return out
@@ -984,7 +985,7 @@ def ppo_plan(d: ModelDims, precision, rows, mode="train"):
     are 0 where the mode has no such launch. The plan is d.activation's (dppo_ppo_plan_act): a Mish actor
     runs the 32-row tile on 8 waves at every row count. The critic's row tile: ppo_plan_critic."""
     out = (ctypes.c_int * 6)()
-    _lib.call("dppo_ppo_plan_act", ctypes.byref(d.c()), _prec(precision), _lib.ACTIVATION[d.activation], int(rows),
+    _lib.call("dppo_ppo_plan_act", ctypes.byref(d.c()), _prec(precision), _lib.ACTOR_ACTIVATION[d.activation], int(rows),
               _PLAN_MODES[mode], out)
     return dict(actor_tile_rows=out[0], actor_waves=out[1], dw_chunks_actor=out[2], dw_chunk_rows_actor=out[3],
                 dw_chunks_critic=out[4], dw_chunk_rows_critic=out[5])

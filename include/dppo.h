@@ -121,7 +121,11 @@ typedef struct dppo_dims {
  * every row count and precision: the 64-row tile of large 2-byte minibatches and the fp32 16-wave tile
  * (4 waves per SIMD, 128 registers) have no room for them and are not instantiated for Mish, and neither
  * is their K' <= 23 LDS line (a Mish actor takes every K' <= 64 at every row count). dppo_ppo_plan_act
- * reports the tile. tests/test_actor_mish_gpu.py pins this. */
+ * reports the tile. tests/test_actor_mish_gpu.py pins this.
+ * ELU, GELU and Softplus actor images (DPPO_ACT_ELU / _GELU / _SOFTPLUS) are Mish images in every respect
+ * above: none of their derivatives can be read off the stored activation, so they carry h1 and h2, run
+ * the same 32-row tile on 8 waves with the same plan, take every K' <= 64, and are accepted and refused
+ * exactly where Mish images are, with the same messages (tests/test_actor_activations_gpu.py). */
 
 /* Schedule table, one fp32 row per sampling row r (r = t for DDPM; the DDIM sub-sequence index for
  * DDIM): {c0, c1, c2, c3, logvar, eval_floor, eval_zero, 0} with
@@ -195,8 +199,15 @@ DPPO_API int dppo_pack_critic(const dppo_dims* d, int precision, const float* pa
  * dppo_logprob, dppo_ppo_minibatch{,_part}, dppo_pretrain_minibatch) looks the image up (ReLU when it was
  * never packed through these entries) and runs that activation's kernels. An activation outside the
  * enum is refused with DPPO_EINVAL; so is a sampler launch whose base and fine-tuned images carry
- * different activations, before anything is enqueued. The critic is Mish always (critic.py:40-54). */
-enum { DPPO_ACT_RELU = 0, DPPO_ACT_MISH = 1 };
+ * different activations, before anything is enqueued. The critic is Mish always (critic.py:40-54).
+ * The values follow the reference's activation_dict: relu; mish = x tanh(softplus(x)); elu with alpha = 1
+ * (x > 0 ? x : expm1(x)); gelu in its erf form (x Phi(x), keras' approximate=False, not the tanh
+ * approximation); softplus = log1p(e^x). Value 2 is RESERVED for Tanh and refused like any value outside
+ * the enum ("dppo_pack_actor_act: bad activation 2 ..."): no kernel implements it yet, and its number is
+ * kept so that a later Tanh does not renumber the values below. An activation has no parameters: the image
+ * bytes of a pack do not depend on it. */
+enum { DPPO_ACT_RELU = 0, DPPO_ACT_MISH = 1, /* 2 reserved, refused */ DPPO_ACT_ELU = 3, DPPO_ACT_GELU = 4,
+       DPPO_ACT_SOFTPLUS = 5 };
 DPPO_API int dppo_pack_actor_act(const dppo_dims* d, int precision, int activation, const float* params, void* packed,
                                  void* stream);
 /* The actor's head (DiffusionMLP residual_style, model/diffusion/mlp_diffusion.py:12-25), the image's second
@@ -332,7 +343,8 @@ DPPO_API int dppo_forget_image(const void* packed);
  * Mish actor images (dppo_pack_actor_act; both images of a launch carry the same activation, else
  * DPPO_EINVAL) run on every line above, on the same kernel (dppo_sampler_plan does not depend on the
  * activation), and are refused where ReLU images are, with the same messages
- * (tests/test_actor_mish_gpu.py).                                                             */
+ * (tests/test_actor_mish_gpu.py). ELU, GELU and Softplus images run and are refused exactly where Mish
+ * images are, with the same messages (tests/test_actor_activations_gpu.py).                    */
 DPPO_API int dppo_sample(const dppo_dims* d, int precision, const void* packed_base, const void* packed_ft,
                 const float* sched, const float* cond, int n_envs, const float* x_T, const float* noise,
                 uint64_t seed, uint64_t call_id, int env_offset, int deterministic,
@@ -577,7 +589,7 @@ DPPO_API size_t dppo_ppo_workspace_bytes(const dppo_dims* d, int precision, int 
 enum { DPPO_PLAN_TRAIN = 0, DPPO_PLAN_PRETRAIN = 1, DPPO_PLAN_LOGPROB = 2 };
 DPPO_API int dppo_ppo_plan(const dppo_dims* d, int precision, int rows, int mode, int* out);
 /* the same for an actor image of the given activation (DPPO_ACT_*; dppo_ppo_plan is the ReLU plan): a
- * Mish actor runs the 32-row tile on 8 waves at every row count (the table above) */
+ * Mish, ELU, GELU or Softplus actor runs the 32-row tile on 8 waves at every row count (the table above) */
 DPPO_API int dppo_ppo_plan_act(const dppo_dims* d, int precision, int activation, int rows, int mode, int* out);
 /* The critic's row tile for an image of the given attributes (dppo_pack_critic_ln), which the six outputs above have
  * no field for; host arithmetic, no image, no device work (an addition within ABI 15). out[3] = {the tile's rows (32),

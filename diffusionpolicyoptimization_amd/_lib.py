@@ -22,6 +22,9 @@ DPPO_PPO_LEARN_ETA = 2                   # (ABI 9) d loss / d eta into metrics[8
 DPPO_STEP_FUSED_PACK = 0x400             # (ABI 11) AdamW + the image in one launch
 DPPO_STEP_CLEAR_GRADS = 0x800            # (ABI 11) the step zeroes the range's gradients after reading
 DPPO_PPO_PRECLEARED = 4                  # (ABI 11) the part's accumulators are already zero
+DPPO_PPO_ADV_CLIP = 8                    # (within ABI 15) adv_stats is fp64[5]: the row tiles clamp to {lo, hi}
+# the quantile select's count launch: threads per workgroup, workgroups per segment at most (include/dppo.h)
+DPPO_ADV_QUANTILES_BLOCK, DPPO_ADV_QUANTILES_MAX_CHUNKS = 256, 16
 DPPO_NET_ACTOR, DPPO_NET_CRITIC = 1, 2   # dppo_grad_clip_scales / dppo_optimizer_step_clip: OR'd, 3 = [actor | critic]
 SCHED_COLS = 8
 PRECISION = {"fp32": DPPO_F32, "f32": DPPO_F32, "bf16": DPPO_BF16, "fp16": DPPO_F16, "f16": DPPO_F16}
@@ -114,6 +117,10 @@ _SIGNATURES = {
     "dppo_ppo_plan_critic": (_I, [_DIMS, _I, _I, _I, ctypes.POINTER(ctypes.c_int)]),
     "dppo_ppo_adv_stats": (_I, [_P, _I64, _I, _U64, _I, _I64, _I, _P, _P, _P]),
     "dppo_ppo_adv_stats_all": (_I, [_P, _I64, _I, _U64, _I, _I, _I64, _I, _P, _P]),
+    "dppo_ppo_adv_quantiles_workspace_bytes": (_SZ, [_I, _I]),
+    "dppo_ppo_adv_quantiles_all": (_I, [_P, _I64, _I, _U64, _I, _I, _I64, _I, _D, _D, _P, _P, _P]),
+    "dppo_ppo_adv_quantiles_count": (_I, [_P, _I64, _I, _U64, _I, _I, _I64, _I, _I, _P, _P, _P]),
+    "dppo_ppo_adv_quantiles_pick": (_I, [_I, _I, _D, _D, _I, _P, _P, _P, _P, _P]),
     "dppo_ppo_minibatch": (_I, [_DIMS, _I, ctypes.POINTER(DppoPpoHparams), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                _I64, _U64, _I, _I64, _I, _P, _P, _P, _P, _P, _P]),
     "dppo_pretrain_minibatch": (_I, [_DIMS, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I64, _F, _P, _P, _P, _P]),

@@ -191,6 +191,9 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         self.emulate_world = max(1, int(cfg.train.get("emulate_world", 1)))
         if self.emulate_world > 1 and self.world_size > 1:
             raise ValueError("train.emulate_world is a single-process measurement mode")
+        if self.model.adv_clip and self.update_epochs > 64:   # one select launch carries every epoch's Feistel key
+            raise ValueError(f"train.update_epochs = {self.update_epochs} > 64 with the advantage clip on "
+                             "(dppo_ppo_adv_quantiles_all takes at most 64 epochs per update)")
         self.sampler_events = None    # optional list of (start, end) torch.cuda.Event pairs
         self.update_events = None
         self.host_profile = None      # optional dict: host seconds per update-loop phase (tools)
@@ -203,6 +206,8 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         self._ev_map = None          # explained-variance moments, mapped host memory
         self._metrics = None         # _PendingMetrics: mapped metric slots, their events, the tag counter
         self._adv_all = None         # every minibatch's advantage moments, fp64 [n_mb, 3]
+        self._adv_clip = self._adv_bounds = self._adv_sel = None   # with the advantage clip on: _update_resources
+        self._adv_n = self._adv_n_key = None   # data parallel: every segment's rows over all ranks, int64 [n_mb]
         self._side = None            # the split update's side stream (tools/cu_mask_probe.py swaps it)
         self._met_dev = self._ev_rows = self._ev_met = None   # ... its two metric buffers and events
         self._clip_buf = None        # device clip: (norms, scales, actor workspace, critic workspace)
@@ -507,6 +512,15 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
             self._metrics = _PendingMetrics()
         if self._adv_all is None or self._adv_all.shape[0] != n_mb:
             self._adv_all = torch.zeros(n_mb, 3, dtype=torch.float64, device=dev)
+        if self.model.adv_clip and (self._adv_clip is None or self._adv_clip.shape[0] != n_mb):
+            # the clipped update's table, fp64 [n_mb, 5] = {count, sum, sumsq, lo, hi}; the bounds as the select
+            # writes them; its count table and state (one rank: inside the entry's workspace)
+            self._adv_clip = torch.zeros(n_mb, 5, dtype=torch.float64, device=dev)
+            self._adv_bounds = torch.zeros(n_mb, 2, dtype=torch.float64, device=dev)
+            if self.world_size > 1:
+                self._adv_sel = ops.ppo_adv_quantiles_state(n_mb, 1, dev)
+            else:
+                self._adv_sel = ops.ppo_adv_quantiles_workspace(n_mb, 1, dev)
         if split and self._side is None:
             self._side = torch.cuda.Stream(device=dev)
         if split and self._met_dev is None:
@@ -588,6 +602,7 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
                      m.packed_ft, m.packed_critic, m.sched, m.workspace(rows_local_full), opt.m, opt.v),
                 self.perm_seed, rows_local_full, self.reward_horizon, split,
                 self.max_grad_norm is None, m.dims.ft_denoising_steps, m.precision, fuse,
+                m.adv_clip,   # in the bound minibatch's cached hparams (DPPO_PPO_ADV_CLIP)
                 (ptrs(*self._clip_buf), clip_c) if clip_dev else None)
         if self._bound_key == bkey:
             return self._bound
@@ -734,6 +749,38 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
                             n_metrics=5, metrics_tag=tag, defer_sampler_tables=True)
         return clipped_step
 
+    def _adv_clip_table(self, adv_flat, total_local, kf, rows_local_full, num_batch, dp):
+        """The clipped update's per-minibatch table fp64 [n_mb, 5] = {count, sum, sumsq, lo, hi}: the moments of
+        self._adv_all (already all-reduced) and each minibatch's advantage quantiles (PPODiffusion's
+        clip_advantage_*_quantile; ops.ppo_adv_quantiles_all), about ten launches per update and no host wait.
+        Data parallelism: the pass loop with one SUM all-reduce of the count table per pass, so every rank gets
+        the quantiles of the union of the ranks' rows (n = rows * W). train.emulate_world runs ONE rank's share
+        with every collective skipped, so there the quantiles are those of this rank's rows alone (n = the local
+        rows): the launches and their cost are a rank's, the bounds are not the W-rank run's."""
+        m = self.model
+        q_lo, q_hi = m.clip_advantage_lower_quantile, m.clip_advantage_upper_quantile
+        geom = (adv_flat, total_local, kf, self.perm_seed, 1000 * self.itr, self.update_epochs, rows_local_full, num_batch)
+        if dp:
+            counts, state = self._adv_sel
+            key = (total_local, rows_local_full, num_batch, self.update_epochs, self.world_size)
+            if self._adv_n_key != key:   # every rank draws the same window lengths: n_global = rows * W
+                rows = [max(0, min(rows_local_full, total_local - b * rows_local_full)) for b in range(num_batch)]
+                self._adv_n = torch.tensor(rows * self.update_epochs, dtype=torch.int64,
+                                           device=self.device) * self.world_size
+                self._adv_n_key = key
+            counts.zero_()
+            for p in range(4):
+                ops.ppo_adv_quantiles_count(*geom, p, state, counts)
+                self._allreduce(counts)
+                ops.ppo_adv_quantiles_pick(self.update_epochs, num_batch, q_lo, q_hi, p, state, counts,
+                                           out=self._adv_bounds, n_global=self._adv_n)
+        else:
+            ops.ppo_adv_quantiles_all(*geom, q_lo, q_hi, self._adv_bounds, workspace=self._adv_sel)
+        tab = self._adv_clip
+        tab[:, :3].copy_(self._adv_all)
+        tab[:, 3:].copy_(self._adv_bounds)
+        return tab
+
     def update(self):
         m, opt = self.model, self.actor_optimizer
         kf = m.ft_denoising_steps
@@ -766,6 +813,10 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
                               rows_local_full, num_batch, self._adv_all)
         if dp:
             self._allreduce(self._adv_all)
+        adv_tab = self._adv_all
+        if m.adv_clip:   # off (quantiles (0, 1)): no call, no buffer, the stride-3 table as ever
+            adv_tab = self._adv_clip_table(adv_flat, total_local, kf, rows_local_full, num_batch, dp)
+        adv_stride = 8 * adv_tab.shape[1]
         # the epochs run on the caller's stream (a high-priority stream for the actor's half, r03, was
         # measured slower: update 15.0 vs 14.8 ms per iteration, tools/ab_env.sh)
         stream = torch.cuda.current_stream(self.device)
@@ -782,7 +833,7 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
             enqueue = self._enqueue_unsplit(run_mb, dp)
             step, mets = self._step_unsplit(bound, clip_c), (m.metrics, m.metrics)
         hp_, events, hook, learn_eta = self.host_profile, self.update_events, self.minibatch_hook, self.learn_eta
-        adv_base, epoch0, steps0 = self._adv_all.data_ptr(), 1000 * self.itr, opt.iterations
+        adv_base, epoch0, steps0 = adv_tab.data_ptr(), 1000 * self.itr, opt.iterations
         info = {}
         last_mb = None    # (epoch key, start, rows) of the last minibatch run (the bc_loss report)
         cleared = False   # the previous optimizer step zeroed this minibatch's accumulators
@@ -802,7 +853,7 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
                 mb = (update_epoch + epoch0, start, rows)
                 prev_mb, last_mb = last_mb, mb
                 slot = k % 2
-                enqueue(mb, global_rows, adv_base + 24 * (update_epoch * num_batch + batch),   # its fp64[3] row
+                enqueue(mb, global_rows, adv_base + adv_stride * (update_epoch * num_batch + batch),   # its fp64[3 | 5] row
                         cleared and rows == rows_local_full, slot)
                 if hook is not None:
                     if split:

@@ -89,6 +89,7 @@ struct LossHP {
     float eta_unscale;    // learnable DDIM eta (DPPO_PPO_LEARN_ETA): 1 / the fp16 seed scale, else 0
     float clip_vloss;     // > 0: the clipped value loss against old_values (diffusion_ppo.py:110-116)
     const float* old_values;
+    int adv_clip;         // DPPO_PPO_ADV_CLIP: adv_stats[3], [4] bound the raw advantage
 };
 
 struct ActorArgs {
@@ -109,7 +110,7 @@ struct ActorArgs {
     const int64_t* row_index;
     const float* lp_old;   // [nsamp][KF]
     const float* adv;      // [nsamp]
-    const double* adv_stats;
+    const double* adv_stats;   // fp64[3] {count, sum, sumsq}; hp.adv_clip: fp64[5], then {lo, hi}
     LossHP hp;
     PpoWorkspace ws;
     double* metrics;

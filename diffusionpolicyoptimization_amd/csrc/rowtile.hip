@@ -144,7 +144,7 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
     int* rj = (int*)(smem + S.rj);
     float* radv = (float*)(smem + S.radv);   // per row: the row's advantage (train)
     float* rlpo = (float*)(smem + S.rlpo);   // per row: its old log-prob (train)
-    float* nrm = (float*)(smem + S.nrm);     // advantage normalisation: mean, std + 1e-8
+    float* nrm = (float*)(smem + S.nrm);     // advantage normalisation: mean, std + 1e-8; clip bounds lo, hi
     float* part = (float*)(smem + S.tA);   // out-layer partials alias tA (relu(h1) is dead after L2)
     const size_t grow0 = (size_t)a.row0 + (size_t)blockIdx.x * ROWS;
     const __amdgpu_buffer_rsrc_t wsr = packed_rsrc(a.ws.base);
@@ -200,6 +200,8 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
         const double var = fmax(S3[2] / S3[0] - mean * mean, 0.0);
         pre_m = (float)mean;
         pre_s = (float)(sqrt(var) + 1e-8);
+        // the clip bounds ride to LDS in this thread's row registers (rows are tid < ROWS)
+        if (a.hp.adv_clip) { pre_adv = (float)S3[3]; pre_lpo = (float)S3[4]; }
     }
     lds_sync();
     // time embeddings t_emb(r TS), r < K' (mlp_diffusion.py:40-45): rows of the image's TEMB table,
@@ -300,7 +302,10 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
     PHASE(1);
     if (train && !pre) {   // loaded in the prologue, read from the epilogue on (after later barriers)
         if (tid < ROWS) { radv[tid] = pre_adv; rlpo[tid] = pre_lpo; }
-        else if (tid == ROWS) { nrm[0] = pre_m; nrm[1] = pre_s; }
+        else if (tid == ROWS) {
+            nrm[0] = pre_m; nrm[1] = pre_s;
+            if (a.hp.adv_clip) { nrm[2] = pre_adv; nrm[3] = pre_lpo; }
+        }
     }
     // ---- L2: h2 = act(h1) W_l1 + b ----
     if constexpr (train)
@@ -427,6 +432,9 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
                 if (n >= 0 && a.lp_mean) a.lp_mean[(size_t)n * KF + j] = newlp;
             } else if (n >= 0) {
                 float A = radv[r];
+                // the minibatch's quantile bounds on the raw advantage (DPPO_PPO_ADV_CLIP); the moments stay
+                // those of the unclipped minibatch
+                if (a.hp.adv_clip) A = fminf(fmaxf(A, nrm[2]), nrm[3]);
                 if (a.hp.norm_adv) A = (A - nrm[0]) / nrm[1];   // population std over the minibatch (:74-75)
                 A *= powf(a.hp.gamma_denoising, (float)(KF - j - 1));                 // :83-86
                 const float oldlp = rlpo[r];

@@ -463,8 +463,12 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     DPPO_CHECK(part >= MB_ACTOR && part <= MB_ACTOR_DW, "dppo_ppo_minibatch: bad part %d", (int)part);
     const bool needs_adv = part == MB_WHOLE || part == MB_ACTOR || part == MB_ACTOR_TILES;   // runs the actor's row tiles
     DPPO_CHECK(part == MB_WHOLE || m.adv_stats || !needs_adv, "dppo_ppo_minibatch_part: the actor half needs adv_stats");
-    DPPO_CHECK((hp->flags & ~(DPPO_PPO_L2_DEFERRED | DPPO_PPO_LEARN_ETA | DPPO_PPO_PRECLEARED)) == 0,
+    DPPO_CHECK((hp->flags & ~(DPPO_PPO_L2_DEFERRED | DPPO_PPO_LEARN_ETA | DPPO_PPO_PRECLEARED | DPPO_PPO_ADV_CLIP)) == 0,
                "dppo_ppo_minibatch: unknown flags 0x%x", hp->flags);
+    // the bounds follow the moments in the caller's table: there is none to compute locally (every part: the
+    // critic's half of a clipped minibatch is handed the same pointer)
+    DPPO_CHECK(!(hp->flags & DPPO_PPO_ADV_CLIP) || m.adv_stats,
+               "dppo_ppo_minibatch: DPPO_PPO_ADV_CLIP needs adv_stats fp64[5] {count, sum, sumsq, lo, hi}");
     DPPO_CHECK((uint64_t)m.total < ((uint64_t)1 << 32), "dppo_ppo_minibatch: %lld samples x steps exceed 2^32",
                (long long)m.total);
     const FeistelKey fk = feistel_key((uint64_t)m.total, m.perm_seed, m.epoch);
@@ -473,6 +477,7 @@ static int ppo_minibatch_impl(const MinibatchArgs& m, MbPart part) {
     lh.clip_coef_base = hp->clip_ploss_coef_base; lh.clip_coef_rate = hp->clip_ploss_coef_rate;
     lh.min_lp_std = hp->min_logprob_std; lh.vf_coef = hp->vf_coef; lh.norm_adv = hp->norm_adv;
     lh.reward_horizon = hp->reward_horizon;
+    lh.adv_clip = (hp->flags & DPPO_PPO_ADV_CLIP) != 0;
     // fp16: the backward images carry GRAD_SCALE x the gradient (fp16 range); dW divides it out
     const float gscale = dppo_grad_scale_rows(precision, hp->global_rows);
     lh.grad_scale = hp->loss_scale / (float)hp->global_rows * gscale;

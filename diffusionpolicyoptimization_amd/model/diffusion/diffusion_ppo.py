@@ -19,18 +19,31 @@ class PPODiffusion(VPGDiffusion):
     def __init__(self, gamma_denoising, clip_ploss_coef, clip_ploss_coef_base=1e-3, clip_ploss_coef_rate=3,
                  clip_vloss_coef=None, clip_advantage_lower_quantile=0, clip_advantage_upper_quantile=1, norm_adv=True,
                  vf_coef=0.5, **kwargs):
+        # the DPPO algorithm's advantage clip, which the reference comments out (:77-80): each minibatch's
+        # advantages are clamped to their own quantiles (linear interpolation, torch.quantile's) before the
+        # denoising discount. (0, 1), the defaults, clip nothing and run the update exactly as without the knobs.
+        # Refused before anything is built
+        if not 0 <= clip_advantage_lower_quantile < clip_advantage_upper_quantile <= 1:
+            raise ValueError("PPODiffusion: need 0 <= clip_advantage_lower_quantile < clip_advantage_upper_quantile "
+                             f"<= 1, got ({clip_advantage_lower_quantile}, {clip_advantage_upper_quantile})")
         super().__init__(**kwargs)
         self.gamma_denoising = gamma_denoising
         self.clip_ploss_coef = clip_ploss_coef
         self.clip_ploss_coef_base = clip_ploss_coef_base
         self.clip_ploss_coef_rate = clip_ploss_coef_rate
         self.clip_vloss_coef = clip_vloss_coef
-        self.clip_advantage_lower_quantile = clip_advantage_lower_quantile  # unused, as in the reference (:77-80)
-        self.clip_advantage_upper_quantile = clip_advantage_upper_quantile
+        self.clip_advantage_lower_quantile = float(clip_advantage_lower_quantile)
+        self.clip_advantage_upper_quantile = float(clip_advantage_upper_quantile)
         self.norm_adv = norm_adv
         self.vf_coef = vf_coef
         self.metrics = torch.zeros(16, dtype=torch.float64, device=self.device)
         self._ws = {}
+
+    @property
+    def adv_clip(self):
+        """Whether the advantage quantiles clip anything: the minibatch calls then take adv_stats fp64[5]
+        {count, sum, sumsq, lo, hi} (DPPO_PPO_ADV_CLIP; the bounds from ops.ppo_adv_quantiles_all)."""
+        return (self.clip_advantage_lower_quantile, self.clip_advantage_upper_quantile) != (0.0, 1.0)
 
     def hparams(self, global_rows, reward_horizon=4, loss_scale=1.0, l2_deferred=False, old_values=None):
         """old_values: the rollout's value pass (fp32 [S*E] by sample), read by the clipped value loss when
@@ -39,7 +52,8 @@ class PPODiffusion(VPGDiffusion):
                                self.clip_ploss_coef_rate, self.min_logprob_denoising_std, self.vf_coef, self.norm_adv,
                                reward_horizon, loss_scale, global_rows, l2_deferred=l2_deferred,
                                learn_eta=self.learn_eta, clip_vloss_coef=self.clip_vloss_coef,
-                               old_values=old_values if self.clip_vloss_coef is not None else None)
+                               old_values=old_values if self.clip_vloss_coef is not None else None,
+                               adv_clip=self.adv_clip)
 
     def workspace(self, rows):
         ws = self._ws.get(rows)
@@ -53,7 +67,11 @@ class PPODiffusion(VPGDiffusion):
         """One fused PPO minibatch over HBM rollout buffers (obs [N,SD], chains [N,K'+1,XD],
         lp_old_mean [N,K'], advantages/returns [N]); writes self.grads and self.metrics (sums).
         part = 1 / 2 runs only the actor / critic half on the current stream (metrics: an
-        alternative fp64[16] buffer)."""
+        alternative fp64[16] buffer). With the advantage clip on (adv_clip), adv_stats is the minibatch's
+        fp64[5] {count, sum, sumsq, lo, hi} and must be given."""
+        if self.adv_clip and adv_stats is None:
+            raise ValueError("PPODiffusion.minibatch: the advantage clip needs adv_stats fp64[5] "
+                             "{count, sum, sumsq, lo, hi} (ops.ppo_adv_stats, ops.ppo_adv_quantiles_all)")
         hp = self.hparams(global_rows or rows, reward_horizon, loss_scale, old_values=old_values)
         ops.ppo_minibatch(self.dims, self.precision, hp, self.packed_ft, self.packed_critic, self.actor_ft_params,
                           self.sched, obs, chains, lp_old_mean, advantages, returns, perm_seed, epoch, start, rows,
@@ -131,8 +149,14 @@ class PPODiffusion(VPGDiffusion):
         oldv = None
         if self.clip_vloss_coef is not None:   # :110-116: sample n = row r of this batch
             oldv = torch.as_tensor(oldvalues, device=dev, dtype=torch.float32).reshape(b).contiguous()
+        stats = None
+        if self.adv_clip:   # row r is sample r once: the batch's quantiles are those of adv itself
+            stats = torch.empty(5, dtype=torch.float64, device=dev)
+            ops.ppo_adv_stats(adv, b * kf, kf, 0, 0, 0, b, stats[:3], row_index=row_index)
+            ops.ppo_adv_quantiles_all(adv, b, 1, 0, 0, 1, b, 1, self.clip_advantage_lower_quantile,
+                                      self.clip_advantage_upper_quantile, stats[3:].view(1, 2))
         self.minibatch(state, ch, lp_old, adv, ret, 0, 0, 0, b, reward_horizon=reward_horizon, row_index=row_index,
-                       old_values=oldv)
+                       old_values=oldv, adv_stats=stats)
         m = (self.metrics[:5] / b).cpu().numpy()
         eta = self.current_eta()
         # entropy_loss = -mean(eta), the last element mean(eta) (diffusion_ppo.py:49, 131); with

@@ -1015,15 +1015,82 @@ def ppo_adv_stats_all(advantages, total, kf, perm_seed, epoch0, n_epochs, rows_f
     return out
 
 
+def _check_quantiles(q_lo, q_hi):
+    if not 0.0 <= float(q_lo) < float(q_hi) <= 1.0:
+        raise ValueError(f"advantage quantiles: need 0 <= lower < upper <= 1, got ({q_lo}, {q_hi})")
+
+
+def ppo_adv_quantiles_workspace(n_epochs, n_batch, device):
+    nbytes = _lib.query("dppo_ppo_adv_quantiles_workspace_bytes", int(n_epochs), int(n_batch))
+    if nbytes == 0:
+        raise ValueError("ppo_adv_quantiles_workspace: n_epochs and n_batch must be > 0")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def ppo_adv_quantiles_all(advantages, total, kf, perm_seed, epoch0, n_epochs, rows_full, n_batch, q_lo, q_hi, out,
+                          workspace=None):
+    """out fp64 [n_epochs * n_batch, 2]: every minibatch's
+    advantage quantiles {Q(q_lo), Q(q_hi)} (dppo_ppo_adv_quantiles_all: numpy.quantile's linear method in fp64 on
+    exact order statistics; an empty window gets (-inf, +inf)). About ten launches, no host wait."""
+    n_seg = int(n_epochs) * int(n_batch)
+    _check_quantiles(q_lo, q_hi)
+    if workspace is None:
+        workspace = ppo_adv_quantiles_workspace(n_epochs, n_batch, advantages.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != (n_seg, 2) or not out.is_contiguous():
+        raise ValueError(f"out: expected contiguous fp64 [{n_seg}, 2]")
+    _lib.call("dppo_ppo_adv_quantiles_all", ptr(advantages), int(total), int(kf), ctypes.c_uint64(perm_seed), int(epoch0),
+              int(n_epochs), int(rows_full), int(n_batch), float(q_lo), float(q_hi), ptr(workspace), ptr(out),
+              stream_handle(advantages.device))
+    return out
+
+
+def ppo_adv_quantiles_state(n_epochs, n_batch, device):
+    """(counts int32 [n_seg, 4, 256] zeroed, state int64 [n_seg, 9]) for the pass-level pair below."""
+    n_seg = int(n_epochs) * int(n_batch)
+    return (torch.zeros(n_seg, 4, 256, dtype=torch.int32, device=device),
+            torch.zeros(n_seg, 9, dtype=torch.int64, device=device))
+
+
+def ppo_adv_quantiles_count(advantages, total, kf, perm_seed, epoch0, n_epochs, rows_full, n_batch, pass_, state,
+                            counts):
+    """Pass pass_ (0..3) of the select: adds this rank's rows into counts (zero before pass 0; every pick leaves it
+    zero). A data-parallel caller SUM-all-reduces counts before ppo_adv_quantiles_pick."""
+    n_seg = int(n_epochs) * int(n_batch)
+    _check(counts, (n_seg, 4, 256), torch.int32, "counts")
+    _check(state, (n_seg, 9), torch.int64, "state")
+    _lib.call("dppo_ppo_adv_quantiles_count", ptr(advantages), int(total), int(kf), ctypes.c_uint64(perm_seed),
+              int(epoch0), int(n_epochs), int(rows_full), int(n_batch), int(pass_), ptr(state), ptr(counts),
+              stream_handle(advantages.device))
+
+
+def ppo_adv_quantiles_pick(n_epochs, n_batch, q_lo, q_hi, pass_, state, counts, out=None, n_global=None):
+    """Advances every segment's four targets by pass pass_'s byte; pass 3 writes out fp64 [n_seg, 2]. n_global
+    int64 [n_seg]: the segments' row counts over all ranks (None: the pass-0 counts' own sum)."""
+    n_seg = int(n_epochs) * int(n_batch)
+    _check_quantiles(q_lo, q_hi)
+    _check(counts, (n_seg, 4, 256), torch.int32, "counts")
+    _check(state, (n_seg, 9), torch.int64, "state")
+    if out is not None and (out.dtype != torch.float64 or tuple(out.shape) != (n_seg, 2) or not out.is_contiguous()):
+        raise ValueError(f"out: expected contiguous fp64 [{n_seg}, 2]")
+    if n_global is not None:
+        _check(n_global, (n_seg,), torch.int64, "n_global")
+    _lib.call("dppo_ppo_adv_quantiles_pick", int(n_epochs), int(n_batch), float(q_lo), float(q_hi), int(pass_),
+              ptr(n_global), ptr(state), ptr(counts), ptr(out), stream_handle(counts.device))
+    return out
+
+
 def ppo_hparams(gamma_denoising=0.99, clip_ploss_coef=0.01, clip_ploss_coef_base=0.01, clip_ploss_coef_rate=3.0,
                 min_logprob_std=0.1, vf_coef=0.5, norm_adv=True, reward_horizon=4, loss_scale=1.0, global_rows=1,
-                l2_deferred=False, learn_eta=False, clip_vloss_coef=None, old_values=None):
+                l2_deferred=False, learn_eta=False, clip_vloss_coef=None, old_values=None, adv_clip=False):
     """l2_deferred (ABI 8, DPPO_PPO_L2_DEFERRED): the actor's l2 gradient is left factored in grads
     for an optimizer step with l2_from_pl2 (or materialize_l2). learn_eta (ABI 9,
     DPPO_PPO_LEARN_ETA): the row tiles add d loss / d eta of a DDIM schedule into metrics[8].
     clip_vloss_coef (ABI 14, diffusion_ppo.py:110-116): the clipped value loss against old_values, the
-    rollout's value pass (device fp32 [S*E], indexed by sample; the caller keeps it alive)."""
-    flags = (_lib.DPPO_PPO_L2_DEFERRED if l2_deferred else 0) | (_lib.DPPO_PPO_LEARN_ETA if learn_eta else 0)
+    rollout's value pass (device fp32 [S*E], indexed by sample; the caller keeps it alive).
+    adv_clip (DPPO_PPO_ADV_CLIP): the minibatch's adv_stats is fp64[5] {count, sum, sumsq, lo, hi} and the row
+    tiles clamp the raw advantage to [lo, hi] (ppo_adv_quantiles_all computes the bounds)."""
+    flags = (_lib.DPPO_PPO_L2_DEFERRED if l2_deferred else 0) | (_lib.DPPO_PPO_LEARN_ETA if learn_eta else 0) | (
+        _lib.DPPO_PPO_ADV_CLIP if adv_clip else 0)
     clip = clip_vloss_coef is not None
     if clip and (old_values is None or old_values.dtype != torch.float32 or not old_values.is_cuda):
         raise ValueError("clip_vloss_coef needs the rollout's old values (fp32 device tensor)")

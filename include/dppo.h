@@ -556,6 +556,22 @@ enum { DPPO_PPO_LEARN_ETA = 2 };
  * metrics) are already zero — the previous optimizer step of the range cleared them
  * (DPPO_STEP_CLEAR_GRADS) — so the part skips its zeroing launch. */
 enum { DPPO_PPO_PRECLEARED = 4 };
+/* An addition within ABI 15, dppo_ppo_hparams.flags. DPPO_PPO_ADV_CLIP: PPODiffusion's clip_advantage_lower_quantile /
+ * clip_advantage_upper_quantile (the DPPO algorithm's live lines; the reference comments them out at
+ * diffusion_ppo.py:77-80, so parity is unpinned). The adv_stats pointer of dppo_ppo_minibatch / _part then addresses
+ * fp64[5] = {count, sum, sumsq, lo, hi} (launch-uniform), and the actor's TRAIN row tiles clamp each row's RAW
+ * advantage to [lo, hi] (rounded to fp32) before the normalisation, which keeps the mean and std of the UNCLIPPED
+ * minibatch ({count, sum, sumsq}), and before the denoising discount: in real arithmetic the reference's
+ * normalise-then-clamp, and the same with norm_adv off. dppo_ppo_adv_quantiles_all computes lo, hi.
+ *   accepted: every part, precision, row tile (32 and 64 rows), activation, head and DPPO_PPO_LEARN_ETA;
+ *             (lo, hi) = (-inf, +inf) gives the bits of the flag unset.
+ *   refused (DPPO_EINVAL, outputs untouched, nothing enqueued): the flag with adv_stats == NULL, in every part.
+ *   not checked: lo and hi are device memory, read by the kernel alone; no entry waits on the device to look at
+ *             them. lo > hi or a NaN bound is the caller's error (dppo_ppo_adv_quantiles_* never produce one).
+ *             What the tile then computes is fminf(fmaxf(A, lo), hi) with IEEE minNum / maxNum: lo > hi gives every
+ *             row the advantage hi; a NaN lo leaves only the upper clamp, a NaN hi only the lower one, two NaNs
+ *             none. Nothing else is read or written differently. */
+enum { DPPO_PPO_ADV_CLIP = 8 };
 
 /* ABI 9: the learnable DDIM eta's optimizer step (the original DPPO's EtaFixed trained by its own
  * AdamW every eta_update_interval minibatches, train_ppo_diffusion_agent.py:28-45, 358-359 — the
@@ -605,6 +621,41 @@ DPPO_API int dppo_ppo_adv_stats(const float* advantages, int64_t total, int K_ft
  * dppo_ppo_adv_stats (row_index = NULL); a multi-GPU caller all-reduces the whole array once. */
 DPPO_API int dppo_ppo_adv_stats_all(const float* advantages, int64_t total, int K_ft, uint64_t perm_seed, int epoch0,
                            int n_epochs, int64_t rows_full, int n_batch, double* adv_stats, void* stream);
+/* The advantage quantiles of every minibatch of an update phase (DPPO_PPO_ADV_CLIP; an addition within ABI 15):
+ * segments indexed as dppo_ppo_adv_stats_all indexes minibatches, each the multiset {advantages[row / K_ft]} over
+ * the rows of its window (n of them). For q in {q_lo, q_hi}: pos = q (n - 1), k = floor(pos),
+ *   Q(q) = v_k + (pos - k) (v_min(k+1, n-1) - v_k)
+ * over the sorted values v, in fp64 (numpy.quantile's default linear method on the values as float64). The order
+ * statistics are exact: an 8-bit-per-pass radix select over order-preserving 32-bit keys of the fp32 values, four
+ * targets per segment. bounds receives fp64 [n_epochs * n_batch][2] = {Q(q_lo), Q(q_hi)}; a window past `total`
+ * (an empty segment) gets (-inf, +inf). NaN advantages are out of scope. 4 count + 4 pick launches and one
+ * memset on `stream`, nothing waits on the host. workspace: dppo_ppo_adv_quantiles_workspace_bytes(n_epochs,
+ * n_batch) bytes, 16-B aligned, any contents.
+ * Refused (DPPO_EINVAL, nothing enqueued, outputs untouched): a null pointer, total / K_ft / rows_full / n_batch /
+ * n_epochs <= 0, n_epochs > 64, total >= 2^32, more than 65535 segments, a segment of 2^31 rows or more (the
+ * bins are int32; a data-parallel caller keeps a segment's rows SUMMED OVER RANKS below 2^31 itself), and
+ * anything but 0 <= q_lo < q_hi <= 1 (NaN included). */
+DPPO_API size_t dppo_ppo_adv_quantiles_workspace_bytes(int n_epochs, int n_batch);
+DPPO_API int dppo_ppo_adv_quantiles_all(const float* advantages, int64_t total, int K_ft, uint64_t perm_seed, int epoch0,
+                               int n_epochs, int64_t rows_full, int n_batch, double q_lo, double q_hi,
+                               void* workspace, double* bounds, void* stream);
+/* The same pass by pass (pass = 0..3, most significant byte first), which dppo_ppo_adv_quantiles_all loops over, so
+ * a data-parallel caller can SUM-all-reduce `counts` between a pass's count and its pick: every rank then picks
+ * the same bins, and the bounds are those of the union of the ranks' rows.
+ *   counts int32 [n_seg][4][256] (n_seg = n_epochs * n_batch; 16-B aligned): zero before the pass-0 count; each
+ *     pick leaves it zero again. state int64 [n_seg][9]: written by the pass-0 pick, any contents before.
+ *   count adds this rank's rows into counts (reads state from pass 1 on).
+ *   pick advances state; n_global int64 [n_seg] is each segment's row count over all ranks, or NULL to take it
+ *     from the pass-0 counts themselves (their sum per target, which after the all-reduce is the same number);
+ *     pass 3 also writes bounds (may be NULL in passes 0..2).
+ * DPPO_ADV_QUANTILES_BLOCK threads bin a chunk; a segment is cut into at most DPPO_ADV_QUANTILES_MAX_CHUNKS
+ * workgroups, which stride over it (a segment longer than BLOCK * MAX_CHUNKS rows takes a second trip). */
+enum { DPPO_ADV_QUANTILES_BLOCK = 256, DPPO_ADV_QUANTILES_MAX_CHUNKS = 16 };
+DPPO_API int dppo_ppo_adv_quantiles_count(const float* advantages, int64_t total, int K_ft, uint64_t perm_seed,
+                                 int epoch0, int n_epochs, int64_t rows_full, int n_batch, int pass,
+                                 const int64_t* state, int* counts, void* stream);
+DPPO_API int dppo_ppo_adv_quantiles_pick(int n_epochs, int n_batch, double q_lo, double q_hi, int pass,
+                                const int64_t* n_global, int64_t* state, int* counts, double* bounds, void* stream);
 DPPO_API int dppo_ppo_minibatch(const dppo_dims* d, int precision, const dppo_ppo_hparams* hp,
                        const void* packed_ft, const void* packed_critic, const float* actor_params,
                        const float* sched, const float* obs, const float* chains, const float* lp_old_mean,

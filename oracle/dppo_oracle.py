@@ -8,6 +8,20 @@ library.
 Every function cites the reference file:line (relative to the reference repo root) whose
 semantics it restates. Weights use the Keras layout (kernel [in, out], bias [out]).
 
+The model variant is an argument, never a patch of this module:
+  * the networks: Model(act, head, critic_head, critic_layernorm), frozen; Model.from_dims(dims) reads the keys
+    ops.ModelDims takes. sample, bc_loss, get_logprobs, c_loss, p_losses (and oracle/iteration.py) take it as
+    model= and pass it to the one actor pair (diffusion_mlp_forward / _backward: five activations in ACT, the
+    residual or the plain head) and the one critic pair (critic_forward / critic_backward: residual or plain,
+    with or without layer normalisation), which dispatch on it. No function looks at cache keys or parameter
+    names to learn the variant;
+  * the diffusion parameterisation travels with the schedule dict, as in the product: with_param(sched,
+    denoised_clip, predict_epsilon) sets sched["denoised_clip"] (None = inf) and sched["predict_epsilon"];
+    p_mean_var, c_loss's learnable-eta term and p_losses' target read them (absent: 1.0 and True);
+  * the advantage quantile clip: c_loss(adv_clip_quantiles=, adv_clip_bounds=).
+Every default is the flagship configuration (ReLU residual actor, residual Mish critic without layer norm,
+clip 1.0, epsilon prediction, no advantage clip).
+
 Parity pinning:
   * reward scaling is pinned bit-for-bit against the reference's own util/reward_scaling.py
     (importable in the build container) through tests/golden/reward_scaling.npz;
@@ -16,6 +30,7 @@ Parity pinning:
     AdamW) is "parity unpinned" at the TF boundary: no reference test or fixture exists and
     TF is not installable, so the restatement follows the cited formulas.
 """
+import dataclasses
 import math
 
 import numpy as np
@@ -153,7 +168,90 @@ def mish_grad(x):
     return th + x * (1.0 - th * th) * sig
 
 
-ACT = {"ReLU": (relu, relu_grad), "Mish": (mish, mish_grad)}
+# ELU / GELU / Softplus, Keras' float64 definitions:
+#     ELU       keras.activations.elu, alpha = 1:          x > 0 ? x : expm1(x);        x > 0 ? 1 : exp(x)
+#     GELU      keras.activations.gelu, approximate=False: x Phi(x);                    Phi(x) + x phi(x)
+#     Softplus  tf.math.softplus:                          max(x, 0) + log1p(e^-|x|);   sigmoid(x)
+# Phi(x) = (1 + erf(x / sqrt 2)) / 2 is evaluated as erfc(-x / sqrt 2) / 2, the same function without the
+# cancellation of 1 + erf in the negative tail. No exponential takes a positive argument, so none overflows.
+try:
+    from scipy.special import erfc as _erfc
+except ImportError:   # math.erfc, element by element
+    _erfc = np.vectorize(math.erfc, otypes=[np.float64])
+
+_SQRT2, _SQRT2PI = math.sqrt(2.0), math.sqrt(2.0 * math.pi)
+
+
+def _f64(x):
+    return np.asarray(x, np.float64)
+
+
+def elu(x):
+    x = _f64(x)
+    return np.where(x > 0, x, np.expm1(np.minimum(x, 0.0)))
+
+
+def elu_grad(x):
+    x = _f64(x)
+    return np.where(x > 0, 1.0, np.exp(np.minimum(x, 0.0)))
+
+
+def _Phi(x):
+    return 0.5 * _erfc(-x / _SQRT2)
+
+
+def gelu(x):
+    x = _f64(x)
+    return x * _Phi(x)
+
+
+def gelu_grad(x):
+    x = _f64(x)
+    xc = np.clip(x, -40.0, 40.0)            # e^-800 is 0 in float64, and x^2 cannot overflow
+    return _Phi(x) + x * np.exp(-0.5 * xc * xc) / _SQRT2PI
+
+
+def softplus_act(x):
+    x = _f64(x)
+    return np.maximum(x, 0.0) + np.log1p(np.exp(-np.abs(x)))
+
+
+def softplus_grad(x):
+    x = _f64(x)
+    u = np.exp(-np.abs(x))
+    return np.where(x >= 0, 1.0, u) / (1.0 + u)
+
+
+ACT = {"ReLU": (relu, relu_grad), "Mish": (mish, mish_grad), "ELU": (elu, elu_grad), "GELU": (gelu, gelu_grad),
+       "Softplus": (softplus_act, softplus_grad)}
+
+
+# ----------------------------------------------------------------------------------------------
+# which networks: the variant every composed function below takes as `model=`
+# ----------------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class Model:
+    """act: the actor block's activation (a key of ACT; the time MLP and the critic are Mish in every variant).
+    head / critic_head: "residual" (ResidualMLP) or "plain" (MLP). critic_layernorm: CriticObs(use_layernorm)."""
+    act: str = "ReLU"
+    head: str = "residual"
+    critic_head: str = "residual"
+    critic_layernorm: bool = False
+
+    def __post_init__(self):
+        assert self.act in ACT and self.head in ("residual", "plain") and self.critic_head in ("residual", "plain"), self
+
+    @classmethod
+    def from_dims(cls, dims):
+        """From a dims dict with the keys ops.ModelDims takes (or such a dataclass); a missing key is the default."""
+        if dataclasses.is_dataclass(dims):
+            dims = dataclasses.asdict(dims)
+        return cls(act=dims.get("activation", "ReLU"), head=dims.get("head", "residual"),
+                   critic_head=dims.get("critic_head", "residual"),
+                   critic_layernorm=bool(dims.get("critic_layernorm", False)))
+
+
+DEFAULT_MODEL = Model()
 
 
 def dense(x, w, b):
@@ -275,6 +373,47 @@ def residual_mlp_backward(p, cache, dy, act, prefix):
 
 
 # ----------------------------------------------------------------------------------------------
+# the plain actor head: MLP([in, h, h, out]) (model/common/mlp.py:35-92, DiffusionMLP residual_style=False with
+# the default mlp_dims = [h, h])
+#   h1 = in(x);  u1 = act(h1);  h2 = l1(u1);  a = act(h2);  eps = W_out^T a + b_out
+# GEMM operands go through `rnd` (x, the weights, u1, and u2 = a, rounded as the l1 output is in the residual
+# form); biases and accumulators are not rounded; dx comes from the unrounded in_w. The parameter dict may carry
+# l2_w / l2_b: a plain head ignores them, and the backward returns no gradient for them.
+# ----------------------------------------------------------------------------------------------
+def plain_mlp_forward(p, x, act, rnd=None):
+    a, _ = ACT[act]
+    R = rnd or _ident
+    xr = R(x)
+    h1 = xr @ R(p["in_w"]) + np.asarray(p["in_b"], np.float64)
+    u1 = R(a(h1))
+    h2 = u1 @ R(p["l1_w"]) + np.asarray(p["l1_b"], np.float64)
+    u2 = R(a(h2))
+    y = u2 @ R(p["out_w"]) + np.asarray(p["out_b"], np.float64)
+    return y, dict(x=xr, h1=h1, u1=u1, h2=h2, u2=u2, R=R)
+
+
+def plain_mlp_backward(p, cache, dy, act):
+    """(grads, dx): residual_mlp_backward with the l2 layer and the skip removed."""
+    _, ag = ACT[act]
+    R = cache.get("R", _ident)
+    Rg = getattr(R, "grad_round", R)
+    g = {}
+    dyr = Rg(dy)
+    g["out_w"] = cache["u2"].T @ dyr
+    g["out_b"] = dyr.sum(0)
+    du2 = dyr @ R(p["out_w"]).T
+    dh2 = Rg(du2 * ag(cache["h2"]))
+    g["l1_w"] = cache["u1"].T @ dh2
+    g["l1_b"] = dh2.sum(0)
+    du1 = dh2 @ R(p["l1_w"]).T
+    dh1 = Rg(du1 * ag(cache["h1"]))
+    g["in_w"] = cache["x"].T @ dh1
+    g["in_b"] = dh1.sum(0)
+    dx = dh1 @ np.asarray(p["in_w"], np.float64).T
+    return g, dx
+
+
+# ----------------------------------------------------------------------------------------------
 # a4: DiffusionMLP (model/diffusion/mlp_diffusion.py:38-90); time MLP Dense(16->32, mish)->Dense(32->16)
 # ----------------------------------------------------------------------------------------------
 def time_mlp_forward(p, t, time_dim=16):
@@ -294,20 +433,28 @@ def time_mlp_backward(p, cache, dtemb):
     return g
 
 
-def diffusion_mlp_forward(p, x, t, state, act="ReLU", rnd=None, round_h3=True):
-    """x [B,Ta,Da], t [B] int, state [B,To,Do] -> eps [B,Ta,Da]; cond concat [x, t_emb, state] (:86)."""
+def diffusion_mlp_forward(p, x, t, state, model=DEFAULT_MODEL, rnd=None, round_h3=True):
+    """x [B,Ta,Da], t [B] int, state [B,To,Do] -> eps [B,Ta,Da]; cond concat [x, t_emb, state] (:86).
+    model.head picks the ResidualMLP or the plain MLP (round_h3 has no meaning without h3), model.act the
+    activation of either."""
     B = x.shape[0]
     temb, tcache = time_mlp_forward(p, t, np.shape(p["time_w1"])[0])   # time_dim: time_w1 is [TD, 2 TD]
     inp = np.concatenate([x.reshape(B, -1), temb, state.reshape(B, -1)], axis=-1).astype(np.float64)
-    y, cache = residual_mlp_forward(p, inp, act, "", rnd, round_h3)
+    if model.head == "plain":
+        y, cache = plain_mlp_forward(p, inp, model.act, rnd)
+    else:
+        y, cache = residual_mlp_forward(p, inp, model.act, "", rnd, round_h3)
     cache["time"] = tcache
     cache["t"] = np.asarray(t)
     return y.reshape(x.shape), cache
 
 
-def diffusion_mlp_backward(p, cache, deps, xdim, act="ReLU"):
+def diffusion_mlp_backward(p, cache, deps, xdim, model=DEFAULT_MODEL):
     B = deps.shape[0]
-    g, dinp = residual_mlp_backward(p, cache, deps.reshape(B, -1), act, "")
+    if model.head == "plain":
+        g, dinp = plain_mlp_backward(p, cache, deps.reshape(B, -1), model.act)
+    else:
+        g, dinp = residual_mlp_backward(p, cache, deps.reshape(B, -1), model.act, "")
     tdim = p["time_w2"].shape[1]
     dtemb = dinp[:, xdim:xdim + tdim]
     g.update(time_mlp_backward(p, cache["time"], dtemb))
@@ -315,39 +462,207 @@ def diffusion_mlp_backward(p, cache, deps, xdim, act="ReLU"):
 
 
 # ----------------------------------------------------------------------------------------------
-# a6: CriticObs (model/common/critic.py:15-54): ResidualMLP([Do,256,256,256,1], Mish)
+# a6: CriticObs (model/common/critic.py:15-54), Mish in every variant:
+#   residual (the default)  ResidualMLP([Do,256,256,256,1], Mish)
+#   plain                   CriticObs(residual_style=False) (critic.py:15-38): MLP([Do To, h, h, h, 1], Mish)
+#                           (model/common/mlp.py:35-92)
+#       h1 = in(s);  u1 = mish(h1);  h2 = l1(u1);  u2 = mish(h2);  h3 = l2(u2);  u3 = mish(h3);  V = out(u3)
+#     GEMM operands go through `rnd` (s, the weights, u1, u2, u3); the gradient images dV, dh3, dh2, dh1 through
+#     `rnd.grad_round` (fp16: the row-tied scale); biases and accumulators are not rounded. The parameter dict is
+#     the residual critic's (the four Dense layers have the same shapes in both forms).
+#   layer-normed            CriticObs(use_layernorm=True) (critic.py:15-38):
+#     plain     MLP (mlp.py:62-78): per hidden layer Dense -> LayerNormalization() -> Mish, Keras' default
+#               epsilon 1e-3, no norm on the output layer:
+#                   y_k = LN_k(h_k), u_k = mish(y_k), k = 1..3;  V = out(u3)
+#     residual  ResidualMLP (mlp.py:163-206): the block's pre-activation norms, epsilon 1e-6, the skip
+#               un-normalised:
+#                   h1 = in(s); u1 = mish(LN_1(h1)); h2 = l1(u1); u2 = mish(LN_2(h2)); h3 = l2(u2) + h1; V = out(h3)
+#     LayerNormalization is Keras': over the last axis, population variance,
+#     y = gamma (h - mean) / sqrt(var + eps) + beta. GEMM operands go through `rnd` (s, the weights, u_k, the
+#     residual h3); the gradient images dV, dh_k through `rnd.grad_round`; biases, accumulators, the norm's
+#     statistics, y_k, dy_k, dgamma and dbeta are not rounded. The parameter dict is the critic's eight tensors
+#     plus ln{k}_g / ln{k}_b (k = 1..3 plain, 1..2 residual).
 # ----------------------------------------------------------------------------------------------
-def critic_forward(pc, state, act="Mish", rnd=None):
+LN_EPS = {"plain": 1e-3, "residual": 1e-6}
+
+
+def plain_critic_forward(pc, state, act="Mish", rnd=None):
+    """(V [B, 1], cache)."""
+    a, _ = ACT[act]
+    R = rnd or _ident
     B = state.shape[0]
-    v, cache = residual_mlp_forward(pc, state.reshape(B, -1).astype(np.float64), act, "", rnd)
+    xr = R(state.reshape(B, -1).astype(np.float64))
+    h1 = xr @ R(pc["in_w"]) + np.asarray(pc["in_b"], np.float64)
+    u1 = R(a(h1))
+    h2 = u1 @ R(pc["l1_w"]) + np.asarray(pc["l1_b"], np.float64)
+    u2 = R(a(h2))
+    h3 = u2 @ R(pc["l2_w"]) + np.asarray(pc["l2_b"], np.float64)
+    u3 = R(a(h3))
+    v = u3 @ R(pc["out_w"]) + np.asarray(pc["out_b"], np.float64)
+    return v, dict(x=xr, h1=h1, u1=u1, h2=h2, u2=u2, h3=h3, u3=u3, R=R)
+
+
+def plain_critic_backward(pc, cache, dy, act="Mish"):
+    """(grads, dx) of a plain_critic_forward cache."""
+    _, ag = ACT[act]
+    R = cache.get("R", _ident)
+    Rg = getattr(R, "grad_round", R)
+    g = {}
+    dyr = Rg(dy)
+    g["out_w"] = cache["u3"].T @ dyr
+    g["out_b"] = dyr.sum(0)
+    du3 = dyr @ R(pc["out_w"]).T
+    dh3 = Rg(du3 * ag(cache["h3"]))
+    g["l2_w"] = cache["u2"].T @ dh3
+    g["l2_b"] = dh3.sum(0)
+    du2 = dh3 @ R(pc["l2_w"]).T
+    dh2 = Rg(du2 * ag(cache["h2"]))
+    g["l1_w"] = cache["u1"].T @ dh2
+    g["l1_b"] = dh2.sum(0)
+    du1 = dh2 @ R(pc["l1_w"]).T
+    dh1 = Rg(du1 * ag(cache["h1"]))
+    g["in_w"] = cache["x"].T @ dh1
+    g["in_b"] = dh1.sum(0)
+    dx = dh1 @ np.asarray(pc["in_w"], np.float64).T
+    return g, dx
+
+
+def layer_norm(h, gamma, beta, eps):
+    mean = h.mean(-1, keepdims=True)
+    var = ((h - mean) ** 2).mean(-1, keepdims=True)
+    rstd = 1.0 / np.sqrt(var + eps)
+    xh = (h - mean) * rstd
+    return np.asarray(gamma, np.float64) * xh + np.asarray(beta, np.float64), xh, rstd, var
+
+
+def layer_norm_backward(dy, xh, rstd, gamma):
+    """(dh, dgamma, dbeta) of y = gamma x_hat + beta."""
+    g = dy * np.asarray(gamma, np.float64)
+    dh = rstd * (g - g.mean(-1, keepdims=True) - xh * (g * xh).mean(-1, keepdims=True))
+    return dh, (dy * xh).sum(0), dy.sum(0)
+
+
+def ln_critic_forward(pc, state, head, act="Mish", rnd=None, eps=None):
+    """(V [B, 1], cache). eps: the norm's epsilon (default: the head's, LN_EPS)."""
+    a, _ = ACT[act]
+    R = rnd or _ident
+    eps = LN_EPS[head] if eps is None else eps
+    B = state.shape[0]
+    c = dict(R=R, var=[])
+    c["x"] = R(state.reshape(B, -1).astype(np.float64))
+    prev, names = c["x"], ("in", "l1", "l2")
+    for k in range(1, (3 if head == "plain" else 2) + 1):
+        h = prev @ R(pc[names[k - 1] + "_w"]) + np.asarray(pc[names[k - 1] + "_b"], np.float64)
+        y, xh, rstd, var = layer_norm(h, pc[f"ln{k}_g"], pc[f"ln{k}_b"], eps)
+        prev = R(a(y))
+        c.update({f"h{k}": h, f"y{k}": y, f"xh{k}": xh, f"rstd{k}": rstd, f"u{k}": prev})
+        c["var"].append(var)
+    if head == "residual":
+        h3 = prev @ R(pc["l2_w"]) + np.asarray(pc["l2_b"], np.float64) + c["h1"]
+        prev = c["h3"] = R(h3)
+    v = prev @ R(pc["out_w"]) + np.asarray(pc["out_b"], np.float64)
+    return v, c
+
+
+def ln_critic_backward(pc, cache, dy, head, act="Mish"):
+    """(grads, dx) of an ln_critic_forward cache of the same head."""
+    _, ag = ACT[act]
+    R = cache.get("R", _ident)
+    Rg = getattr(R, "grad_round", R)
+    g = {}
+    dyr = Rg(dy)
+    wo = R(pc["out_w"])
+    g["out_w"] = (cache["u3"] if head == "plain" else cache["h3"]).T @ dyr
+    g["out_b"] = dyr.sum(0)
+    dlast = dyr @ wo.T                                     # plain: du3; residual: dh3
+
+    def site(k, du):
+        dh, g[f"ln{k}_g"], g[f"ln{k}_b"] = layer_norm_backward(du * ag(cache[f"y{k}"]), cache[f"xh{k}"], cache[f"rstd{k}"],
+                                                               pc[f"ln{k}_g"])
+        return dh
+
+    if head == "plain":
+        dh3 = Rg(site(3, dlast))
+        g["l2_w"] = cache["u2"].T @ dh3
+        g["l2_b"] = dh3.sum(0)
+        skip = 0.0
+    else:
+        dh3 = Rg(dlast)
+        g["l2_w"] = (cache["u2"].T @ dyr) @ wo.T            # the factored form (residual_mlp_backward)
+        g["l2_b"] = g["out_b"] @ wo.T
+        skip = dh3
+    dh2 = Rg(site(2, dh3 @ R(pc["l2_w"]).T))
+    g["l1_w"] = cache["u1"].T @ dh2
+    g["l1_b"] = dh2.sum(0)
+    dh1 = Rg(skip + site(1, dh2 @ R(pc["l1_w"]).T))
+    g["in_w"] = cache["x"].T @ dh1
+    g["in_b"] = dh1.sum(0)
+    return g, dh1 @ np.asarray(pc["in_w"], np.float64).T
+
+
+def critic_forward(pc, state, model=DEFAULT_MODEL, rnd=None, ln_eps=None):
+    """(V [B, 1], cache) of the critic model.critic_head / model.critic_layernorm describe. ln_eps: the norm's
+    epsilon where there is one (default: the head's, LN_EPS)."""
+    if model.critic_layernorm:
+        return ln_critic_forward(pc, state, model.critic_head, "Mish", rnd, ln_eps)
+    if model.critic_head == "plain":
+        return plain_critic_forward(pc, state, "Mish", rnd)
+    B = state.shape[0]
+    v, cache = residual_mlp_forward(pc, state.reshape(B, -1).astype(np.float64), "Mish", "", rnd)
     return v, cache
+
+
+def critic_backward(pc, cache, dv, model=DEFAULT_MODEL):
+    """(grads, dstate) of a critic_forward cache of the same model; dv [B, 1]."""
+    if model.critic_layernorm:
+        return ln_critic_backward(pc, cache, dv, model.critic_head, "Mish")
+    if model.critic_head == "plain":
+        return plain_critic_backward(pc, cache, dv, "Mish")
+    return residual_mlp_backward(pc, cache, dv, "Mish", "")
 
 
 # ----------------------------------------------------------------------------------------------
 # a8: p_mean_var, DDPM branch (model/diffusion/diffusion_vpg.py:152-245)
 # ----------------------------------------------------------------------------------------------
-def p_mean_var(sched, eps, x, t, denoised_clip=1.0):
+def with_param(sched, denoised_clip=1.0, predict_epsilon=True):
+    """A copy of the schedule carrying the diffusion parameterisation, as the product's schedule does (DESIGN
+    §4b'): sched["denoised_clip"] (denoised_clip_value; None = no clip = inf) and sched["predict_epsilon"]. A
+    schedule without the keys means 1.0 and True."""
+    return dict(sched, denoised_clip=float("inf") if denoised_clip is None else float(denoised_clip),
+                predict_epsilon=bool(predict_epsilon))
+
+
+def p_mean_var(sched, eps, x, t):
+    """eps: the network's output, the noise or (sched["predict_epsilon"] False, model/diffusion/diffusion.py:
+    117-134) x_recon itself. The cache's deps_dxr is d eps / d x_recon's cotangent: -c2, or +1."""
     t = np.asarray(t)
+    denoised_clip = sched.get("denoised_clip", 1.0)
     sh = (-1,) + (1,) * (x.ndim - 1)
     c1 = sched["sqrt_recip_alphas_cumprod"].astype(np.float64)[t].reshape(sh)
     c2 = sched["sqrt_recipm1_alphas_cumprod"].astype(np.float64)[t].reshape(sh)
-    xr = c1 * x - c2 * eps                                       # :198-201
+    if sched.get("predict_epsilon", True):
+        xr = c1 * x - c2 * eps                                   # :198-201
+        deps_dxr = -c2
+    else:
+        xr = np.asarray(eps, np.float64)
+        deps_dxr = 1.0
     unclipped = np.abs(xr) <= denoised_clip
     xr = np.clip(xr, -denoised_clip, denoised_clip)              # :204-206
     m1 = sched["ddpm_mu_coef1"].astype(np.float64)[t].reshape(sh)
     m2 = sched["ddpm_mu_coef2"].astype(np.float64)[t].reshape(sh)
     mu = m1 * xr + m2 * x                                        # :239-242
     logvar = sched["ddpm_logvar_clipped"].astype(np.float64)[t].reshape(sh)
-    return mu, logvar, dict(m1=m1, c1=c1, c2=c2, unclipped=unclipped)
+    return mu, logvar, dict(m1=m1, c1=c1, c2=c2, unclipped=unclipped, x0=xr, deps_dxr=deps_dxr)
 
 
 # ----------------------------------------------------------------------------------------------
 # a9: sampler VPGDiffusion.call (diffusion_vpg.py:250-339), DDPM, with injected noise
 # ----------------------------------------------------------------------------------------------
 def sample(p_base, p_ft, sched, state, x_T, z, ft_steps, deterministic=False, min_std=0.1,
-           randn_clip=3.0, final_clip=None, rnd=None, round_h3=True):
+           randn_clip=3.0, final_clip=None, rnd=None, round_h3=True, model=DEFAULT_MODEL, caches=None):
     """state [E,To,Do]; x_T [E,Ta,Da]; z [K,E,Ta,Da] raw N(0,1) draws for loop index i (t=K-1-i).
-    Returns (trajectories [E,Ta,Da], chains [E,K'+1,Ta,Da]). round_h3: see residual_mlp_forward."""
+    Returns (trajectories [E,Ta,Da], chains [E,K'+1,Ta,Da]). round_h3: see residual_mlp_forward.
+    caches: a list of the caller's that receives the cache of every actor forward, in order."""
     K = z.shape[0]
     x = np.asarray(x_T, np.float64)
     chain = []
@@ -357,7 +672,9 @@ def sample(p_base, p_ft, sched, state, x_T, z, ft_steps, deterministic=False, mi
         t = K - 1 - i
         tb = np.full(x.shape[0], t)
         params = p_ft if t < ft_steps else p_base                # :161-180
-        eps, _ = diffusion_mlp_forward(params, x, tb * _tstride(sched), state, rnd=rnd, round_h3=round_h3)
+        eps, cache = diffusion_mlp_forward(params, x, tb * _tstride(sched), state, model, rnd=rnd, round_h3=round_h3)
+        if caches is not None:
+            caches.append(cache)
         mu, logvar, _ = p_mean_var(sched, eps, x, tb)
         std = np.exp(0.5 * logvar)                               # :301
         ez = sched["eval_zero"][t] if "eval_zero" in sched else t == 0
@@ -377,13 +694,13 @@ def sample(p_base, p_ft, sched, state, x_T, z, ft_steps, deterministic=False, mi
 
 
 def bc_loss(p_base, p_ft, sched, state, x_T, z, ft_steps, min_std=0.1, randn_clip=3.0, min_logprob_std=0.1,
-            rnd=None):
+            rnd=None, model=DEFAULT_MODEL):
     """c_loss's behaviour-cloning term (diffusion_ppo.py:63-71): chains of the base policy for every
     denoising step (use_base_policy=True, diffusion_vpg.py:175-176), their log-probs under actor_ft,
     clipped to [-5, 2]; -mean over every element. Reported only (agent :340-342)."""
     _, chains = sample(p_base, p_base, sched, state, x_T, z, ft_steps, min_std=min_std, randn_clip=randn_clip,
-                       rnd=rnd, round_h3=False)
-    lp = get_logprobs(p_ft, sched, state, chains, ft_steps, min_logprob_std=min_logprob_std, rnd=rnd)
+                       rnd=rnd, round_h3=False, model=model)
+    lp = get_logprobs(p_ft, sched, state, chains, ft_steps, min_logprob_std=min_logprob_std, rnd=rnd, model=model)
     return -float(np.clip(lp, -5.0, 2.0).mean())
 
 
@@ -395,18 +712,58 @@ def gaussian_logprob(x, mu, std):
 # ----------------------------------------------------------------------------------------------
 # a10: get_logprobs (diffusion_vpg.py:343-425)
 # ----------------------------------------------------------------------------------------------
-def get_logprobs(p_ft, sched, state, chains, ft_steps, min_logprob_std=0.1, rnd=None, round_h3=False):
+def get_logprobs(p_ft, sched, state, chains, ft_steps, min_logprob_std=0.1, rnd=None, round_h3=False,
+                 model=DEFAULT_MODEL, caches=None):
     """state [n,To,Do], chains [n,K'+1,Ta,Da] -> logprob [n*K', Ta, Da]; row = n*K' + j, t = K'-1-j.
-    round_h3=False: the folded row tile's rounding points (residual_mlp_forward)."""
+    round_h3=False: the folded row tile's rounding points (residual_mlp_forward). caches: see sample."""
     n = chains.shape[0]
     cond = np.repeat(state, ft_steps, axis=0)                    # :374-379 (sample-major tile)
     t_all = np.tile(np.arange(ft_steps - 1, -1, -1), n)          # :385-390
     prev = chains[:, :-1].reshape(-1, *chains.shape[2:])          # :402-407
     nxt = chains[:, 1:].reshape(-1, *chains.shape[2:])
-    eps, _ = diffusion_mlp_forward(p_ft, prev, t_all * _tstride(sched), cond, rnd=rnd, round_h3=round_h3)
+    eps, cache = diffusion_mlp_forward(p_ft, prev, t_all * _tstride(sched), cond, model, rnd=rnd, round_h3=round_h3)
+    if caches is not None:
+        caches.append(cache)
     mu, logvar, _ = p_mean_var(sched, eps, prev, t_all)
     std = np.clip(np.exp(0.5 * logvar), min_logprob_std, 1e6)    # :417-418
     return gaussian_logprob(nxt, mu, std)
+
+
+# ----------------------------------------------------------------------------------------------
+# the advantage quantile clip. `quantile` is the definition, in float64: over the sorted values
+# v_0 <= ... <= v_{n-1},
+#     pos = q (n - 1),  k = floor(pos),  Q(q) = v_k + (pos - k) (v_min(k+1, n-1) - v_k),
+# numpy.quantile's default linear method (torch.quantile's), the DPPO algorithm's live lines. The reference
+# comments them out (model/diffusion/diffusion_ppo.py:77-80) and would have used tfp.stats.percentile, whose
+# default is "nearest": parity is unpinned.
+# ----------------------------------------------------------------------------------------------
+def order_stats(values, q):
+    """(n, k, k1, v_k, v_k1) of the definition; values as float64."""
+    v = np.sort(np.asarray(values, np.float64).reshape(-1))
+    n = v.size
+    pos = q * (n - 1)
+    k = int(np.floor(pos))
+    k1 = min(k + 1, n - 1)
+    return n, k, k1, v[k], v[k1]
+
+
+def quantile(values, q):
+    n, k, k1, vk, vk1 = order_stats(values, q)
+    pos = q * (n - 1)
+    return vk + (pos - k) * (vk1 - vk)
+
+
+def bounds(values, q_lo, q_hi):
+    """(Q(q_lo), Q(q_hi)); an empty set clips nothing."""
+    if np.asarray(values).size == 0:
+        return -float("inf"), float("inf")
+    return quantile(values, q_lo), quantile(values, q_hi)
+
+
+def clip_adv(adv, q_lo, q_hi, lo_hi=None):
+    adv = np.asarray(adv, np.float64)
+    lo, hi = bounds(adv, q_lo, q_hi) if lo_hi is None else lo_hi
+    return np.clip(adv, lo, hi)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -417,8 +774,16 @@ def c_loss(p_ft, pc, sched, obs, chains_prev, chains_next, denoising_inds, retur
            advantages, oldlogprobs, ft_steps, gamma_denoising=0.99, clip_ploss_coef=0.01,
            clip_ploss_coef_base=0.01, clip_ploss_coef_rate=3.0, clip_vloss_coef=None,
            norm_adv=True, min_logprob_std=0.1, vf_coef=0.5, with_grad=True, reward_horizon=4, rnd=None,
-           adv_mean_std=None, denom=None, critic_dedup=None, eta_grad=False, round_h3=False):
+           adv_mean_std=None, denom=None, critic_dedup=None, eta_grad=False, round_h3=False,
+           model=DEFAULT_MODEL, adv_clip_quantiles=None, adv_clip_bounds=None, caches=None):
     """Returns (metrics dict, grads_actor dict, grads_critic dict).
+
+    adv_clip_quantiles = (q_lo, q_hi): PPODiffusion's clip_advantage_lower_quantile / _upper_quantile. The raw
+    advantages of the minibatch are clamped to [Q(q_lo), Q(q_hi)] of themselves (quantile), and the normalisation
+    keeps the mean and std of the UNCLIPPED minibatch unless adv_mean_std was given; then the denoising discount.
+    Clamping before the affine normalisation is the algorithm's normalise-then-clamp in real arithmetic, and works
+    the same with norm_adv off. adv_clip_bounds = (lo, hi) hands in bounds computed elsewhere (a data-parallel
+    shard's come from the union of the ranks' rows). caches: see sample.
 
     Data-parallel restatement hooks: adv_mean_std overrides the minibatch
     advantage mean/std (the global ones), denom overrides the row count the means divide by
@@ -432,7 +797,9 @@ def c_loss(p_ft, pc, sched, obs, chains_prev, chains_next, denoising_inds, retur
     if rnd is round_fp16:                    # the fp16 gradient images use the row-tied scale
         rnd = round_fp16_rows(b if denom is None else denom)
     t = ft_steps - 1 - j                                          # :456-458
-    eps, acache = diffusion_mlp_forward(p_ft, chains_prev, t * _tstride(sched), obs, rnd=rnd, round_h3=round_h3)
+    eps, acache = diffusion_mlp_forward(p_ft, chains_prev, t * _tstride(sched), obs, model, rnd=rnd, round_h3=round_h3)
+    if caches is not None:
+        caches.append(acache)
     mu, logvar, pm = p_mean_var(sched, eps, chains_prev, t)
     std = np.clip(np.exp(0.5 * logvar), min_logprob_std, 1e6)
     lp_el = gaussian_logprob(chains_next, mu, std)
@@ -445,6 +812,10 @@ def c_loss(p_ft, pc, sched, obs, chains_prev, chains_next, denoising_inds, retur
     else:
         oldlp = np.asarray(oldlogprobs, np.float64)
     adv = np.asarray(advantages, np.float64)
+    if adv_clip_quantiles is not None or adv_clip_bounds is not None:
+        if norm_adv and adv_mean_std is None:
+            adv_mean_std = (adv.mean(), adv.std())                # of the unclipped minibatch
+        adv = clip_adv(adv, *(adv_clip_quantiles or (None, None)), adv_clip_bounds)
     if norm_adv:                                                  # :74-75 (population std)
         am, asd = (adv.mean(), adv.std()) if adv_mean_std is None else adv_mean_std
         adv = (adv - am) / (asd + 1e-8)
@@ -474,7 +845,7 @@ def c_loss(p_ft, pc, sched, obs, chains_prev, chains_next, denoising_inds, retur
         obs, returns = obs[first], np.asarray(returns, np.float64)[first]
         if oldvalues is not None:
             oldvalues = np.asarray(oldvalues, np.float64)[first]
-    v, ccache = critic_forward(pc, obs, rnd=rnd)
+    v, ccache = critic_forward(pc, obs, model, rnd=rnd)
     v = v[:, 0]                                                   # :109
     w_rows = cw if cw is not None else np.ones_like(v)
     if clip_vloss_coef is not None:                               # :110-116
@@ -503,9 +874,9 @@ def c_loss(p_ft, pc, sched, obs, chains_prev, chains_next, denoising_inds, retur
     dlp_el = dlp_el * in_clip
     dmu = dlp_el * (chains_next - mu) / std ** 2
     dxr = dmu * pm["m1"] * pm["unclipped"]
-    deps = -pm["c2"] * dxr
+    deps = pm["deps_dxr"] * dxr
     xdim = chains_prev.shape[1] * chains_prev.shape[2]
-    ga = diffusion_mlp_backward(p_ft, acache, deps, xdim)
+    ga = diffusion_mlp_backward(p_ft, acache, deps, xdim, model)
     if clip_vloss_coef is not None:
         # tf.maximum's gradient to its first argument on ties; tf.clip_by_value's passes inside [-c, c]
         d_old = v - oldvalues
@@ -515,7 +886,7 @@ def c_loss(p_ft, pc, sched, obs, chains_prev, chains_next, denoising_inds, retur
         dv = vf_coef * (v - returns) / D
     if cw is not None:
         dv = dv * cw
-    gc, _ = residual_mlp_backward(pc, ccache, dv[:, None], "Mish", "")
+    gc, _ = critic_backward(pc, ccache, dv[:, None], model)
     if eta_grad:
         # d loss / d eta (learnable DDIM eta, parity unpinned): mu = c2 x0 + c3 x moves through
         # d (dmu/deta = dd/deta * eps', eps' the noise recomputed from the clipped x0) and the
@@ -523,7 +894,7 @@ def c_loss(p_ft, pc, sched, obs, chains_prev, chains_next, denoising_inds, retur
         dd, dstd = ddim_eta_grad_terms(sched, t, sched["ddim_eta"], min_logprob_std)
         sh = (-1,) + (1,) * (chains_prev.ndim - 1)
         a = sched["ddim_alphas"].astype(np.float64)[t].reshape(sh)
-        x0 = np.clip(pm["c1"] * chains_prev - pm["c2"] * eps, -1.0, 1.0)
+        x0 = pm["x0"]                                             # clipped at the schedule's bound
         e2 = (chains_prev - np.sqrt(a) * x0) / np.sqrt(1.0 - a)
         r = chains_next - mu
         dlp_deta = r / std ** 2 * dd.reshape(sh) * e2 + (r ** 2 / std ** 3 - 1.0 / std) * dstd.reshape(sh)
@@ -532,7 +903,7 @@ def c_loss(p_ft, pc, sched, obs, chains_prev, chains_next, denoising_inds, retur
 
 
 # ----------------------------------------------------------------------------------------------
-# §8(f) row 3: pretraining loss (model/diffusion/diffusion.py:179-202, predict_epsilon = True)
+# §8(f) row 3: pretraining loss (model/diffusion/diffusion.py:179-202)
 # ----------------------------------------------------------------------------------------------
 def q_sample(sched, x_start, t, noise):
     """diffusion.py:196-202: sqrt(ac_t) x_0 + sqrt(1 - ac_t) noise, the buffers in fp32 (:62-65)."""
@@ -543,23 +914,26 @@ def q_sample(sched, x_start, t, noise):
     return sa.reshape(shape).astype(np.float64) * x_start + s1.reshape(shape).astype(np.float64) * noise
 
 
-def p_losses(p, sched, x_start, state, t, noise, with_grad=True, rnd=None, denom=None, round_h3=False):
-    """diffusion.py:186-194: loss = mean((network(q_sample(x_0, t, noise), t, cond) - noise)^2) and
-    its parameter gradient. x_start, noise [B,Ta,Da]; state [B,To,Do]; t [B] int (the draws of
+def p_losses(p, sched, x_start, state, t, noise, with_grad=True, rnd=None, denom=None, round_h3=False,
+             model=DEFAULT_MODEL, caches=None):
+    """diffusion.py:186-194: loss = mean((network(q_sample(x_0, t, noise), t, cond) - target)^2) and
+    its parameter gradient; target = noise, or x_start where sched["predict_epsilon"] is False. x_start, noise [B,Ta,Da]; state [B,To,Do]; t [B] int (the draws of
     :182 and :187 are inputs here). denom overrides the element count of the mean (data-parallel
     shards: summing per-shard gradients with the global count gives the full-batch one)."""
     xn = q_sample(sched, x_start, np.asarray(t), noise)
     if rnd is round_fp16:                    # the fp16 gradient images use the row-tied scale
         xd = x_start.shape[1] * x_start.shape[2]
         rnd = round_fp16_rows(x_start.shape[0] if denom is None else denom // xd)
-    eps, cache = diffusion_mlp_forward(p, xn, np.asarray(t), state, rnd=rnd, round_h3=round_h3)
-    e = eps - noise
+    eps, cache = diffusion_mlp_forward(p, xn, np.asarray(t), state, model, rnd=rnd, round_h3=round_h3)
+    if caches is not None:
+        caches.append(cache)
+    e = eps - (noise if sched.get("predict_epsilon", True) else x_start)
     n = e.size if denom is None else denom
     loss = float((e ** 2).sum() / n)
     if not with_grad:
         return loss, None
     deps = 2.0 * e / n
-    return loss, diffusion_mlp_backward(p, cache, deps, x_start.shape[1] * x_start.shape[2])
+    return loss, diffusion_mlp_backward(p, cache, deps, x_start.shape[1] * x_start.shape[2], model)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -102,7 +102,8 @@ class PPODiffusionLoopOracle:
     """TrainPPODiffusionAgent.run (agent :58-377) with PPODiffusion / VPGDiffusion on the oracle
     functions. actor_spec / critic_spec: [(name, shape)] of the flat [actor_ft | critic] layout
     (include/dppo.h); base / ft / critic: parameter dicts (f64). Noise, permutation and env seeds
-    are inputs (see the module docstring)."""
+    are inputs (see the module docstring). model: the networks' variant (O.Model); the clip bound and the
+    parameterisation travel with sched (O.with_param); adv_clip_quantiles: c_loss's."""
 
     def __init__(self, base, ft, critic, actor_spec, critic_spec, sched, env, *, seed, perm_seed,
                  n_steps, ft_steps, act_steps, horizon_steps, action_dim, val_freq, batch_size,
@@ -111,7 +112,8 @@ class PPODiffusionLoopOracle:
                  weight_decay=0.004, min_sampling_std=0.1, randn_clip=3.0, min_logprob_std=0.1,
                  gamma_denoising=0.99, clip_ploss_coef=0.01, clip_ploss_coef_base=0.01,
                  clip_ploss_coef_rate=3.0, vf_coef=0.5, success_threshold=3.0, env_offset=0,
-                 n_critic_warmup_itr=0, ft_denoising_steps_d=0, ft_denoising_steps_t=0):
+                 n_critic_warmup_itr=0, ft_denoising_steps_d=0, ft_denoising_steps_t=0, model=O.DEFAULT_MODEL,
+                 adv_clip_quantiles=None):
         self.base = {k: np.asarray(v, np.float64) for k, v in base.items()}
         self.actor_spec, self.critic_spec = actor_spec, critic_spec
         self.theta = np.concatenate([_flat(actor_spec, ft), _flat(critic_spec, critic)])
@@ -131,7 +133,9 @@ class PPODiffusionLoopOracle:
         self.min_sampling_std, self.randn_clip, self.min_logprob_std = min_sampling_std, randn_clip, min_logprob_std
         self.closs_kw = dict(gamma_denoising=gamma_denoising, clip_ploss_coef=clip_ploss_coef,
                              clip_ploss_coef_base=clip_ploss_coef_base, clip_ploss_coef_rate=clip_ploss_coef_rate,
-                             min_logprob_std=min_logprob_std, vf_coef=vf_coef, reward_horizon=act_steps)
+                             min_logprob_std=min_logprob_std, vf_coef=vf_coef, reward_horizon=act_steps,
+                             model=model, adv_clip_quantiles=adv_clip_quantiles)
+        self.model = model
         self.success_threshold = success_threshold
         self.n_critic_warmup_itr = n_critic_warmup_itr
         self.ft_steps_d, self.ft_steps_t, self.ft_steps_cnt = ft_denoising_steps_d, ft_denoising_steps_t, 0
@@ -158,7 +162,7 @@ class PPODiffusionLoopOracle:
         sh = (E, self.horizon, self.da)
         traj, chain = O.sample(self.base, self.ft, self.sched, obs32[:, None, :], x_T.reshape(sh),
                                z.reshape((K,) + sh), self.kf, deterministic=deterministic,
-                               min_std=self.min_sampling_std, randn_clip=self.randn_clip)
+                               min_std=self.min_sampling_std, randn_clip=self.randn_clip, model=self.model)
         return traj, chain
 
     def iteration(self):
@@ -213,14 +217,14 @@ class PPODiffusionLoopOracle:
         obs_k = obs_traj.reshape(N, 1, -1)
         chains_k = chains.reshape(N, kf + 1, self.horizon, self.da)
         critic = self.critic
-        values = O.critic_forward(critic, obs_k)[0][:, 0].reshape(S, E)              # :191-208
-        lp = O.get_logprobs(self.ft, self.sched, obs_k, chains_k, kf, self.min_logprob_std)   # :209-229
+        values = O.critic_forward(critic, obs_k, self.model)[0][:, 0].reshape(S, E)  # :191-208
+        lp = O.get_logprobs(self.ft, self.sched, obs_k, chains_k, kf, self.min_logprob_std, model=self.model)   # :209-229
         H = min(self.act_steps, self.horizon)
         lp_old = np.clip(lp, -5, 2)[:, :H].mean(axis=(1, 2)).reshape(N, kf)          # c_loss :50-59
         if self.reward_scaler is not None:                                           # :232-236
             rewards = self.reward_scaler(rewards.T, firsts[:-1].T).T
         last_obs = self.prev_obs.astype(np.float32).astype(np.float64)
-        last_values = O.critic_forward(critic, last_obs[:, None, :])[0][:, 0]        # :252
+        last_values = O.critic_forward(critic, last_obs[:, None, :], self.model)[0][:, 0]   # :252
         adv, ret = O.gae(rewards, values, last_values, terms, self.gamma, self.gae_lambda,
                          self.reward_scale_const)                                    # :239-263
         adv_k, ret_k, val_k = adv.reshape(-1), ret.reshape(-1), values.reshape(-1)

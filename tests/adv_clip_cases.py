@@ -1,77 +1,12 @@
-"""The oracle side of the advantage-clip tests (tests/test_adv_clip_cpu.py, tests/test_adv_clip_gpu.py):
+"""The cases of the advantage-clip tests (tests/test_adv_clip_cpu.py, tests/test_adv_clip_gpu.py):
 PPODiffusion's clip_advantage_lower_quantile / clip_advantage_upper_quantile.
 
-`quantile` is the definition, in float64: over the sorted values v_0 <= ... <= v_{n-1},
-    pos = q (n - 1),  k = floor(pos),  Q(q) = v_k + (pos - k) (v_min(k+1, n-1) - v_k),
-numpy.quantile's default linear method (torch.quantile's), the DPPO algorithm's live lines. The reference
-comments them out (model/diffusion/diffusion_ppo.py:77-80) and would have used tfp.stats.percentile, whose
-default is "nearest": parity is unpinned.
-
-The oracle itself is not edited. `adv_clip_oracle(q_lo, q_hi)` replaces O.c_loss for the duration of a case, in
-the manner of tests/param_oracle.py (oracle/iteration.py reaches it by module attribute): the raw advantages of
-the minibatch are clamped to [Q(q_lo), Q(q_hi)] of themselves, and the normalisation keeps the mean and std of
-the UNCLIPPED minibatch through c_loss's own adv_mean_std hook; the denoising discount and the rest are the
-oracle's. Clamping before the affine normalisation is the algorithm's normalise-then-clamp in real arithmetic,
-and works the same with norm_adv off. `lo_hi=` hands in bounds computed elsewhere (a data-parallel shard's
-come from the union of the ranks' rows)."""
-import contextlib
-import inspect
-
+The float64 definition (quantile, bounds, clip_adv) and the clipped loss are the oracle's
+(oracle/dppo_oracle.py; O.c_loss(adv_clip_quantiles=..., adv_clip_bounds=...)). Here: the device's radix select
+restated in NumPy, which is no oracle of the reference, and the inputs both test files run."""
 import numpy as np
 
-from oracle import dppo_oracle as O
-
 INF = float("inf")
-
-
-def order_stats(values, q):
-    """(n, k, k1, v_k, v_k1) of the definition; values as float64."""
-    v = np.sort(np.asarray(values, np.float64).reshape(-1))
-    n = v.size
-    pos = q * (n - 1)
-    k = int(np.floor(pos))
-    k1 = min(k + 1, n - 1)
-    return n, k, k1, v[k], v[k1]
-
-
-def quantile(values, q):
-    n, k, k1, vk, vk1 = order_stats(values, q)
-    pos = q * (n - 1)
-    return vk + (pos - k) * (vk1 - vk)
-
-
-def bounds(values, q_lo, q_hi):
-    """(Q(q_lo), Q(q_hi)); an empty set clips nothing."""
-    if np.asarray(values).size == 0:
-        return -INF, INF
-    return quantile(values, q_lo), quantile(values, q_hi)
-
-
-def clip_adv(adv, q_lo, q_hi, lo_hi=None):
-    adv = np.asarray(adv, np.float64)
-    lo, hi = bounds(adv, q_lo, q_hi) if lo_hi is None else lo_hi
-    return np.clip(adv, lo, hi)
-
-
-@contextlib.contextmanager
-def adv_clip_oracle(q_lo, q_hi, lo_hi=None):
-    orig = O.c_loss
-    sig = inspect.signature(orig)
-
-    def c_loss(*args, **kw):
-        b = sig.bind(*args, **kw)
-        b.apply_defaults()
-        raw = np.asarray(b.arguments["advantages"], np.float64)
-        if b.arguments["norm_adv"] and b.arguments["adv_mean_std"] is None:
-            b.arguments["adv_mean_std"] = (raw.mean(), raw.std())   # of the unclipped minibatch
-        b.arguments["advantages"] = clip_adv(raw, q_lo, q_hi, lo_hi)
-        return orig(*b.args, **b.kwargs)
-
-    O.c_loss = c_loss
-    try:
-        yield
-    finally:
-        O.c_loss = orig
 
 
 # ------------------------------------------------------------------------------------------------

@@ -97,7 +97,7 @@ def recipe150(dims=HOPPER):
 
 
 def reference(p, sched, inp, rnd=None, global_rows=None, loss_scale=1.0, dims=HOPPER):
-    """(loss, gradients) of O.p_losses on the case's rows in float64: the mean over global_rows * XD elements
+    """(loss, gradients) of O.p_losses on the case's rows in float64, for the actor the dims describe: the mean over global_rows * XD elements
     (denom=, a data-parallel shard's share; fp16 then rounds its gradient images with round_fp16_rows(
     global_rows)), times loss_scale."""
     Ta, Da, To, Do = dims["horizon_steps"], dims["action_dim"], dims["cond_steps"], dims["obs_dim"]
@@ -105,7 +105,7 @@ def reference(p, sched, inp, rnd=None, global_rows=None, loss_scale=1.0, dims=HO
     f = lambda x, a, b: np.asarray(x, np.float64).reshape(rows, a, b)
     denom = None if global_rows is None else int(global_rows) * Ta * Da
     loss, g = O.p_losses(p, sched, f(inp["x0"], Ta, Da), f(inp["cond"], To, Do), inp["t"], f(inp["noise"], Ta, Da),
-                         rnd=rnd, denom=denom)
+                         rnd=rnd, denom=denom, model=O.Model.from_dims(dims))
     return loss * loss_scale, {k: v * loss_scale for k, v in g.items()}
 
 

@@ -1,6 +1,6 @@
-"""ELU, GELU and Softplus actors, the CPU half: the float64 definitions of tests/act_oracle.py are what they
+"""ELU, GELU and Softplus actors, the CPU half: the oracle's float64 definitions (O.ACT) are what they
 say (derivatives, no overflow), the Python containers take the three names and the critic still refuses them,
-the oracle under the fixture tells every pair of supported activations apart by at least ten times the bound
+the oracle tells every pair of supported activations apart by at least ten times the bound
 the GPU file uses, and the C ABI carries the new enum values within ABI 15."""
 import json
 import os
@@ -12,9 +12,8 @@ import pytest
 from oracle import dppo_oracle as O
 from tests import test_update_surface_gpu as US
 from tests import test_sampler_surface_gpu as SS
-from tests.act_oracle import (ALL_ACTIVATIONS, F64, NEW_ACTIVATIONS, act_oracle, dims_of, mish_models,  # noqa: F401
-                              sampler_self_noise, site_coverage)
 from tests.helpers import HOPPER, to_f64
+from tests.variants import ALL_ACTIVATIONS, NEW_ACTIVATIONS, dims_of, mish_models, sampler_self_noise, site_coverage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENUM = {"ELU": 3, "GELU": 4, "Softplus": 5}
@@ -26,7 +25,7 @@ def test_derivative_is_the_forwards(name):
     """f' against the central difference of f on [-8, 8] (step 1e-5: truncation h^2 |f'''| / 6 <= 1e-10 for
     these functions, rounding 2e-16 / 1e-5 per unit of |f|: bound 1e-8 (1 + |x|)); ELU's kink at 0, where no
     derivative exists, is stepped over."""
-    f, g = F64[name]
+    f, g = O.ACT[name]
     x = np.linspace(-8, 8, 160001)
     h = 1e-5
     if name == "ELU":
@@ -46,7 +45,7 @@ def test_derivative_is_the_forwards(name):
 @pytest.mark.parametrize("name", NEW_ACTIVATIONS)
 def test_no_overflow(name):
     """+-1e4 (and +-1e300) with floating-point errors raised: finite, the asymptotes exactly."""
-    f, g = F64[name]
+    f, g = O.ACT[name]
     x = np.array([-1e300, -1e4, 1e4, 1e300])
     with np.errstate(over="raise", invalid="raise", divide="raise"):
         y, dy = f(x), g(x)
@@ -95,27 +94,27 @@ def test_constructors_take_the_activation(name):
 _LP = {}
 
 
-def _logprobs(precision, use):
+def _logprobs(precision):
     if precision not in _LP:
         p = US._Problem(HOPPER, precision)
         _, ft, _ = mish_models(0, HOPPER)
         out = {}
         for name in ALL_ACTIVATIONS:
-            last = use(name)
+            caches = []
             out[name] = O.get_logprobs(to_f64(ft), p.sched, p.state(p.obs), p.x(p.chains, p.kf + 1), p.kf,
-                                       rnd=US._rnd(precision))
-            site_coverage(last.cache)
+                                       rnd=US._rnd(precision), model=O.Model(act=name), caches=caches)
+            site_coverage(caches[-1])
         _LP[precision] = out
     return _LP[precision]
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 @pytest.mark.parametrize("name", NEW_ACTIVATIONS)
-def test_oracle_tells_the_activations_apart(act_oracle, name, precision):
+def test_oracle_tells_the_activations_apart(name, precision):
     """The log-probs of `name` against those of every other supported activation, same weights and chains
     (test_mish_oracle_moves_the_update's measure): q99 of |d| / (1 + |other|) >= 10x the log-prob bound of
     the GPU cases (1e-3 fp32, 2e-3 bf16). A pair below it is named."""
-    lp = _logprobs(precision, act_oracle)
+    lp = _logprobs(precision)
     tol = {"fp32": 1e-3, "bf16": 2e-3}[precision]
     q = {o: float(np.quantile(np.abs(lp[name] - lp[o]) / (1 + np.abs(lp[o])), 0.99)) for o in ALL_ACTIVATIONS if o != name}
     print(json.dumps({"case": f"apart-{name}-{precision}", "q99": q, "needs": 10 * tol}))
@@ -123,7 +122,7 @@ def test_oracle_tells_the_activations_apart(act_oracle, name, precision):
     assert not close, close
 
 
-def test_sampler_q99_scale_is_the_oracles_own(act_oracle):
+def test_sampler_q99_scale_is_the_oracles_own():
     """The reason behind ACT_Q99_SCALE of tests/test_actor_activations_gpu.py, on the oracle alone
     (sampler_self_noise: O.sample in bf16 against itself with 2e-7 relative noise ahead of each rounding, hopper,
     the GPU cases' inputs). At E = 513 the actions' q99 of ELU and of Softplus is past the ReLU network's 2e-3 bound
@@ -134,10 +133,9 @@ def test_sampler_q99_scale_is_the_oracles_own(act_oracle):
     tol = SS.TOL["bf16"]
     big, small = {}, {}
     for name in ("ReLU", "GELU", "ELU", "Softplus"):
-        act_oracle(name)
-        big[name] = sampler_self_noise(SS._Inputs(HOPPER, 513, seed=11), "bf16", 0)["act_q99"]
+        big[name] = sampler_self_noise(SS._Inputs(dims_of(name), 513, seed=11), "bf16", 0)["act_q99"]
         if name in ("ReLU", "ELU", "Softplus"):
-            inp = SS._Inputs(HOPPER, 17, seed=11)
+            inp = SS._Inputs(dims_of(name), 17, seed=11)
             small[name] = [sampler_self_noise(inp, "bf16", s)["act_q99"] for s in range(16)]
     spread = {k: (min(v), float(np.median(v)), max(v)) for k, v in small.items()}
     print(json.dumps({"case": "oracle self-noise, actions q99", "E513": big, "E17 min/median/max": spread}))
@@ -150,7 +148,7 @@ def test_sampler_q99_scale_is_the_oracles_own(act_oracle):
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-def test_swapped_derivative_moves_the_gradients(act_oracle, monkeypatch, precision):
+def test_swapped_derivative_moves_the_gradients(monkeypatch, precision):
     """A kernel that ran GELU's forward with Mish's derivative would fail the gradient cases: the oracle with that
     pair against the oracle with GELU's own, on the GPU cases' problem (tests/test_update_surface_gpu.py _Problem,
     N(0, 1) biases), moves every actor gradient tensor that holds the derivative (l1, in, the time MLP) by more than TWICE the
@@ -158,10 +156,9 @@ def test_swapped_derivative_moves_the_gradients(act_oracle, monkeypatch, precisi
     that were within one bound of the wrong oracle is then more than one bound from the right one. Measured: 40 to
     72 bounds in fp32, 9 to 19 in bf16."""
     monkeypatch.setattr(US, "make_models", mish_models)
-    act_oracle("GELU")
     p = US._Problem(dims_of("GELU"), precision)
     right = p.oracle()
-    monkeypatch.setitem(O.ACT, "GELU", (F64["GELU"][0], O.ACT["Mish"][1]))
+    monkeypatch.setitem(O.ACT, "GELU", (O.ACT["GELU"][0], O.ACT["Mish"][1]))   # fault injection: a wrong pair
     wrong = p.oracle()
     moved = {k: US._rel(wrong[1][k], right[1][k]) for k in right[1]}
     print(json.dumps({"case": f"gelu-forward-mish-derivative-{precision}", "moved": moved, "needs": 2 * US.TOL[precision]}))
@@ -171,15 +168,12 @@ def test_swapped_derivative_moves_the_gradients(act_oracle, monkeypatch, precisi
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-def test_elu_swapped_for_relu_moves_the_sampler(act_oracle, precision):
-    """A kernel that ran ReLU where the image says ELU would fail the sampler cases: O.sample under ELU against
-    O.sample under ReLU, the GPU cases' inputs (hopper, E = 17), differs by >= 10x the sampler bound
+def test_elu_swapped_for_relu_moves_the_sampler(precision):
+    """A kernel that ran ReLU where the image says ELU would fail the sampler cases: O.sample with ELU against
+    O.sample with ReLU, the GPU cases' inputs (hopper, E = 17), differs by >= 10x the sampler bound
     (SS._assert_moved: test_mish_oracle_moves_the_sampler's measure)."""
-    inp = SS._Inputs(HOPPER, 17, seed=11)
-    act_oracle("ELU")
-    elu = inp.oracle(precision)
-    act_oracle("ReLU")
-    SS._assert_moved(f"elu-vs-relu-{precision}", precision, elu, inp.oracle(precision))
+    inp = SS._Inputs(dims_of("ELU"), 17, seed=11)
+    SS._assert_moved(f"elu-vs-relu-{precision}", precision, inp.oracle(precision), inp.oracle(precision, model=O.Model()))
 
 
 def test_header_and_abi():

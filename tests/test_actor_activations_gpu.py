@@ -1,6 +1,5 @@
 """ELU, GELU and Softplus actors on the GPU: every entry that takes a packed actor image, against the oracle
-under tests/act_oracle.py's fixture (the oracle's composed functions with diffusion_mlp_forward / _backward
-wrapped for the duration of a test, and the float64 pair added to O.ACT).
+with that activation (O.Model(act=<name>), derived from the dims).
 
 Each case mirrors a case of tests/test_actor_mish_gpu.py at the same shape with the same bound, through the same
 helpers (_Inputs / _Gpu / _check of test_sampler_surface_gpu, _Problem / _Gpu / _compare of
@@ -29,8 +28,8 @@ from tests import test_kernels_gpu as KG
 from tests import test_sampler_surface_gpu as SS
 from tests import test_update_regimes_gpu as UR
 from tests import test_update_surface_gpu as US
-from tests.act_oracle import NEW_ACTIVATIONS, act_oracle, dims_of, mish_models, site_coverage  # noqa: F401
 from tests.helpers import HOPPER, HOPPER_DDIM, WALKER, to_f64
+from tests.variants import NEW_ACTIVATIONS, dims_of, mish_models, site_coverage
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -49,7 +48,7 @@ ACTS = pytest.mark.parametrize("name", NEW_ACTIVATIONS)
 # the other way; how far twenty denoising steps carry such a decision depends on the network, and the 2e-3 bound is
 # the ReLU network's. ELU and Softplus do not vanish on the negative side (-1, and ln 2 at 0), so every hidden unit
 # carries a bf16 half-ulp of 1e-3 to 2e-3 where relu, mish and gelu carry zeros or small values. The ORACLE ALONE
-# shows it (tests.act_oracle.sampler_self_noise: O.sample against itself with 2e-7 relative noise ahead of each
+# shows it (tests.variants.sampler_self_noise: O.sample against itself with 2e-7 relative noise ahead of each
 # rounding; tests/test_actor_activations_cpu.py::test_sampler_q99_scale_is_the_oracles_own pins these figures):
 #   E = 513 (q99 of 6,156 actions, a stable statistic): ReLU 1.21e-3, Mish 1.19e-3, GELU 0.95e-3, ELU 2.02e-3 (1.67 x
 #     ReLU), Softplus 3.18e-3 (2.63 x ReLU): ELU and Softplus are past ReLU's bound in the reference itself; the
@@ -86,12 +85,11 @@ SAMPLER_CASES = [
 
 @ACTS
 @pytest.mark.parametrize("label,dims,extra,precision,E,kernel", SAMPLER_CASES, ids=[c[0] for c in SAMPLER_CASES])
-def test_sampler_matches_oracle(cuda, act_oracle, name, label, dims, extra, precision, E, kernel):
-    """dppo_sample on images of the activation, injected noise, against O.sample under the fixture: actions and
+def test_sampler_matches_oracle(cuda, name, label, dims, extra, precision, E, kernel):
+    """dppo_sample on images of the activation, injected noise, against O.sample with the activation: actions and
     every stored chain row (SS._check's bounds, the ReLU and Mish cases'; ACT_Q99_SCALE above for one statistic of
     three cases); the plan is the ReLU plan of the shape."""
     from diffusionpolicyoptimization_amd import ops
-    act_oracle(name, head=extra.get("head", "residual"))
     inp = SS._Inputs(dims_of(name, dims, **extra), E, seed=11)
     g = SS._Gpu(inp, precision, cuda)
     assert g.plan["kernel"] == kernel and g.plan == ops.sampler_plan(ops.ModelDims(**dims), precision, E), g.plan
@@ -140,20 +138,21 @@ def test_sampler_refuses_mixed_images(cuda, precision, E):
 @pytest.mark.parametrize("head", ["residual", "plain"])
 @pytest.mark.parametrize("precision,tol", [("fp32", 1e-3), ("bf16", 2e-3)])
 @pytest.mark.parametrize("n", [48, 45])
-def test_logprob_matches_oracle(cuda, act_oracle, monkeypatch, name, head, precision, tol, n):
+def test_logprob_matches_oracle(cuda, monkeypatch, name, head, precision, tol, n):
     """48 samples x K' = 10 = fifteen 32-row tiles, 45 a partial last tile; lp_elem (q99) and lp_mean against
-    O.get_logprobs under the fixture."""
+    O.get_logprobs with the activation and the head."""
     import torch
     from diffusionpolicyoptimization_amd import ops
-    last = act_oracle(name, head=head)
     monkeypatch.setattr(KG, "make_models", mish_models)
     d, _, ft, _, sched, tab, _, pf, _ = KG._setup(dims_of(name, head=head), cuda)
     kf = d.ft_denoising_steps
     rng = np.random.default_rng(4)
     state = rng.uniform(-1, 1, (n, 1, d.obs_dim)).astype(np.float32)
     chains = (rng.standard_normal((n, kf + 1, d.horizon_steps, d.action_dim)) * 0.5).astype(np.float32)
-    ref = O.get_logprobs(to_f64(ft), sched, state.astype(np.float64), chains.astype(np.float64), kf, rnd=KG._rnd(precision))
-    cov = site_coverage(last.cache)
+    caches = []
+    ref = O.get_logprobs(to_f64(ft), sched, state.astype(np.float64), chains.astype(np.float64), kf, rnd=KG._rnd(precision),
+                         model=O.Model.from_dims(d), caches=caches)
+    cov = site_coverage(caches[-1])
     assert ops.ppo_plan(d, precision, n * kf, mode="logprob")["actor_tile_rows"] == 32
     lpe, lpm = ops.logprob(d, precision, ops.pack_actor(d, pf, precision), tab,
                            torch.tensor(state.reshape(n, -1), device=cuda),
@@ -176,15 +175,15 @@ GRAD_CASES = [("hopper", HOPPER, "fp32"), ("hopper", HOPPER, "bf16"), ("hopper",
 
 @ACTS
 @pytest.mark.parametrize("geo,dims,precision", GRAD_CASES, ids=[f"{n}-{p}" for n, _, p in GRAD_CASES])
-def test_ppo_minibatch_grads_match_oracle(cuda, act_oracle, monkeypatch, name, geo, dims, precision):
+def test_ppo_minibatch_grads_match_oracle(cuda, monkeypatch, name, geo, dims, precision):
     """test_ppo_minibatch_grads_match_mish_oracle: the surface tests' 150 rows (four 32-row tiles and a ragged
-    fifth): the loss metrics and every gradient tensor against O.c_loss under the fixture."""
+    fifth): the loss metrics and every gradient tensor against O.c_loss with the activation."""
     from diffusionpolicyoptimization_amd import ops
-    last = act_oracle(name)
     monkeypatch.setattr(US, "make_models", mish_models)
     p = US._Problem(dims_of(name, dims), precision)
-    ref = p.oracle()
-    cov = site_coverage(last.cache)
+    caches = []
+    ref = p.oracle(caches=caches)
+    cov = site_coverage(caches[-1])
     gpu = US._Gpu(p, cuda)
     plan = ops.ppo_plan(p.d, precision, US.ROWS)
     assert (plan["actor_tile_rows"], plan["actor_waves"]) == (32, 8), plan
@@ -195,20 +194,20 @@ def test_ppo_minibatch_grads_match_oracle(cuda, act_oracle, monkeypatch, name, g
 
 @ACTS
 @pytest.mark.parametrize("size", ["33", "round+1"])
-def test_ppo_minibatch_row_edges(cuda, act_oracle, monkeypatch, name, size):
+def test_ppo_minibatch_row_edges(cuda, monkeypatch, name, size):
     """33 rows (one 32-row tile and one row of a second) and 32 C + 1 rows (C the CU count: one full round of
     32-row tiles and one row more), bf16: metrics and every gradient tensor at the regime tests' bound
     (test_large_minibatch_runs_the_32_row_tile's checks)."""
     from diffusionpolicyoptimization_amd import ops
-    last = act_oracle(name)
     monkeypatch.setattr(KG, "make_models", mish_models)
     rows = 33 if size == "33" else 32 * UR._cus(cuda) + 1
     case = UR._Case(cuda, "bf16", dims_of(name), -(-(UR.START + rows) // 10) + 5)
     plan = ops.ppo_plan(case.d, "bf16", rows)
     assert (plan["actor_tile_rows"], plan["actor_waves"]) == (32, 8), plan
     stats, mean_std = case.adv_stats(rows)
-    met_ref, ga_ref, gc_ref = case.oracle(rows, adv_mean_std=mean_std)
-    cov = site_coverage(last.cache)
+    caches = []
+    met_ref, ga_ref, gc_ref = case.oracle(rows, adv_mean_std=mean_std, caches=caches)
+    cov = site_coverage(caches[-1])
     g, m = case.launch(rows, UR.START, rows, stats=stats)
     print(json.dumps({"case": f"{name}-rows-{size}", "rows": rows, "plan": plan, "coverage": cov}))
     assert np.isfinite(g).all()
@@ -216,15 +215,15 @@ def test_ppo_minibatch_row_edges(cuda, act_oracle, monkeypatch, name, size):
     UR._check_errs(UR._tensor_errs(case.d, g, ga_ref, gc_ref), UR.TOL["bf16"], f"{name}-rows-{size}")
 
 
-def test_ppo_minibatch_learn_eta_ddim_gelu(cuda, act_oracle, monkeypatch):
+def test_ppo_minibatch_learn_eta_ddim_gelu(cuda, monkeypatch):
     """test_ppo_minibatch_learn_eta_ddim_mish with GELU: metrics[8] and every gradient tensor (d_eta 3e-2 relative)."""
-    last = act_oracle("GELU")
     monkeypatch.setattr(KG, "make_models", mish_models)
     rows = US.ROWS
     case = UR._Case(cuda, "bf16", dims_of("GELU", HOPPER_DDIM), US.NSAMP, eta=0.6)
     stats, mean_std = case.adv_stats(rows)
-    met_ref, ga_ref, gc_ref = case.oracle(rows, adv_mean_std=mean_std, eta_grad=True)
-    cov = site_coverage(last.cache)
+    caches = []
+    met_ref, ga_ref, gc_ref = case.oracle(rows, adv_mean_std=mean_std, eta_grad=True, caches=caches)
+    cov = site_coverage(caches[-1])
     g, m = case.launch(rows, UR.START, rows, stats=stats, learn_eta=True)
     ref = met_ref["d_eta"]
     print(json.dumps({"case": "GELU-learn-eta", "d_eta": float(m[8]), "ref": ref, "coverage": cov}))
@@ -236,13 +235,12 @@ def test_ppo_minibatch_learn_eta_ddim_gelu(cuda, act_oracle, monkeypatch):
 @ACTS
 @pytest.mark.parametrize("precision,rtol", [("fp32", 2e-3), ("bf16", 1e-2)])
 @pytest.mark.parametrize("rows", [1, 33, 65])
-def test_pretrain_matches_oracle(cuda, act_oracle, monkeypatch, name, precision, rtol, rows):
-    """dppo_pretrain_minibatch at 1, 33 and 65 rows: loss and every actor gradient against O.p_losses under the
-    fixture (test_pretrain_matches_mish_oracle's inputs and bounds). One row covers little of the activation's
+def test_pretrain_matches_oracle(cuda, monkeypatch, name, precision, rtol, rows):
+    """dppo_pretrain_minibatch at 1, 33 and 65 rows: loss and every actor gradient against O.p_losses with the
+    activation (test_pretrain_matches_mish_oracle's inputs and bounds). One row covers little of the activation's
     range, so the coverage is asserted from 33 rows on."""
     import torch
     from diffusionpolicyoptimization_amd import ops
-    last = act_oracle(name)
     monkeypatch.setattr(KG, "make_models", mish_models)
     d, _, ft, _, sched, tab, _, pf, _ = KG._setup(dims_of(name), cuda)
     rng = np.random.default_rng(21)
@@ -252,10 +250,12 @@ def test_pretrain_matches_oracle(cuda, act_oracle, monkeypatch, name, precision,
     t = rng.integers(0, K, rows).astype(np.int32)
     noise = rng.standard_normal((rows, d.xd)).astype(np.float32)
     sh = (rows, d.horizon_steps, d.action_dim)
+    caches = []
     loss_ref, g_ref = O.p_losses(to_f64(ft), sched, x0.reshape(sh).astype(np.float64),
                                  cond.reshape(rows, d.cond_steps, d.obs_dim).astype(np.float64), t,
-                                 noise.reshape(sh).astype(np.float64), rnd=KG._rnd(precision))
-    cov = site_coverage(last.cache) if rows >= 33 else None
+                                 noise.reshape(sh).astype(np.float64), rnd=KG._rnd(precision), model=O.Model.from_dims(d),
+                                 caches=caches)
+    cov = site_coverage(caches[-1]) if rows >= 33 else None
     T = lambda x: torch.tensor(x, device=cuda)
     grads = torch.zeros(ops.spec_count(ops.actor_param_spec(d)), dtype=torch.float32, device=cuda)
     metrics = torch.zeros(16, dtype=torch.float64, device=cuda)
@@ -274,7 +274,7 @@ def test_pretrain_matches_oracle(cuda, act_oracle, monkeypatch, name, precision,
 # ------------------------------------------------------------------------------------------------
 # the attribute
 # ------------------------------------------------------------------------------------------------
-def test_attribute_follows_the_image(cuda, act_oracle):
+def test_attribute_follows_the_image(cuda):
     """The same weights packed as ELU into one pair of buffers and as GELU into another: each launch runs its own
     activation (each within the sampler's bound of its own oracle, and the two results differ); fresh ELU, GELU
     and Softplus packs are SHA-equal to the Mish pack of the same weights; re-packed in place by plain dppo_pack_actor the ELU
@@ -284,7 +284,6 @@ def test_attribute_follows_the_image(cuda, act_oracle):
     sha = lambda t: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
     out = {}
     for name in ("ELU", "GELU"):
-        act_oracle(name)
         inp = SS._Inputs(dims_of(name), 17, seed=11)
         g = SS._Gpu(inp, "bf16", cuda)
         out[name] = (g, *g.sample())
@@ -368,13 +367,12 @@ CFG = {"ELU": "elu", "GELU": "gelu", "Softplus": "softplus"}
 
 
 @ACTS
-def test_model_call_matches_oracle(cuda, act_oracle, tmp_path, name):
+def test_model_call_matches_oracle(cuda, tmp_path, name):
     """test_model_call_matches_mish_oracle on the model built from the activation's cfg."""
     import torch
     from diffusionpolicyoptimization_amd import ops
     from diffusionpolicyoptimization_amd.model.diffusion.sampling import ddpm_buffers
     from diffusionpolicyoptimization_amd.util.config import instantiate, load_config
-    act_oracle(name)
     cfg = load_config(os.path.join(ROOT, "cfg/gym/finetune/hopper-v2"), f"ft_ppo_diffusion_mlp_{CFG[name]}",
                       ["model.precision=fp32", f"logdir={tmp_path}"])
     m = instantiate(cfg.model)
@@ -391,20 +389,20 @@ def test_model_call_matches_oracle(cuda, act_oracle, tmp_path, name):
     un = lambda flat, spec: to_f64(ops.unflatten_params(spec, flat.cpu().numpy()))
     ref_a, ref_c = O.sample(un(m.base_params, m.actor_spec), un(m.actor_ft_params, m.actor_spec), ddpm_buffers(K),
                             state.astype(np.float64), xT, z, d.ft_denoising_steps,
-                            min_std=m.get_min_sampling_denoising_std(), randn_clip=m.randn_clip_value, round_h3=False)
+                            min_std=m.get_min_sampling_denoising_std(), randn_clip=m.randn_clip_value, round_h3=False,
+                            model=O.Model.from_dims(d))
     st = SS._stats(act.cpu().numpy().reshape(ref_a.shape), ch.cpu().numpy().reshape(ref_c.shape), ref_a, ref_c)
     SS._check(f"{name} model(cond)", "fp32", st)
 
 
 @ACTS
-def test_iteration_matches_oracle(cuda, act_oracle, tmp_path, monkeypatch, name):
+def test_iteration_matches_oracle(cuda, tmp_path, monkeypatch, name):
     """An eval and a training iteration of the fp32 agent from the activation's cfg (seed 42, n_steps 8, batch
-    size 160) against oracle/iteration.py under the fixture, at tests/test_iteration_gpu.py's own bounds,
+    size 160) against oracle/iteration.py with the activation, at tests/test_iteration_gpu.py's own bounds,
     unchanged (_run_and_compare: chains 2e-5 absolute, rewards, values, old log-probs, advantages, returns, the last
     minibatch's losses, the number of applied minibatches, the parameter change). Measured chains: ELU 2.9e-6,
     GELU 2.2e-6, Softplus 5.3e-6."""
     from diffusionpolicyoptimization_amd.util import config
-    act_oracle(name)
     load = config.load_config
     monkeypatch.setattr(config, "load_config", lambda root, cfg, ov: load(root, f"{cfg}_{CFG[name]}", ov))
     a, orc = IT._agent_and_oracle(42, tmp_path, ["train.n_steps=8", "train.batch_size=160"])

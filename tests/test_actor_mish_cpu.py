@@ -1,5 +1,5 @@
-"""Mish actor, the CPU half: the Python container takes the reference's default activation, the Mish
-oracle fixture (tests/mish_oracle.py) moves every quantity the GPU file compares by at least ten times
+"""Mish actor, the CPU half: the Python container takes the reference's default activation, the oracle's
+Mish actor (O.Model(act="Mish")) moves every quantity the GPU file compares by at least ten times
 the bound used there, and the C ABI carries the new entries within ABI 15."""
 import json
 import os
@@ -13,7 +13,7 @@ from oracle import dppo_oracle as O
 from tests import test_sampler_surface_gpu as SS
 from tests import test_update_surface_gpu as US
 from tests.helpers import HOPPER, to_f64
-from tests.mish_oracle import HOPPER_MISH, mish_models, mish_oracle, site_coverage  # noqa: F401
+from tests.variants import HOPPER_MISH, mish_models, site_coverage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -39,26 +39,24 @@ def test_diffusion_mlp_takes_mish():
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16", "fp16"])
-def test_mish_oracle_moves_the_sampler(mish_oracle, monkeypatch, precision):
-    """O.sample under the fixture against ReLU, same weights and draws: >= 10x the sampler bound."""
-    inp = SS._Inputs(HOPPER, 17, seed=11)
-    mish = inp.oracle(precision)
-    monkeypatch.undo()
-    SS._assert_moved(f"mish-vs-relu-{precision}", precision, mish, inp.oracle(precision))
+def test_mish_oracle_moves_the_sampler(precision):
+    """O.sample with the Mish actor against ReLU, same weights and draws: >= 10x the sampler bound."""
+    inp = SS._Inputs(HOPPER_MISH, 17, seed=11)
+    SS._assert_moved(f"mish-vs-relu-{precision}", precision, inp.oracle(precision), inp.oracle(precision, model=O.Model()))
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-def test_mish_oracle_moves_the_update(mish_oracle, monkeypatch, precision):
-    """get_logprobs and the c_loss gradients under the fixture against ReLU on the same problem
+def test_mish_oracle_moves_the_update(monkeypatch, precision):
+    """get_logprobs and the c_loss gradients with the Mish actor against ReLU on the same problem
     (weights, rows, old log-probs): >= 10x the bounds of the GPU cases; and the Mish problem's
     pre-activations cover x < -1 and x > 0 at both sites."""
     monkeypatch.setattr(US, "make_models", mish_models)
     p = US._Problem(HOPPER_MISH, precision)
-    lp_m, ref_m = p.lp_ref, p.oracle()
-    cov = site_coverage(mish_oracle.cache)
-    monkeypatch.undo()
+    caches = []
+    lp_m, ref_m = p.lp_ref, p.oracle(caches=caches)
+    cov = site_coverage(caches[-1])
     lp_r = O.get_logprobs(to_f64(p.ft), p.sched, p.state(p.obs), p.x(p.chains, p.kf + 1), p.kf, rnd=US._rnd(precision))
-    ref_r = p.oracle()
+    ref_r = p.oracle(model=O.Model())
     tol_lp = {"fp32": 1e-3, "bf16": 2e-3}[precision]
     rel = np.abs(lp_m - lp_r) / (1 + np.abs(lp_r))
     moved = {k: US._rel(ref_m[1][k], ref_r[1][k]) for k in ref_r[1]}

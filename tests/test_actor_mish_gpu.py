@@ -1,6 +1,5 @@
-"""Mish actor on the GPU: every entry that takes a packed actor image, against the Mish oracle
-(tests/mish_oracle.py: the oracle's composed functions with diffusion_mlp_forward / _backward wrapped
-for the duration of a test).
+"""Mish actor on the GPU: every entry that takes a packed actor image, against the oracle's Mish actor
+(O.Model(act="Mish"), derived from the dims).
 
 Bounds are the ReLU cases' of the same entry and path, unchanged: the sampler's of
 tests/test_sampler_surface_gpu.py (fp32 2e-4 absolute on actions and chains; 2-byte q99 / means 2e-3
@@ -33,7 +32,7 @@ from tests import test_sampler_surface_gpu as SS
 from tests import test_update_regimes_gpu as UR
 from tests import test_update_surface_gpu as US
 from tests.helpers import HOPPER, HOPPER_DDIM, WALKER, to_f64
-from tests.mish_oracle import HOPPER_MISH, MISH, WALKER_MISH, mish_models, mish_oracle, site_coverage  # noqa: F401
+from tests.variants import HOPPER_MISH, MISH, WALKER_MISH, mish_models, site_coverage
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,8 +57,8 @@ SAMPLER_CASES = [
 
 
 @pytest.mark.parametrize("label,dims,precision,E,kernel,kw,eta", SAMPLER_CASES, ids=[c[0] for c in SAMPLER_CASES])
-def test_sampler_matches_mish_oracle(cuda, mish_oracle, label, dims, precision, E, kernel, kw, eta):
-    """dppo_sample on Mish images, injected noise, against O.sample under the fixture: actions and every
+def test_sampler_matches_mish_oracle(cuda, label, dims, precision, E, kernel, kw, eta):
+    """dppo_sample on Mish images, injected noise, against O.sample with the Mish actor: actions and every
     stored chain row; the plan is the ReLU plan of the same shape."""
     from diffusionpolicyoptimization_amd import ops
     inp = SS._Inputs(dims, E, seed=11, eta=eta)
@@ -102,7 +101,7 @@ def test_sampler_refuses_mixed_images(cuda, precision, E):
     g.sample()
 
 
-def test_attribute_follows_the_image(cuda, mish_oracle, monkeypatch):
+def test_attribute_follows_the_image(cuda):
     """A buffer packed with Mish samples as Mish; re-packed in place by plain dppo_pack_actor it samples
     as a fresh ReLU image does, bit for bit (and differs from its Mish result)."""
     import torch
@@ -122,7 +121,7 @@ def test_attribute_follows_the_image(cuda, mish_oracle, monkeypatch):
     a_relu, c_relu = fresh.sample()
     assert a_again.tobytes() == a_relu.tobytes() and c_again.tobytes() == c_relu.tobytes()
     assert a_again.tobytes() != a_mish.tobytes()
-    monkeypatch.undo()                                       # and that is the ReLU oracle's result
+    # and that is the ReLU oracle's result
     SS._check("attribute: relu after re-pack", "bf16", SS._stats(a_again, c_again, *fresh.inp.oracle("bf16")))
     torch.cuda.synchronize()
 
@@ -132,9 +131,9 @@ def test_attribute_follows_the_image(cuda, mish_oracle, monkeypatch):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("precision,tol", [("fp32", 1e-3), ("bf16", 2e-3)])
 @pytest.mark.parametrize("n", [48, 45])
-def test_logprob_matches_mish_oracle(cuda, mish_oracle, monkeypatch, precision, tol, n):
+def test_logprob_matches_mish_oracle(cuda, monkeypatch, precision, tol, n):
     """dppo_logprob on a Mish image: 48 samples x K' = 10 = fifteen 32-row tiles, 45 a partial last tile;
-    lp_elem and lp_mean against O.get_logprobs under the fixture (test_logprob's measures and bounds)."""
+    lp_elem and lp_mean against O.get_logprobs with the Mish actor (test_logprob's measures and bounds)."""
     import torch
     from diffusionpolicyoptimization_amd import ops
     monkeypatch.setattr(KG, "make_models", mish_models)
@@ -143,8 +142,10 @@ def test_logprob_matches_mish_oracle(cuda, mish_oracle, monkeypatch, precision, 
     rng = np.random.default_rng(4)
     state = rng.uniform(-1, 1, (n, 1, d.obs_dim)).astype(np.float32)
     chains = (rng.standard_normal((n, kf + 1, d.horizon_steps, d.action_dim)) * 0.5).astype(np.float32)
-    ref = O.get_logprobs(to_f64(ft), sched, state.astype(np.float64), chains.astype(np.float64), kf, rnd=KG._rnd(precision))
-    cov = site_coverage(mish_oracle.cache)
+    caches = []
+    ref = O.get_logprobs(to_f64(ft), sched, state.astype(np.float64), chains.astype(np.float64), kf, rnd=KG._rnd(precision),
+                         model=O.Model.from_dims(d), caches=caches)
+    cov = site_coverage(caches[-1])
     assert ops.ppo_plan(d, precision, n * kf, mode="logprob")["actor_tile_rows"] == 32
     lpe, lpm = ops.logprob(d, precision, ops.pack_actor(d, pf, precision), tab,
                            torch.tensor(state.reshape(n, -1), device=cuda),
@@ -167,13 +168,14 @@ GRAD_CASES = [("hopper", HOPPER_MISH, "fp32"), ("hopper", HOPPER_MISH, "bf16"), 
 
 
 @pytest.mark.parametrize("name,dims,precision", GRAD_CASES, ids=[f"{n}-{p}" for n, _, p in GRAD_CASES])
-def test_ppo_minibatch_grads_match_mish_oracle(cuda, mish_oracle, monkeypatch, name, dims, precision):
+def test_ppo_minibatch_grads_match_mish_oracle(cuda, monkeypatch, name, dims, precision):
     """dppo_ppo_minibatch on a Mish image at the surface tests' NSAMP / ROWS: the loss metrics and every
-    gradient tensor against O.c_loss under the fixture; h1 and h2 cover x < -1 and x > 0."""
+    gradient tensor against O.c_loss with the Mish actor; h1 and h2 cover x < -1 and x > 0."""
     monkeypatch.setattr(US, "make_models", mish_models)
     p = US._Problem(dims, precision)
-    ref = p.oracle()
-    cov = site_coverage(mish_oracle.cache)
+    caches = []
+    ref = p.oracle(caches=caches)
+    cov = site_coverage(caches[-1])
     gpu = US._Gpu(p, cuda)
     from diffusionpolicyoptimization_amd import ops
     plan = ops.ppo_plan(p.d, precision, US.ROWS)
@@ -183,15 +185,16 @@ def test_ppo_minibatch_grads_match_mish_oracle(cuda, mish_oracle, monkeypatch, n
     US._compare(f"mish-{name}-{precision}", gpu, m, g, ref, US.TOL[precision])
 
 
-def test_ppo_minibatch_learn_eta_ddim_mish(cuda, mish_oracle, monkeypatch):
+def test_ppo_minibatch_learn_eta_ddim_mish(cuda, monkeypatch):
     """DPPO_PPO_LEARN_ETA behind a Mish forward (hopper DDIM, bf16, eta 0.6): metrics[8] and every
     gradient tensor against the oracle (the 64-row tile test's d_eta bound, 3e-2 relative)."""
     monkeypatch.setattr(KG, "make_models", mish_models)
     rows = US.ROWS
     case = UR._Case(cuda, "bf16", HOPPER_DDIM_MISH, US.NSAMP, eta=0.6)
     stats, mean_std = case.adv_stats(rows)
-    met_ref, ga_ref, gc_ref = case.oracle(rows, adv_mean_std=mean_std, eta_grad=True)
-    cov = site_coverage(mish_oracle.cache)
+    caches = []
+    met_ref, ga_ref, gc_ref = case.oracle(rows, adv_mean_std=mean_std, eta_grad=True, caches=caches)
+    cov = site_coverage(caches[-1])
     g, m = case.launch(rows, UR.START, rows, stats=stats, learn_eta=True)
     ref = met_ref["d_eta"]
     print(json.dumps({"case": "mish-learn-eta", "d_eta": float(m[8]), "ref": ref, "coverage": cov}))
@@ -201,9 +204,9 @@ def test_ppo_minibatch_learn_eta_ddim_mish(cuda, mish_oracle, monkeypatch):
 
 
 @pytest.mark.parametrize("precision,rtol", [("fp32", 2e-3), ("bf16", 1e-2)])
-def test_pretrain_matches_mish_oracle(cuda, mish_oracle, monkeypatch, precision, rtol):
-    """dppo_pretrain_minibatch on a Mish image: loss and every actor gradient against O.p_losses under
-    the fixture (test_pretrain_loss_grads' shapes and bounds)."""
+def test_pretrain_matches_mish_oracle(cuda, monkeypatch, precision, rtol):
+    """dppo_pretrain_minibatch on a Mish image: loss and every actor gradient against O.p_losses with
+    the Mish actor (test_pretrain_loss_grads' shapes and bounds)."""
     import torch
     from diffusionpolicyoptimization_amd import ops
     monkeypatch.setattr(KG, "make_models", mish_models)
@@ -215,10 +218,12 @@ def test_pretrain_matches_mish_oracle(cuda, mish_oracle, monkeypatch, precision,
     t = rng.integers(0, K, rows).astype(np.int32)
     noise = rng.standard_normal((rows, d.xd)).astype(np.float32)
     sh = (rows, d.horizon_steps, d.action_dim)
+    caches = []
     loss_ref, g_ref = O.p_losses(to_f64(ft), sched, x0.reshape(sh).astype(np.float64),
                                  cond.reshape(rows, d.cond_steps, d.obs_dim).astype(np.float64), t,
-                                 noise.reshape(sh).astype(np.float64), rnd=KG._rnd(precision))
-    cov = site_coverage(mish_oracle.cache)
+                                 noise.reshape(sh).astype(np.float64), rnd=KG._rnd(precision), model=O.Model.from_dims(d),
+                                 caches=caches)
+    cov = site_coverage(caches[-1])
     T = lambda x: torch.tensor(x, device=cuda)
     grads = torch.zeros(ops.spec_count(ops.actor_param_spec(d)), dtype=torch.float32, device=cuda)
     metrics = torch.zeros(16, dtype=torch.float64, device=cuda)
@@ -234,7 +239,7 @@ def test_pretrain_matches_mish_oracle(cuda, mish_oracle, monkeypatch, precision,
     assert not bad, (bad, errs)
 
 
-def test_large_minibatch_runs_the_32_row_tile(cuda, mish_oracle, monkeypatch):
+def test_large_minibatch_runs_the_32_row_tile(cuda, monkeypatch):
     """One round of 64-row tiles for a ReLU actor (64 (C - 1) + 1 rows, C the CU count: the smallest size
     of test_actor_tile64_grads_match_oracle), bf16 TRAIN with a Mish actor: the 64-row tile is not
     instantiated for Mish, ops.ppo_plan says 32 rows on 8 waves, and every gradient tensor matches the
@@ -248,8 +253,9 @@ def test_large_minibatch_runs_the_32_row_tile(cuda, mish_oracle, monkeypatch):
     assert ops.ppo_plan(ops.ModelDims(**HOPPER), "bf16", rows)["actor_tile_rows"] == 64
     assert (plan["actor_tile_rows"], plan["actor_waves"]) == (32, 8) and plan["dw_chunks_actor"] > 1, plan
     stats, mean_std = case.adv_stats(rows)
-    met_ref, ga_ref, gc_ref = case.oracle(rows, adv_mean_std=mean_std)
-    cov = site_coverage(mish_oracle.cache)
+    caches = []
+    met_ref, ga_ref, gc_ref = case.oracle(rows, adv_mean_std=mean_std, caches=caches)
+    cov = site_coverage(caches[-1])
     g, m = case.launch(rows, UR.START, rows, stats=stats)
     print(json.dumps({"case": "mish-large-minibatch", "rows": rows, "plan": plan, "coverage": cov}))
     assert np.isfinite(g).all()
@@ -294,7 +300,7 @@ def test_mish_refusals(cuda):
 # ------------------------------------------------------------------------------------------------
 # agents
 # ------------------------------------------------------------------------------------------------
-def test_model_call_matches_mish_oracle(cuda, mish_oracle, tmp_path):
+def test_model_call_matches_mish_oracle(cuda, tmp_path):
     """The model built from ft_ppo_diffusion_mlp_mish.yaml: model(cond) on injected draws equals the Mish
     oracle's sample (fp32, the sampler's bound)."""
     import torch
@@ -317,7 +323,8 @@ def test_model_call_matches_mish_oracle(cuda, mish_oracle, tmp_path):
     from diffusionpolicyoptimization_amd.model.diffusion.sampling import ddpm_buffers
     ref_a, ref_c = O.sample(un(m.base_params, m.actor_spec), un(m.actor_ft_params, m.actor_spec), ddpm_buffers(K),
                             state.astype(np.float64), xT, z, d.ft_denoising_steps,
-                            min_std=m.get_min_sampling_denoising_std(), randn_clip=m.randn_clip_value, round_h3=False)
+                            min_std=m.get_min_sampling_denoising_std(), randn_clip=m.randn_clip_value, round_h3=False,
+                            model=O.Model.from_dims(d))
     st = SS._stats(act.cpu().numpy().reshape(ref_a.shape), ch.cpu().numpy().reshape(ref_c.shape), ref_a, ref_c)
     SS._check("mish model(cond)", "fp32", st)
 

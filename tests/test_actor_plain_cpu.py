@@ -1,5 +1,5 @@
-"""Plain-head actor (DiffusionMLP residual_style=False, mlp_dims [h, h]), the CPU half: the plain oracle
-(tests/plain_oracle.py) is right (finite differences) and moves every quantity the GPU file compares by at
+"""Plain-head actor (DiffusionMLP residual_style=False, mlp_dims [h, h]), the CPU half: the oracle's plain head
+(O.Model(head="plain")) is right (finite differences) and moves every quantity the GPU file compares by at
 least ten times that quantity's bound; the Python containers accept exactly the supported shape; actor_spec
 has no l2 and maps onto the residual offsets; the C ABI carries the new symbols within ABI 15; checkpoints
 round-trip and do not cross heads."""
@@ -14,7 +14,7 @@ from oracle import dppo_oracle as O
 from tests import test_sampler_surface_gpu as SS
 from tests import test_update_surface_gpu as US
 from tests.helpers import HOPPER, to_f64
-from tests.plain_oracle import (HOPPER_PLAIN, diffusion_plain_backward, diffusion_plain_forward, plain_oracle)  # noqa: F401
+from tests.variants import HOPPER_PLAIN
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -37,10 +37,11 @@ def test_plain_backward_matches_finite_differences(act):
          "out_w": rng.normal(0, .6, (h, xd)), "out_b": rng.normal(0, .3, xd)}
     x, state = rng.normal(0, 1, (B, 1, xd)), rng.normal(0, 1, (B, 1, sd))
     t, w = rng.integers(0, 20, B), rng.normal(0, 1, (B, 1, xd))
-    loss = lambda q: float((diffusion_plain_forward(q, x, t, state, act)[0] * w).sum())
-    _, cache = diffusion_plain_forward(p, x, t, state, act)
+    model = O.Model(act=act, head="plain")
+    loss = lambda q: float((O.diffusion_mlp_forward(q, x, t, state, model)[0] * w).sum())
+    _, cache = O.diffusion_mlp_forward(p, x, t, state, model)
     assert min(np.abs(cache["h1"]).min(), np.abs(cache["h2"]).min()) > 1e-3
-    g = diffusion_plain_backward(p, cache, w, xd, act)
+    g = O.diffusion_mlp_backward(p, cache, w, xd, model)
     assert set(g) == set(p)
     errs = {}
     for k, v in p.items():
@@ -56,32 +57,30 @@ def test_plain_backward_matches_finite_differences(act):
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16", "fp16"])
-def test_plain_oracle_moves_the_sampler(plain_oracle, monkeypatch, precision):
-    """O.sample under the fixture against the residual oracle, same weights and draws: actions and chains
+def test_plain_oracle_moves_the_sampler(precision):
+    """O.sample with the plain head against the residual one, same weights and draws: actions and chains
     move by >= 10x the sampler bound."""
-    inp = SS._Inputs(HOPPER, 17, seed=11)
-    plain = inp.oracle(precision)
-    monkeypatch.undo()
-    SS._assert_moved(f"plain-vs-residual-{precision}", precision, plain, inp.oracle(precision))
+    inp = SS._Inputs(HOPPER_PLAIN, 17, seed=11)
+    SS._assert_moved(f"plain-vs-residual-{precision}", precision, inp.oracle(precision), inp.oracle(precision, model=O.Model()))
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-def test_plain_oracle_moves_the_update(plain_oracle, monkeypatch, precision):
-    """get_logprobs, the c_loss gradients per tensor and the pretrain loss under the fixture against the
-    residual oracle on the same problem: >= 10x the bounds of the GPU cases."""
-    p = US._Problem(HOPPER, precision)
+def test_plain_oracle_moves_the_update(precision):
+    """get_logprobs, the c_loss gradients per tensor and the pretrain loss with the plain head against the
+    residual one on the same problem: >= 10x the bounds of the GPU cases."""
+    p = US._Problem(HOPPER_PLAIN, precision)
     lp_p, ref_p = p.lp_ref, p.oracle()
     rng = np.random.default_rng(21)
     rows, d = 40, p.d
     sh = (rows, d.horizon_steps, d.action_dim)
-    pre = lambda: O.p_losses(to_f64(p.ft), p.sched, rng0["x0"], rng0["cond"], rng0["t"], rng0["z"], rnd=US._rnd(precision))
+    pre = lambda model: O.p_losses(to_f64(p.ft), p.sched, rng0["x0"], rng0["cond"], rng0["t"], rng0["z"],
+                                   rnd=US._rnd(precision), model=model)
     rng0 = dict(x0=rng.uniform(-1, 1, sh), cond=rng.uniform(-1, 1, (rows, d.cond_steps, d.obs_dim)),
                 t=rng.integers(0, d.denoising_steps, rows), z=rng.standard_normal(sh))
-    loss_p, _ = pre()
-    monkeypatch.undo()
+    loss_p, _ = pre(p.model)
     lp_r = O.get_logprobs(to_f64(p.ft), p.sched, p.state(p.obs), p.x(p.chains, p.kf + 1), p.kf, rnd=US._rnd(precision))
-    ref_r = p.oracle()
-    loss_r, _ = pre()
+    ref_r = p.oracle(model=O.Model())
+    loss_r, _ = pre(O.Model())
     tol_lp = {"fp32": 1e-3, "bf16": 2e-3}[precision]
     rel = np.abs(lp_p - lp_r) / (1 + np.abs(lp_r))
     moved = {k: US._rel(ref_p[1][k], ref_r[1][k]) for k in ref_p[1]}

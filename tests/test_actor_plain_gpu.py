@@ -1,6 +1,5 @@
-"""Plain-head actor on the GPU: the entries that take a packed actor image, against the plain oracle
-(tests/plain_oracle.py: the oracle's composed functions with diffusion_mlp_forward / _backward wrapped for
-the duration of a test).
+"""Plain-head actor on the GPU: the entries that take a packed actor image, against the oracle's plain head
+(O.Model(head="plain"), derived from the dims).
 
 Bounds are the residual cases' of the same entry and path, unchanged (tests/test_actor_mish_gpu.py lists
 them): the sampler's of tests/test_sampler_surface_gpu.py, test_logprob's, the per-tensor gradient bounds of
@@ -22,7 +21,7 @@ from tests import test_sampler_surface_gpu as SS
 from tests import test_update_regimes_gpu as UR
 from tests import test_update_surface_gpu as US
 from tests.helpers import HOPPER, HOPPER_DDIM, to_f64
-from tests.plain_oracle import HOPPER_PLAIN, PLAIN, WALKER_PLAIN, plain_oracle  # noqa: F401
+from tests.variants import HOPPER_PLAIN, PLAIN, WALKER_PLAIN
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -70,11 +69,10 @@ SAMPLER_CASES = [
 
 
 @pytest.mark.parametrize("label,dims,precision,E,kernel,kw", SAMPLER_CASES, ids=[c[0] for c in SAMPLER_CASES])
-def test_sampler_matches_plain_oracle(cuda, plain_oracle, label, dims, precision, E, kernel, kw):
-    """dppo_sample on plain images, injected noise, against O.sample under the fixture: actions and every
+def test_sampler_matches_plain_oracle(cuda, label, dims, precision, E, kernel, kw):
+    """dppo_sample on plain images, injected noise, against O.sample with the plain head: actions and every
     stored chain row; the plan is the residual plan of the same shape."""
     from diffusionpolicyoptimization_amd import ops
-    plain_oracle.act = dims.get("activation", "ReLU")
     inp = SS._Inputs(dims, E, seed=11)
     g = SS._Gpu(inp, precision, cuda)
     res_dims = {k: v for k, v in dims.items() if k not in ("activation", "head")}
@@ -89,10 +87,9 @@ KF_EDGES = [("hopper", HOPPER_PLAIN, "bf16", 513, 20), ("hopper", HOPPER_PLAIN_M
 
 @pytest.mark.parametrize("name,dims,precision,E,kf", KF_EDGES,
                          ids=[f"{n}{'-mish' if 'activation' in d else ''}-{p}-E{e}-kf{k}" for n, d, p, e, k in KF_EDGES])
-def test_streaming_kf_edges_plain(cuda, plain_oracle, name, dims, precision, E, kf):
+def test_streaming_kf_edges_plain(cuda, name, dims, precision, E, kf):
     """The streaming kernel's plain instantiation at K' = K (chain row 0 = x_T from the draw loop, no actor
     switch) and K' = 1 (the resident set reloaded before the last step): test_streaming_kf_edges on plain images."""
-    plain_oracle.act = dims.get("activation", "ReLU")
     inp = SS._Inputs(dict(dims, ft_denoising_steps=kf), E, seed=1000 * kf + E)
     g = SS._Gpu(inp, precision, cuda)
     assert g.plan["kernel"] == STREAM, g.plan
@@ -104,7 +101,7 @@ def test_streaming_kf_edges_plain(cuda, plain_oracle, name, dims, precision, E, 
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-def test_sample_step_equals_sample_plain(cuda, plain_oracle, precision):
+def test_sample_step_equals_sample_plain(cuda, precision):
     """dppo_sample_step on plain images at 16 envs through mapped staging memory: bit-equal to dppo_sample on
     the same Philox stream, and within the sampler's bound of the plain oracle."""
     import torch
@@ -205,7 +202,7 @@ def test_sampler_refuses_mixed_heads(cuda, precision, E):
 # dppo_logprob, dppo_ppo_minibatch, dppo_pretrain_minibatch
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("precision,tol", [("fp32", 1e-3), ("bf16", 2e-3)])
-def test_logprob_matches_plain_oracle(cuda, plain_oracle, precision, tol):
+def test_logprob_matches_plain_oracle(cuda, precision, tol):
     """dppo_logprob on a plain image at n = 5 samples (50 rows: a partial 32-row tile)."""
     import torch
     from diffusionpolicyoptimization_amd import ops
@@ -214,7 +211,8 @@ def test_logprob_matches_plain_oracle(cuda, plain_oracle, precision, tol):
     rng = np.random.default_rng(4)
     state = rng.uniform(-1, 1, (n, 1, d.obs_dim)).astype(np.float32)
     chains = (rng.standard_normal((n, kf + 1, d.horizon_steps, d.action_dim)) * 0.5).astype(np.float32)
-    ref = O.get_logprobs(to_f64(ft), sched, state.astype(np.float64), chains.astype(np.float64), kf, rnd=KG._rnd(precision))
+    ref = O.get_logprobs(to_f64(ft), sched, state.astype(np.float64), chains.astype(np.float64), kf, rnd=KG._rnd(precision),
+                         model=O.Model.from_dims(d))
     lpe, lpm = ops.logprob(d, precision, ops.pack_actor(d, pf, precision), tab, torch.tensor(state.reshape(n, -1), device=cuda),
                            torch.tensor(chains.reshape(n, kf + 1, -1), device=cuda))
     torch.cuda.synchronize()
@@ -234,11 +232,10 @@ GRAD_CASES = [("fp32", HOPPER_PLAIN, 96, False), ("fp32", HOPPER_PLAIN, 100, Fal
 @pytest.mark.parametrize("precision,dims,rows,deferred", GRAD_CASES,
                          ids=[f"{p}-{'walker' if d is WALKER_PLAIN else 'hopper'}{'-mish' if 'activation' in d else ''}-r{r}"
                               f"{'-l2def' if q else ''}" for p, d, r, q in GRAD_CASES])
-def test_ppo_minibatch_grads_match_plain_oracle(cuda, plain_oracle, precision, dims, rows, deferred):
+def test_ppo_minibatch_grads_match_plain_oracle(cuda, precision, dims, rows, deferred):
     """dppo_ppo_minibatch on a plain image at rows = 96 (whole tiles) and 100 (a tile tail): the loss metrics
-    and every gradient tensor against O.c_loss under the fixture (the regime tests' bounds); the l2 range of
+    and every gradient tensor against O.c_loss with the plain head (the regime tests' bounds); the l2 range of
     grads is exactly zero, also under DPPO_PPO_L2_DEFERRED (nothing to defer: dW_out is written in place)."""
-    plain_oracle.act = dims.get("activation", "ReLU")
     case = UR._Case(cuda, precision, dims, -(-(UR.START + rows) // 10) + 20)
     stats, mean_std = case.adv_stats(rows)
     met_ref, ga_ref, gc_ref = case.oracle(rows, adv_mean_std=mean_std)
@@ -268,7 +265,7 @@ FT_CASES = [("fp32", 1), ("bf16", 1), ("fp32", 17), ("bf16", 17)]
 
 
 @pytest.mark.parametrize("precision,kf", FT_CASES, ids=[f"{p}-kf{k}" for p, k in FT_CASES])
-def test_ppo_minibatch_ft_steps_plain(cuda, plain_oracle, precision, kf):
+def test_ppo_minibatch_ft_steps_plain(cuda, precision, kf):
     """dppo_ppo_minibatch on a plain image at K' = 1 (one bucket) and K' = 17 (bucket 16 alone in the dW's
     second wave row, tests/test_update_ft_steps_gpu.py): 150 rows, every gradient tensor. As in that file and in
     test_update_surface_gpu's ft1 line, fp32 takes perturbed old log-probs (rows on both clip branches; at
@@ -281,7 +278,7 @@ def test_ppo_minibatch_ft_steps_plain(cuda, plain_oracle, precision, kf):
     _grads_vs_oracle(case, 150, f"plain-{precision}-kf{kf}", ratio1=not f32)
 
 
-def test_ppo_minibatch_learn_eta_ddim_plain(cuda, plain_oracle):
+def test_ppo_minibatch_learn_eta_ddim_plain(cuda):
     """DPPO_PPO_LEARN_ETA behind a plain forward (hopper DDIM, bf16, eta 0.6): metrics[8] against the oracle at
     the 64-row tile test's d_eta bound (3e-2 relative), and every gradient tensor."""
     rows = US.ROWS
@@ -292,7 +289,7 @@ def test_ppo_minibatch_learn_eta_ddim_plain(cuda, plain_oracle):
     assert abs(ref) > 1e-3 and abs(m[8] - ref) <= 3e-2 * abs(ref), (m[8], ref)
 
 
-def test_ppo_minibatch_parts_match_whole_plain(cuda, plain_oracle):
+def test_ppo_minibatch_parts_match_whole_plain(cuda):
     """dppo_ppo_minibatch_part on a plain image as actor row tiles (4), actor dW (5) and critic (2), bf16, 150
     rows: the parts against the oracle and against the whole call within test_ft20_parts_match_whole's bounds
     (median 1e-6, max 5e-3 absolute; metrics 1e-3 relative); the l2 range exactly zero on both."""
@@ -317,7 +314,7 @@ def test_ppo_minibatch_parts_match_whole_plain(cuda, plain_oracle):
         assert abs(mp[slot] - mw[slot]) <= 1e-3 * (abs(mw[slot]) + 1e-3), (slot, mp[slot], mw[slot])
 
 
-def test_ppo_minibatch_multichunk_dw_plain(cuda, plain_oracle):
+def test_ppo_minibatch_multichunk_dw_plain(cuda):
     """1,600 rows, fp32 (test_multichunk_dw_grads_match_oracle's size): two actor dW m-chunks on 32-row tiles,
     both adding u2^T dy into W_out's own gradient range."""
     from diffusionpolicyoptimization_amd import ops
@@ -329,7 +326,7 @@ def test_ppo_minibatch_multichunk_dw_plain(cuda, plain_oracle):
 
 
 @pytest.mark.parametrize("deferred", [False, True], ids=["whole", "l2def"])
-def test_ppo_minibatch_tile64_plain(cuda, plain_oracle, deferred):
+def test_ppo_minibatch_tile64_plain(cuda, deferred):
     """64 (C - 1) + 1 rows, C the CU count, bf16 ReLU: the smallest row count at which ops.ppo_plan reports the
     64-row tile (asserted: 64 rows fewer give the 32-row tile) with more than one dW m-chunk
     (test_actor_tile64_grads_match_oracle's R1); also under DPPO_PPO_L2_DEFERRED."""
@@ -343,9 +340,9 @@ def test_ppo_minibatch_tile64_plain(cuda, plain_oracle, deferred):
 
 
 @pytest.mark.parametrize("precision,rtol", [("fp32", 2e-3), ("bf16", 1e-2)])
-def test_pretrain_matches_plain_oracle(cuda, plain_oracle, precision, rtol):
+def test_pretrain_matches_plain_oracle(cuda, precision, rtol):
     """dppo_pretrain_minibatch on a plain image at 40 rows: loss and every actor gradient against O.p_losses
-    under the fixture (test_pretrain_loss_grads' bounds); the l2 range is exactly zero."""
+    with the plain head (test_pretrain_loss_grads' bounds); the l2 range is exactly zero."""
     import torch
     from diffusionpolicyoptimization_amd import ops
     d, _, ft, _, sched, tab, _, pf, _ = KG._setup(HOPPER_PLAIN, cuda)
@@ -358,7 +355,7 @@ def test_pretrain_matches_plain_oracle(cuda, plain_oracle, precision, rtol):
     sh = (rows, d.horizon_steps, d.action_dim)
     loss_ref, g_ref = O.p_losses(to_f64(ft), sched, x0.reshape(sh).astype(np.float64),
                                  cond.reshape(rows, d.cond_steps, d.obs_dim).astype(np.float64), t,
-                                 noise.reshape(sh).astype(np.float64), rnd=KG._rnd(precision))
+                                 noise.reshape(sh).astype(np.float64), rnd=KG._rnd(precision), model=O.Model.from_dims(d))
     T = lambda x: torch.tensor(x, device=cuda)
     grads = torch.full((ops.spec_count(ops.actor_param_spec(d)),), 7.0, dtype=torch.float32, device=cuda)
     metrics = torch.zeros(16, dtype=torch.float64, device=cuda)
@@ -521,9 +518,9 @@ def test_update_geometry_refusals_plain(cuda, geometry, precision):
 # ------------------------------------------------------------------------------------------------
 # agents
 # ------------------------------------------------------------------------------------------------
-def test_plain_iteration_matches_oracle(cuda, plain_oracle, tmp_path, monkeypatch):
+def test_plain_iteration_matches_oracle(cuda, tmp_path, monkeypatch):
     """An eval and a training iteration of the fp32 agent from ft_ppo_diffusion_mlp_plain.yaml (seed 42, the
-    shapes of tests/test_iteration_gpu.py) against oracle/iteration.py under the fixture, at that file's
+    shapes of tests/test_iteration_gpu.py) against oracle/iteration.py with the plain head, at that file's
     bounds: chains, rewards and returns of both; values, old log-probs, advantages, returns, the last
     minibatch's losses, the number of applied minibatches and the parameter change of the training one. The
     oracle's flat parameters are the plain spec's tensors back to back; the agent's are gathered from the

@@ -9,7 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import adv_clip_oracle as AO
+from oracle import dppo_oracle as O
+from tests import adv_clip_cases as AO
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("dppo_ppo_adv_quantiles_workspace_bytes", "dppo_ppo_adv_quantiles_all", "dppo_ppo_adv_quantiles_count",
@@ -100,9 +101,9 @@ def test_numpy_passes_equal_numpy_quantile(kind):
         for q_lo, q_hi in AO.select_quantiles(n):
             sel, got = AO.radix_select(vals, q_lo, q_hi)
             for i, q in enumerate((q_lo, q_hi)):
-                _, k, k1, vk, vk1 = AO.order_stats(vals, q)
+                _, k, k1, vk, vk1 = O.order_stats(vals, q)
                 assert sel[2 * i] == vk and sel[2 * i + 1] == vk1
-                assert got[i] == AO.quantile(vals, q) or (q * (n - 1)) % 1 == 0
+                assert got[i] == O.quantile(vals, q) or (q * (n - 1)) % 1 == 0
                 ref = np.quantile(vals.astype(np.float64), q)
                 assert abs(got[i] - ref) <= 4 * eps * ((q * (n - 1) + 1) * abs(vk1 - vk) + abs(ref)), (kind, n, q, got[i], ref)
 
@@ -112,20 +113,18 @@ def test_the_clip_moves_what_the_gpu_cases_compare(label, precision, rows, norm_
     """On each GPU gradient case's inputs the oracle at quantiles (0.1, 0.9) and at (0, 1) differ in pg_loss and
     in every actor gradient tensor by at least ten times the bound the GPU case asserts; at least a tenth of
     the rows are clamped on each side; no advantage lies within 1e-6 (relative) of a bound, so the fp32 clamp
-    and the float64 one pick the same rows. (0, 1) through the wrapper is the unwrapped oracle."""
+    and the float64 one pick the same rows. Quantiles (0, 1) are the oracle without the clip."""
     from tests.test_update_surface_gpu import TOL, _assert_moved
     p = AO.grad_problem(precision, rows, norm_adv)
     tol, ratio1 = TOL[precision], p.kind == "ratio1"
     ref0 = p.oracle(norm_adv=norm_adv)
-    with AO.adv_clip_oracle(0.0, 1.0):
-        same = p.oracle(norm_adv=norm_adv)
+    same = p.oracle(norm_adv=norm_adv, adv_clip_quantiles=(0.0, 1.0))
     assert same[0] == ref0[0] and all(np.array_equal(same[1][k], ref0[1][k]) for k in ref0[1])
-    with AO.adv_clip_oracle(*AO.GRAD_Q):
-        ref = p.oracle(norm_adv=norm_adv)
+    ref = p.oracle(norm_adv=norm_adv, adv_clip_quantiles=AO.GRAD_Q)
     _assert_moved(ref, ref0, ("pg_loss", "actor"), tol, ratio1, label=label)
     assert ref[0]["v_loss"] == ref0[0]["v_loss"] and all(np.array_equal(ref[2][k], ref0[2][k]) for k in ref0[2])
     a = p.adv[p.bi].astype(np.float64)
-    lo, hi = AO.bounds(a, *AO.GRAD_Q)
+    lo, hi = O.bounds(a, *AO.GRAD_Q)
     below, above = float((a < lo).mean()), float((a > hi).mean())
     gap = float(min(np.abs(a - lo).min() / abs(lo), np.abs(a - hi).min() / abs(hi)))
     print(json.dumps({"case": label, "clamped_below": below, "clamped_above": above, "nearest_rel_gap": gap,

@@ -1,6 +1,6 @@
 """PPODiffusion's advantage clip on the device: the per-minibatch quantile select (csrc/select.hip), the
-DPPO_PPO_ADV_CLIP row tiles and the agent, against tests/adv_clip_oracle.py (the float64 definition and the
-oracle's c_loss with the normalisation step replaced). Every figure is printed before it is asserted.
+DPPO_PPO_ADV_CLIP row tiles and the agent, against the oracle's float64 definition (O.quantile, O.bounds) and its
+c_loss with adv_clip_quantiles. Every figure is printed before it is asserted.
 
 Bounds. The select: the four fp32 order statistics of every segment exact (bit patterns, +-0 as values); the
 fp64 interpolation within 4 ulps of float64, relative (the device evaluates the definition's own operations
@@ -15,10 +15,9 @@ import os
 import numpy as np
 import pytest
 
+from oracle import dppo_oracle as O
 from oracle import philox as PX
-from tests import adv_clip_oracle as AO
-from tests.mish_oracle import mish_oracle  # noqa: F401  (fixtures of the Mish and the plain-head cases)
-from tests.plain_oracle import plain_oracle  # noqa: F401
+from tests import adv_clip_cases as AO
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,9 +60,9 @@ def _check_segment(label, vals, q_lo, q_hi, got, sel, worst):
         assert got[0] == -np.inf and got[1] == np.inf, (label, got)
         return
     for i, q in enumerate((q_lo, q_hi)):
-        n, k, k1, vk, vk1 = AO.order_stats(vals, q)
+        n, k, k1, vk, vk1 = O.order_stats(vals, q)
         assert sel[2 * i] == vk and sel[2 * i + 1] == vk1, (label, q, sel, vk, vk1)   # exact order statistics
-        ref = AO.quantile(vals, q)
+        ref = O.quantile(vals, q)
         err = abs(got[i] - ref) / max(abs(ref), np.finfo(np.float64).tiny)
         worst[0] = max(worst[0], err / EPS)
         assert err <= 4 * EPS, (label, q, got[i], ref)
@@ -131,7 +130,7 @@ def test_select_pass_pair_sums_over_two_halves(cuda):
     for out in outs:
         assert np.array_equal(out.cpu().numpy(), whole), (out, whole)
     for m in range(ne):   # and the whole is the definition on all 1800 rows: every sample three times
-        ref = AO.bounds(np.repeat(adv, kf), *q)
+        ref = O.bounds(np.repeat(adv, kf), *q)
         assert np.allclose(whole[m], ref, rtol=4 * EPS, atol=0), (whole[m], ref)
 
 
@@ -228,15 +227,14 @@ def _return_cached_blocks():
 @pytest.mark.parametrize("label,precision,rows,norm_adv", AO.GRAD_CASES, ids=[c[0] for c in AO.GRAD_CASES])
 def test_flagged_minibatch_matches_oracle(cuda, label, precision, rows, norm_adv):
     """Quantiles (0.1, 0.9): the bounds from the device select, the clamp in the actor's row tiles, every
-    gradient tensor and metric against O.c_loss with the normalisation step replaced."""
+    gradient tensor and metric against O.c_loss(adv_clip_quantiles=(0.1, 0.9))."""
     from tests.test_update_surface_gpu import TOL, _compare
     r = _run(cuda, precision, rows, norm_adv)
     p = r.p
     lo_hi = r.table[3:].cpu().numpy()
-    ref_b = AO.bounds(p.adv[p.bi], *AO.GRAD_Q)
+    ref_b = O.bounds(p.adv[p.bi], *AO.GRAD_Q)
     assert np.allclose(lo_hi, ref_b, rtol=4 * EPS, atol=0), (lo_hi, ref_b)
-    with AO.adv_clip_oracle(*AO.GRAD_Q):
-        ref = p.oracle(norm_adv=norm_adv)
+    ref = p.oracle(norm_adv=norm_adv, adv_clip_quantiles=AO.GRAD_Q)
     grads, metrics = r.minibatch(r.table, True, norm_adv)
     _compare(f"adv-clip-{label}", r.g, metrics.cpu().numpy(), grads.cpu().numpy(), ref, TOL[precision], denom=rows)
 
@@ -305,13 +303,13 @@ TILE_CASES = [("relu-fp16-150", "fp16", "relu", 150, 32, False),
 
 
 @pytest.mark.parametrize("label,precision,kind,size,tile,learn_eta", TILE_CASES, ids=[c[0] for c in TILE_CASES])
-def test_flagged_minibatch_tiles_actors_and_eta(cuda, request, monkeypatch, label, precision, kind, size, tile, learn_eta):
+def test_flagged_minibatch_tiles_actors_and_eta(cuda, monkeypatch, label, precision, kind, size, tile, learn_eta):
     """The flag through the other instantiations of the actor's TRAIN tile, on tests/test_update_regimes_gpu.py's
     _Case (permutation rows from START, ratio 1): fp16; the 64-row, 16-wave tile at its smallest row count and the
     32-row tile one row past a round of C tiles (ops.ppo_plan proves which ran; the bounds reach the epilogue
     through thread ROWS and the tile's own LDS slots); a Mish actor; a plain head; the learnable-eta derivative
     under DDIM (metrics[8], eta 0.6, the unflagged cases' 3e-2). Quantiles (0.1, 0.9) from the device select over
-    the rows, metrics and every gradient tensor against the wrapped oracle at the mirrored cases' bounds.
+    the rows, metrics and every gradient tensor against the oracle with the same quantiles at the mirrored cases' bounds.
 
     The two large cases are bf16, as every large-minibatch case of the suite is (tests/test_update_regimes_gpu.py
     runs fp32 up to 1,600 rows): there the oracle rounds where the kernels round, so both sides take the same ReLU
@@ -326,13 +324,11 @@ def test_flagged_minibatch_tiles_actors_and_eta(cuda, request, monkeypatch, labe
     from tests.helpers import HOPPER, HOPPER_DDIM
     dims = dict(relu=HOPPER, ddim=HOPPER_DDIM)
     if kind == "mish":
-        from tests.mish_oracle import HOPPER_MISH, mish_models
-        request.getfixturevalue("mish_oracle")
+        from tests.variants import HOPPER_MISH, mish_models
         monkeypatch.setattr(KG, "make_models", mish_models)
         dims["mish"] = HOPPER_MISH
     if kind == "plain":
-        from tests.plain_oracle import HOPPER_PLAIN
-        request.getfixturevalue("plain_oracle").act = "ReLU"
+        from tests.variants import HOPPER_PLAIN
         dims["plain"] = HOPPER_PLAIN
     C = UR._cus(cuda)
     rows = {"R64": 64 * (C - 1) + 1, "R32": 32 * C + 1}.get(size, size)
@@ -345,11 +341,10 @@ def test_flagged_minibatch_tiles_actors_and_eta(cuda, request, monkeypatch, labe
     table = torch.zeros(5, dtype=torch.float64, device=cuda)
     table[:3] = stats
     ops.ppo_adv_quantiles_all(case.T(rows_adv), rows, 1, 5, 0, 1, rows, 1, *AO.GRAD_Q, table[3:].view(1, 2))
-    lo, hi = AO.bounds(rows_adv, *AO.GRAD_Q)
+    lo, hi = O.bounds(rows_adv, *AO.GRAD_Q)
     assert np.allclose(table[3:].cpu().numpy(), (lo, hi), rtol=4 * EPS, atol=0)
     assert (rows_adv < lo).mean() >= 0.05 and (rows_adv > hi).mean() >= 0.05   # the clamp has rows to act on
-    with AO.adv_clip_oracle(*AO.GRAD_Q):
-        met_ref, ga_ref, gc_ref = case.oracle(rows, adv_mean_std=mean_std, eta_grad=learn_eta)
+    met_ref, ga_ref, gc_ref = case.oracle(rows, adv_mean_std=mean_std, eta_grad=learn_eta, adv_clip_quantiles=AO.GRAD_Q)
     hp = ops.ppo_hparams(global_rows=rows, learn_eta=learn_eta, adv_clip=True)
     grads = torch.zeros(case.na + case.nc, dtype=torch.float32, device=cuda)
     met = torch.zeros(16, dtype=torch.float64, device=cuda)
@@ -413,7 +408,7 @@ def test_pass_pair_refusals(cuda):
 # ------------------------------------------------------------------------------------------------
 def test_advclip_iterations_match_oracle(cuda, tmp_path, monkeypatch):
     """An eval and two training iterations of the fp32 agent from ft_ppo_diffusion_mlp_advclip.yaml (seed 42, the
-    shapes and bounds of tests/test_iteration_gpu.py) against oracle/iteration.py with c_loss wrapped."""
+    shapes and bounds of tests/test_iteration_gpu.py) against oracle/iteration.py with the model's quantiles."""
     from diffusionpolicyoptimization_amd.util import config
     from tests import test_iteration_gpu as IT
     load = config.load_config
@@ -421,8 +416,8 @@ def test_advclip_iterations_match_oracle(cuda, tmp_path, monkeypatch):
     a, orc = IT._agent_and_oracle(42, tmp_path)
     m = a.model
     assert (m.clip_advantage_lower_quantile, m.clip_advantage_upper_quantile) == (0.05, 0.95) and m.adv_clip
-    with AO.adv_clip_oracle(0.05, 0.95):
-        errs = IT._run_and_compare(a, orc, n_itr=3)
+    assert orc.closs_kw["adv_clip_quantiles"] == (0.05, 0.95)
+    errs = IT._run_and_compare(a, orc, n_itr=3)
     print(json.dumps({"case": "adv-clip-iteration", "iterations": errs}))
     assert [e["eval"] for e in errs] == [True, False, False]
     tab = a._adv_clip.cpu().numpy()
@@ -525,7 +520,7 @@ def test_data_parallel_clip_equals_single_rank_on_the_union(cuda, tmp_path):
                 torch.cuda.synchronize()
                 if (e, b) == (0, 0):
                     got.update(grads=m.grads.cpu().numpy().copy(), metrics=m.metrics[:5].cpu().numpy().copy(),
-                               tab=tab.cpu().numpy(), ref=AO.bounds(rows_adv.cpu().numpy(), 0.05, 0.95))
+                               tab=tab.cpu().numpy(), ref=O.bounds(rows_adv.cpu().numpy(), 0.05, 0.95))
                 tabs.append(tab.cpu().numpy())
                 opt.apply_range(m.grads, 0, ng, opt.begin_step(), m.dims, m.precision, packs=packs)
         torch.cuda.synchronize()

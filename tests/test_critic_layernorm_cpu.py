@@ -1,11 +1,11 @@
-"""Layer-normed critic (CriticObs use_layernorm=True, both heads), the CPU half: the wrapped oracle
-(tests/layernorm_critic_oracle.py) is right (finite differences, gamma / beta included); turning the norm on, or
+"""Layer-normed critic (CriticObs use_layernorm=True, both heads), the CPU half: the oracle's layer-normed critic
+(O.Model(critic_layernorm=True)) is right (finite differences, gamma / beta included); turning the norm on, or
 using the other head's epsilon, moves what the GPU file compares by at least ten times its bound; the Python
 containers carry the tail without moving an existing offset; the C ABI carries the new symbols within ABI 15;
 checkpoints round-trip and do not cross layouts; the two new cfgs load and resolve.
 
 The GPU file's bounds are those of tests/test_critic_plain_gpu.py (V: 1e-4 / 1e-3 / 1e-3 of 1 + max|V|; gradients per
-tensor: 2e-3 fp32, 1e-2 2-byte). The arithmetic they are held against, which `ln_critic_forward` / `_backward` state
+tensor: 2e-3 fp32, 1e-2 2-byte). The arithmetic they are held against, which O.ln_critic_forward / _backward state
 with `rnd` at the kernel's rounding points: the row statistics (mean, then the mean of squared deviations) and
 x_hat, y = gamma x_hat + beta, dy, dgamma, dbeta in the accumulators' precision, never rounded; only u_k = mish(y_k)
 and the gradient images dh_k are rounded to the 2-byte type, as the operands of the next product."""
@@ -20,8 +20,7 @@ import pytest
 from oracle import dppo_oracle as O
 from tests import test_update_surface_gpu as US
 from tests.helpers import HOPPER, make_models, to_f64
-from tests.layernorm_critic_oracle import (EPS, HOPPER_LN, add_ln_params, layernorm_critic_oracle,  # noqa: F401
-                                           ln_critic_backward, ln_critic_forward)
+from tests.variants import HOPPER_LN, add_ln_params
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG_DIR = os.path.join(ROOT, "cfg/gym/finetune/hopper-v2")
@@ -34,7 +33,7 @@ def ln_models(seed=0, dims=HOPPER, in_scale=3.0, **kw):
     """tests.helpers.make_models with the critic the layer-norm tests use: for dims with critic_layernorm, W_in
     times in_scale (hidden rows of variance >= 100 epsilon at the first site too, asserted where used) and random
     norms, gamma ~ U(0.5, 1.5), beta ~ N(0, 1). The GPU file patches this in for the shared case classes."""
-    base, ft, critic = make_models(seed, {k: v for k, v in dims.items() if k not in ("critic_head", "critic_layernorm")}, **kw)
+    base, ft, critic = make_models(seed, dims, **kw)
     if dims.get("critic_layernorm"):
         critic = dict(critic, in_w=(critic["in_w"] * np.float32(in_scale)).astype(np.float32))
         critic = add_ln_params(critic, dims.get("critic_head", "residual"), np.random.default_rng(77 + seed))
@@ -54,7 +53,7 @@ def states77():
 
 def assert_variance(cache, head, factor=100.0):
     worst = min(float(v.min()) for v in cache["var"])
-    assert worst >= factor * EPS[head], (head, worst)
+    assert worst >= factor * O.LN_EPS[head], (head, worst)
     return worst
 
 
@@ -74,10 +73,11 @@ def test_ln_critic_backward_matches_finite_differences(head):
     for k in range(1, (3 if head == "plain" else 2) + 1):
         p[f"ln{k}_g"], p[f"ln{k}_b"] = rng.uniform(0.5, 1.5, h), rng.normal(0, 1, h)
     state, w = rng.normal(0, 1, (B, 1, sd)), rng.normal(0, 1, (B, 1))
-    loss = lambda q: float((ln_critic_forward(q, state)[0] * w).sum())
-    _, cache = ln_critic_forward(p, state)
-    assert cache["ln_critic"] == head
-    g, _ = ln_critic_backward(p, cache, w)
+    model = O.Model(critic_head=head, critic_layernorm=True)
+    loss = lambda q: float((O.critic_forward(q, state, model)[0] * w).sum())
+    _, cache = O.critic_forward(p, state, model)
+    assert ("u3" in cache) == (head == "plain")          # a third normed site only under the plain head
+    g, _ = O.critic_backward(p, cache, w, model)
     assert set(g) == set(p)
     errs = {}
     for k, v in p.items():
@@ -92,19 +92,18 @@ def test_ln_critic_backward_matches_finite_differences(head):
     assert all(e < 1e-6 for e in errs.values()), errs
 
 
-def test_layer_norm_is_keras(layernorm_critic_oracle):
+def test_layer_norm_is_keras():
     """Population variance over the last axis, epsilon inside the square root; gamma = 1, beta = 0 gives rows of mean
     0 and variance var / (var + eps)."""
-    from tests.layernorm_critic_oracle import layer_norm
     h = np.random.default_rng(0).normal(2.0, 3.0, (4, 16))
-    y, xh, rstd, var = layer_norm(h, np.ones(16), np.zeros(16), 1e-3)
+    y, xh, rstd, var = O.layer_norm(h, np.ones(16), np.zeros(16), 1e-3)
     assert np.allclose(var[:, 0], h.var(-1)) and np.allclose(y.mean(-1), 0, atol=1e-12)
     assert np.allclose(y.var(-1), h.var(-1) / (h.var(-1) + 1e-3))
 
 
 @pytest.mark.parametrize("head", HEADS)
 @pytest.mark.parametrize("precision", ["fp32", "bf16", "fp16"])
-def test_layer_norm_moves_values_and_gradients(layernorm_critic_oracle, monkeypatch, precision, head):
+def test_layer_norm_moves_values_and_gradients(monkeypatch, precision, head):
     """On the GPU tests' inputs (77 states; the 150-row minibatch problem of tests/test_update_surface_gpu.py with
     ln_models' critic) the layer-normed oracle and the oracle of the same eight tensors without the norm differ in V
     and in every critic gradient tensor by at least ten times that quantity's bound, so a GPU run that skips the
@@ -113,22 +112,15 @@ def test_layer_norm_moves_values_and_gradients(layernorm_critic_oracle, monkeypa
     rnd = US._rnd(precision)
     p = US._Problem(HOPPER_LN[head], precision)
     critic = to_f64(p.critic)
-    v_ln, cache = O.critic_forward(critic, states77(), rnd=rnd)
+    v_ln, cache = O.critic_forward(critic, states77(), p.model, rnd=rnd)
     worst = assert_variance(cache, head)
-    assert_variance(O.critic_forward(critic, p.state(p.obs[p.bi]), rnd=rnd)[1], head)
+    assert_variance(O.critic_forward(critic, p.state(p.obs[p.bi]), p.model, rnd=rnd)[1], head)
     _, _, gc_ln = p.oracle()
-    monkeypatch.undo()
-    plain_head = head == "plain"
-    if plain_head:
-        from tests.plain_critic_oracle import plain_critic_backward, plain_critic_forward
-        orig = O.residual_mlp_backward
-        monkeypatch.setattr(O, "critic_forward", plain_critic_forward)
-        monkeypatch.setattr(O, "residual_mlp_backward", lambda q, c, dy, act, prefix: plain_critic_backward(q, c, dy, act)
-                            if c.get("plain_critic") else orig(q, c, dy, act, prefix))
+    off = O.Model(critic_head=head)                  # the same head without the norm
     eight = {k: critic[k] for k in EIGHT}
-    v_off = O.critic_forward(eight, states77(), rnd=rnd)[0]
+    v_off = O.critic_forward(eight, states77(), off, rnd=rnd)[0]
     p.critic = eight
-    _, _, gc_off = p.oracle()
+    _, _, gc_off = p.oracle(model=off)
     dv = float(np.abs(v_ln - v_off).max())
     moved = {k: US._rel(gc_ln[k], gc_off[k]) for k in EIGHT}
     print(json.dumps({"case": f"ln-on-vs-off-{head}-{precision}", "dV": dv, "grads": moved, "min_var": worst}))
@@ -145,11 +137,12 @@ def test_wrong_epsilon_moves_the_values(precision, head):
     head's epsilon cannot pass the GPU file's forward case on these inputs."""
     rnd = US._rnd(precision)
     critic = to_f64(near_eps_critic(head))
-    v, cache = ln_critic_forward(critic, states77(), rnd=rnd)
+    model = O.Model(critic_head=head, critic_layernorm=True)
+    v, cache = O.critic_forward(critic, states77(), model, rnd=rnd)
     var1 = cache["var"][0]
     assert 0.2e-3 <= float(var1.min()) and float(var1.max()) <= 5e-3, (float(var1.min()), float(var1.max()))
-    other = EPS["residual" if head == "plain" else "plain"]
-    v_wrong, _ = ln_critic_forward(critic, states77(), rnd=rnd, eps=other)
+    other = O.LN_EPS["residual" if head == "plain" else "plain"]
+    v_wrong, _ = O.critic_forward(critic, states77(), model, rnd=rnd, ln_eps=other)
     dv = float(np.abs(v - v_wrong).max() / (1 + np.abs(v).max()))
     print(json.dumps({"case": f"ln-wrong-eps-{head}-{precision}", "dV": dv, "bound": V_TOL[precision]}))
     assert dv >= 10 * V_TOL[precision]

@@ -1,5 +1,5 @@
-"""Layer-normed critic on the GPU: the entries that take a packed critic image, against the layer-norm oracle
-(tests/layernorm_critic_oracle.py: O.critic_forward and O.residual_mlp_backward replaced for the duration of a test).
+"""Layer-normed critic on the GPU: the entries that take a packed critic image, against the oracle's layer-normed
+critic (O.Model(critic_head=..., critic_layernorm=True), derived from the dims).
 
 Hopper dims (SD = 11, HC = 256) at fp32, bf16 and fp16, both heads. The critic is tests/test_critic_layernorm_cpu.py's
 ln_models: random gamma ~ U(0.5, 1.5), beta ~ N(0, 1), W_in times 3, so that every hidden row's variance is at least
@@ -23,7 +23,7 @@ from tests import test_update_ft_steps_gpu as FT
 from tests import test_update_regimes_gpu as UR
 from tests import test_update_surface_gpu as US
 from tests.helpers import HOPPER, to_f64
-from tests.layernorm_critic_oracle import EPS, HOPPER_LN, layernorm_critic_oracle, ln_critic_forward  # noqa: F401
+from tests.variants import HOPPER_LN
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,11 +34,10 @@ LN_NAMES = {"residual": ["ln1_g", "ln1_b", "ln2_g", "ln2_b"], "plain": ["ln1_g",
 
 
 @pytest.fixture
-def ln(layernorm_critic_oracle, monkeypatch):
-    """The layer-norm oracle, and ln_models in place of make_models for the shared case classes."""
+def ln(monkeypatch):
+    """ln_models in place of make_models for the shared case classes."""
     for mod in (KG, US):
         monkeypatch.setattr(mod, "make_models", LC.ln_models)
-    return layernorm_critic_oracle
 
 
 def _lp(precision):
@@ -62,7 +61,7 @@ def _forward_err(d, precision, img, critic, state, cuda, head=None, min_var=100.
     import torch
     from diffusionpolicyoptimization_amd import ops
     n = state.shape[0]
-    ref, cache = ln_critic_forward(to_f64(critic), state.astype(np.float64), rnd=KG._rnd(precision))
+    ref, cache = O.critic_forward(to_f64(critic), state.astype(np.float64), O.Model.from_dims(d), rnd=KG._rnd(precision))
     if head is not None:
         LC.assert_variance(cache, head, min_var)
     buf = torch.full((n + 1,), 7.5, dtype=torch.float32, device=cuda)
@@ -127,8 +126,8 @@ def _index(case, rows):
 
 
 def _assert_rows_variance(case, head, bi):
-    _, cache = ln_critic_forward(to_f64(case.critic), case.obs[np.unique(bi)].reshape(-1, 1, 11).astype(np.float64),
-                                 rnd=KG._rnd(case.precision))
+    _, cache = O.critic_forward(to_f64(case.critic), case.obs[np.unique(bi)].reshape(-1, 1, 11).astype(np.float64),
+                                case.model, rnd=KG._rnd(case.precision))
     return LC.assert_variance(cache, head)
 
 
@@ -142,7 +141,7 @@ GRAD_CASES = [(p, h, r) for r in ("r77-index", "r100", "r1600") for h in HEADS f
 @pytest.mark.parametrize("precision,head,regime", GRAD_CASES, ids=[f"{p}-{h}-{r}" for p, h, r in GRAD_CASES])
 def test_ppo_minibatch_critic_grads_match_ln_oracle(cuda, ln, precision, head, regime):
     """One whole dppo_ppo_minibatch with a layer-normed critic image: the value loss and every critic gradient
-    tensor, ln*_g / ln*_b included, against O.c_loss under the fixture.
+    tensor, ln*_g / ln*_b included, against O.c_loss with the layer-normed critic.
       r77-index:  77 rows (a partial third tile: padded rows) through an explicit row_index;
       r100:       100 rows over 34 samples: every sample about three times, so the dedup multiplicities run;
       r1600:      1,600 rows over 170 samples: two dW m-chunks on the host's plan, re-cut on the device over the
@@ -334,11 +333,9 @@ def test_attribute_is_reset_by_repacking_and_forgetting(cuda, ln, head):
     eight = {k: critic[k] for k in LC.EIGHT}
 
     def errs():
-        from tests.plain_critic_oracle import plain_critic_forward
-        off_oracle = plain_critic_forward if head == "plain" else (lambda p, s, rnd=None: O.residual_mlp_forward(p, s.reshape(s.shape[0], -1), "Mish", "", rnd))
         v = ops.critic_forward(d, precision, img, torch.tensor(state.reshape(77, -1).astype(np.float32), device=cuda)).cpu().numpy()
-        r_ln = ln_critic_forward(to_f64(critic), state)[0][:, 0]
-        r_off = off_oracle(to_f64(eight), state)[0][:, 0]
+        r_ln = O.critic_forward(to_f64(critic), state, O.Model.from_dims(d))[0][:, 0]
+        r_off = O.critic_forward(to_f64(eight), state, O.Model(critic_head=head))[0][:, 0]
         return (float(np.abs(v - r_ln).max() / (1 + np.abs(r_ln).max())), float(np.abs(v - r_off).max() / (1 + np.abs(r_off).max())))
 
     tol = V_TOL[precision]
@@ -352,9 +349,8 @@ def test_attribute_is_reset_by_repacking_and_forgetting(cuda, ln, head):
     assert errs()[0] < tol
     _lib.call("dppo_forget_image", ptr(img))
     e = errs()
-    residual = lambda p, s: O.residual_mlp_forward(p, s.reshape(s.shape[0], -1), "Mish", "", None)
     v = ops.critic_forward(d, precision, img, torch.tensor(state.reshape(77, -1).astype(np.float32), device=cuda)).cpu().numpy()
-    r = residual(to_f64(eight), state)[0][:, 0]                          # forgotten: RESIDUAL, no layer norm
+    r = O.critic_forward(to_f64(eight), state)[0][:, 0]                       # forgotten: RESIDUAL, no layer norm
     assert float(np.abs(v - r).max() / (1 + np.abs(r).max())) < tol and e[0] >= 10 * tol
     ops.pack_critic(d, pc, precision, out=img)
     assert errs()[0] < tol
@@ -451,9 +447,9 @@ def test_layer_norm_off_is_todays_layout(cuda):
 # agents
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,head", [("_critic_ln", "residual"), ("_plain_critic_ln", "plain")])
-def test_ln_critic_iteration_matches_oracle(cuda, layernorm_critic_oracle, tmp_path, monkeypatch, name, head):
+def test_ln_critic_iteration_matches_oracle(cuda, tmp_path, monkeypatch, name, head):
     """An eval and a training iteration of the fp32 agent from each new cfg (seed 42, the shapes and bounds of
-    tests/test_iteration_gpu.py) against oracle/iteration.py with the critic functions wrapped."""
+    tests/test_iteration_gpu.py) against oracle/iteration.py with the model's critic."""
     from diffusionpolicyoptimization_amd.util import config
     from tests import test_iteration_gpu as IT
     load = config.load_config

@@ -1,5 +1,5 @@
-"""Plain critic (CriticObs residual_style=False, mlp_dims [256, 256, 256]), the CPU half: the plain-critic oracle
-(tests/plain_critic_oracle.py) is right (finite differences) and moves V and every critic gradient tensor the GPU
+"""Plain critic (CriticObs residual_style=False, mlp_dims [256, 256, 256]), the CPU half: the oracle's plain critic
+(O.Model(critic_head="plain")) is right (finite differences) and moves V and every critic gradient tensor the GPU
 file compares by at least ten times that quantity's bound; the Python containers accept exactly the supported
 shape; the C ABI carries the new symbol within ABI 15; checkpoints round-trip and do not cross heads; the two new
 cfgs load and resolve."""
@@ -13,8 +13,9 @@ import pytest
 from oracle import dppo_oracle as O
 from tests import test_update_surface_gpu as US
 from tests.helpers import HOPPER, make_models, to_f64
-from tests.plain_critic_oracle import (HOPPER_PLAIN_CRITIC, plain_critic_backward, plain_critic_forward,  # noqa: F401
-                                       plain_critic_oracle)
+from tests.variants import HOPPER_PLAIN_CRITIC
+
+PLAIN_CRITIC = O.Model(critic_head="plain")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG_DIR = os.path.join(ROOT, "cfg/gym/finetune/hopper-v2")
@@ -33,9 +34,9 @@ def test_plain_critic_backward_matches_finite_differences():
          "l1_b": rng.normal(0, .5, h), "l2_w": rng.normal(0, .6, (h, h)), "l2_b": rng.normal(0, .5, h),
          "out_w": rng.normal(0, .6, (h, 1)), "out_b": rng.normal(0, .3, 1)}
     state, w = rng.normal(0, 1, (B, 1, sd)), rng.normal(0, 1, (B, 1))
-    loss = lambda q: float((plain_critic_forward(q, state)[0] * w).sum())
-    _, cache = plain_critic_forward(p, state)
-    g, _ = plain_critic_backward(p, cache, w)
+    loss = lambda q: float((O.critic_forward(q, state, PLAIN_CRITIC)[0] * w).sum())
+    _, cache = O.critic_forward(p, state, PLAIN_CRITIC)
+    g, _ = O.critic_backward(p, cache, w, PLAIN_CRITIC)
     assert set(g) == set(p)
     errs = {}
     for k, v in p.items():
@@ -50,9 +51,9 @@ def test_plain_critic_backward_matches_finite_differences():
     assert all(e < 1e-6 for e in errs.values()), errs
 
 
-def test_fixture_leaves_the_actor_backward_alone(plain_critic_oracle):
-    """Under the fixture O.residual_mlp_backward still serves a residual cache (the actor's backward calls it) and
-    takes the plain path only for a cache of the plain forward."""
+def test_critic_backward_follows_the_model():
+    """O.critic_backward takes the head from the model it is given: the residual critic's is O.residual_mlp_backward
+    (which the actor's backward calls too), the plain critic's is O.plain_critic_backward."""
     rng = np.random.default_rng(3)
     _, _, critic = make_models(0, HOPPER)
     pc = to_f64(critic)
@@ -60,14 +61,17 @@ def test_fixture_leaves_the_actor_backward_alone(plain_critic_oracle):
     _, rcache = O.residual_mlp_forward(pc, state.reshape(6, -1), "Mish", "")
     g_res, _ = O.residual_mlp_backward(pc, rcache, dy, "Mish", "")
     assert np.array_equal(g_res["l2_w"], (rcache["u2"].T @ dy) @ pc["out_w"].T)      # the factored residual form
-    _, pcache = O.critic_forward(pc, state)
-    g_pl, _ = O.residual_mlp_backward(pc, pcache, dy, "Mish", "")
-    ref, _ = plain_critic_backward(pc, pcache, dy)
+    g_dflt, _ = O.critic_backward(pc, O.critic_forward(pc, state)[1], dy)
+    assert all(np.array_equal(g_dflt[k], g_res[k]) for k in g_res)
+    _, pcache = O.critic_forward(pc, state, PLAIN_CRITIC)
+    g_pl, _ = O.critic_backward(pc, pcache, dy, PLAIN_CRITIC)
+    ref, _ = O.plain_critic_backward(pc, pcache, dy)
     assert all(np.array_equal(g_pl[k], ref[k]) for k in ref)
+    assert not np.array_equal(g_pl["l2_w"], g_res["l2_w"])
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16", "fp16"])
-def test_plain_critic_oracle_moves_values_and_gradients(plain_critic_oracle, monkeypatch, precision):
+def test_plain_critic_oracle_moves_values_and_gradients(precision):
     """On the GPU tests' inputs (test_critic_forward's 77 states, the 150-row minibatch problem of
     tests/test_update_surface_gpu.py, whose samples and weights the GPU file's cases share) the plain and the
     residual oracle differ in V and in every critic gradient tensor by at least ten times that quantity's bound, so
@@ -75,12 +79,11 @@ def test_plain_critic_oracle_moves_values_and_gradients(plain_critic_oracle, mon
     rnd = US._rnd(precision)
     _, _, critic = make_models(0, HOPPER)
     state = np.random.default_rng(5).uniform(-1, 1, (77, 1, 11)).astype(np.float32).astype(np.float64)
-    p = US._Problem(HOPPER, precision)
-    v_p = O.critic_forward(to_f64(critic), state, rnd=rnd)[0]
+    p = US._Problem(HOPPER_PLAIN_CRITIC, precision)
+    v_p = O.critic_forward(to_f64(critic), state, PLAIN_CRITIC, rnd=rnd)[0]
     met_p, ga_p, gc_p = p.oracle()
-    monkeypatch.undo()
     v_r = O.critic_forward(to_f64(critic), state, rnd=rnd)[0]
-    met_r, ga_r, gc_r = p.oracle()
+    met_r, ga_r, gc_r = p.oracle(model=O.Model())
     tol_v = {"fp32": 1e-4, "bf16": 1e-3, "fp16": 1e-3}[precision]
     dv = float(np.abs(v_p - v_r).max())
     moved = {k: US._rel(gc_p[k], gc_r[k]) for k in gc_r}
@@ -90,7 +93,7 @@ def test_plain_critic_oracle_moves_values_and_gradients(plain_critic_oracle, mon
     assert dv >= 10 * tol_v * (1 + np.abs(v_r).max())
     assert all(v >= 10 * US.TOL[precision] for v in moved.values()), moved
     # (v_loss itself is printed, not asserted: against N(0, 1) returns it is dominated by the returns' own square)
-    for k in ga_r:   # the actor's side of c_loss is the residual oracle's under the fixture
+    for k in ga_r:   # the actor's side of c_loss does not depend on the critic's head
         assert np.array_equal(ga_p[k], ga_r[k]), k
 
 

@@ -1,5 +1,5 @@
-"""Plain critic on the GPU: the entries that take a packed critic image, against the plain-critic oracle
-(tests/plain_critic_oracle.py: O.critic_forward and O.residual_mlp_backward replaced for the duration of a test).
+"""Plain critic on the GPU: the entries that take a packed critic image, against the oracle's plain critic
+(O.Model(critic_head="plain"), derived from the dims).
 
 Hopper dims (SD = 11, HC = 256) at fp32, bf16 and fp16. Bounds are the residual critic's of the same entry,
 unchanged: test_critic_forward's for V (1e-4 / 1e-3 / 1e-3 of 1 + max|V|), test_ppo_minibatch_grads's per tensor
@@ -22,7 +22,7 @@ from tests import test_kernels_gpu as KG
 from tests import test_update_ft_steps_gpu as FT
 from tests import test_update_regimes_gpu as UR
 from tests.helpers import HOPPER, to_f64
-from tests.plain_critic_oracle import HOPPER_PLAIN_CRITIC, plain_critic_oracle  # noqa: F401
+from tests.variants import HOPPER_PLAIN_CRITIC
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,12 +40,13 @@ def _states(n, d):
     return np.random.default_rng(5).uniform(-1, 1, (n, 1, d.obs_dim)).astype(np.float32)
 
 
-def _forward_err(d, precision, img, critic, n, cuda, oracle=None):
-    """max|V - ref| / (1 + max|ref|) of dppo_critic_forward on n states against `oracle` (default: O.critic_forward)."""
+def _forward_err(d, precision, img, critic, n, cuda, model=None):
+    """max|V - ref| / (1 + max|ref|) of dppo_critic_forward on n states against O.critic_forward for `model`
+    (default: the critic the dims describe)."""
     import torch
     from diffusionpolicyoptimization_amd import ops
     state = _states(n, d)
-    ref, _ = (oracle or O.critic_forward)(to_f64(critic), state.astype(np.float64), rnd=KG._rnd(precision))
+    ref, _ = O.critic_forward(to_f64(critic), state.astype(np.float64), model or O.Model.from_dims(d), rnd=KG._rnd(precision))
     v = ops.critic_forward(d, precision, img, torch.tensor(state.reshape(n, -1), device=cuda))
     torch.cuda.synchronize()
     v = v.cpu().numpy()
@@ -58,7 +59,7 @@ def _forward_err(d, precision, img, critic, n, cuda, oracle=None):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [1, 31, 33, 77])
 @pytest.mark.parametrize("precision", PRECISIONS)
-def test_critic_forward_matches_plain_oracle(cuda, plain_critic_oracle, precision, n):
+def test_critic_forward_matches_plain_oracle(cuda, precision, n):
     """n = 1 (one lane), 31 (one short of a 32-row tile), 33 (one over), 77 (a partial third tile)."""
     from diffusionpolicyoptimization_amd import ops
     d, _, _, critic, _, _, _, _, pc = KG._setup(HOPPER_PLAIN_CRITIC, cuda)
@@ -94,9 +95,9 @@ GRAD_CASES = [(p, r) for r in ("r96-index", "r100", "r1600") for p in PRECISIONS
 
 
 @pytest.mark.parametrize("precision,regime", GRAD_CASES, ids=[f"{p}-{r}" for p, r in GRAD_CASES])
-def test_ppo_minibatch_critic_grads_match_plain_oracle(cuda, plain_critic_oracle, precision, regime):
+def test_ppo_minibatch_critic_grads_match_plain_oracle(cuda, precision, regime):
     """One whole dppo_ppo_minibatch with a plain critic image: the value loss and every critic gradient tensor
-    against O.c_loss under the fixture; the actor's tensors and the other metrics against the same oracle too.
+    against O.c_loss with the plain critic; the actor's tensors and the other metrics against the same oracle too.
       r96-index:  96 rows (whole 32-row tiles) through an explicit row_index;
       r100:       100 rows over 34 samples, not a multiple of 32: every sample about three times, so the
                   sample-weighted rows and their multiplicities run (asserted);
@@ -146,7 +147,7 @@ def test_ppo_minibatch_critic_grads_match_plain_oracle(cuda, plain_critic_oracle
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
-def test_back_to_back_minibatches_rezero_the_sample_counts(cuda, plain_critic_oracle, precision):
+def test_back_to_back_minibatches_rezero_the_sample_counts(cuda, precision):
     """Two minibatches on one stream into the same outputs, rows [37, 137) and [97, 197) of one permutation over 34
     samples (they share samples: asserted). The plain critic's last launch forms no factored product but must
     still zero the stream's per-sample counts: stale counts would double the second minibatch's row weights. The
@@ -167,7 +168,7 @@ def test_back_to_back_minibatches_rezero_the_sample_counts(cuda, plain_critic_or
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
-def test_critic_part_matches_whole(cuda, plain_critic_oracle, precision):
+def test_critic_part_matches_whole(cuda, precision):
     """dppo_ppo_minibatch_part's critic half (part 2) alone against the whole minibatch, 150 rows: the critic's
     gradient range within test_ft20_parts_match_whole's bounds (median 1e-6, max 5e-3 absolute), v_loss 1e-3
     relative, and the part against the oracle; the part leaves the actor's range and the other metrics untouched."""
@@ -193,7 +194,7 @@ def test_critic_part_matches_whole(cuda, plain_critic_oracle, precision):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 @pytest.mark.parametrize("form", ["staged", "fused"])
-def test_optimizer_steps_keep_the_plain_critic_image(cuda, plain_critic_oracle, precision, form):
+def test_optimizer_steps_keep_the_plain_critic_image(cuda, precision, form):
     """Three AdamW steps of the critic range (staged, and DPPO_STEP_FUSED_PACK): after each the image is
     byte-identical to a fresh dppo_pack_critic_head pack of the stepped parameters, and its head is still PLAIN:
     dppo_critic_forward on it matches the plain oracle of the stepped parameters at test_critic_forward's bound
@@ -223,7 +224,7 @@ def test_optimizer_steps_keep_the_plain_critic_image(cuda, plain_critic_oracle, 
     assert err < V_TOL[precision]
 
 
-def test_pack_critic_head_attribute(cuda, plain_critic_oracle):
+def test_pack_critic_head_attribute(cuda):
     """A head outside the enum is DPPO_EINVAL; the bytes of a plain pack are those of a residual pack; re-packing
     the same buffer through dppo_pack_critic resets the head: the forward then matches the RESIDUAL oracle, and
     dppo_pack_critic_head(PLAIN) on it the plain one again."""
@@ -238,10 +239,9 @@ def test_pack_critic_head_attribute(cuda, plain_critic_oracle):
     assert torch.equal(img, ops.pack_critic(res, pc, precision, out=zeros()))
     with pytest.raises(DppoError, match=re.escape("failed (1): dppo_pack_critic_head: bad head 2")):
         _lib.call("dppo_pack_critic_head", ctypes.byref(d.c()), _lib.PRECISION[precision], 2, ptr(pc), ptr(img), stream_handle(cuda))
-    residual_oracle = lambda p, s, rnd=None: O.residual_mlp_forward(p, s.reshape(s.shape[0], -1), "Mish", "", rnd)
     e_plain = _forward_err(d, precision, img, critic, 77, cuda)                      # the refused pack left the head
     _lib.call("dppo_pack_critic", ctypes.byref(d.c()), _lib.PRECISION[precision], ptr(pc), ptr(img), stream_handle(cuda))
-    e_res = _forward_err(d, precision, img, critic, 77, cuda, oracle=residual_oracle)
+    e_res = _forward_err(d, precision, img, critic, 77, cuda, model=O.Model())
     e_cross = _forward_err(d, precision, img, critic, 77, cuda)
     _lib.call("dppo_pack_critic_head", ctypes.byref(d.c()), _lib.PRECISION[precision], 1, ptr(pc), ptr(img), stream_handle(cuda))
     e_back = _forward_err(d, precision, img, critic, 77, cuda)
@@ -251,7 +251,7 @@ def test_pack_critic_head_attribute(cuda, plain_critic_oracle):
     assert e_cross >= 10 * V_TOL[precision]
 
 
-def test_freed_image_leaves_no_attribute_behind(cuda, plain_critic_oracle):
+def test_freed_image_leaves_no_attribute_behind(cuda):
     """The attributes are keyed by the image's address: when a tensor ops.pack_critic / ops.pack_actor packed is
     freed, its entry goes with it (dppo_forget_image), so whatever is allocated at that address next, a clone of a
     residual image for one, reads as never packed. Checked without relying on the allocator: the tensor's
@@ -261,13 +261,12 @@ def test_freed_image_leaves_no_attribute_behind(cuda, plain_critic_oracle):
     from diffusionpolicyoptimization_amd import ops
     precision = "fp32"
     d, _, _, critic, _, _, _, pf, pc = KG._setup(dict(HOPPER_PLAIN_CRITIC, head="plain", activation="Mish"), cuda)
-    residual_oracle = lambda p, s, rnd=None: O.residual_mlp_forward(p, s.reshape(s.shape[0], -1), "Mish", "", rnd)
     img = ops.pack_critic(d, pc, precision)
     fin = img._dppo_forget
     assert fin.alive and ops.pack_critic(d, pc, precision, out=img)._dppo_forget is fin
     assert _forward_err(d, precision, img, critic, 33, cuda) < V_TOL[precision]
     fin()
-    e_res = _forward_err(d, precision, img, critic, 33, cuda, oracle=residual_oracle)
+    e_res = _forward_err(d, precision, img, critic, 33, cuda, model=O.Model())
     e_plain = _forward_err(d, precision, img, critic, 33, cuda)
     print(json.dumps({"case": "forgotten plain critic image", "residual": e_res, "plain": e_plain}))
     assert e_res < V_TOL[precision] and e_plain >= 10 * V_TOL[precision]
@@ -283,9 +282,9 @@ def test_freed_image_leaves_no_attribute_behind(cuda, plain_critic_oracle):
 # ------------------------------------------------------------------------------------------------
 # agents
 # ------------------------------------------------------------------------------------------------
-def test_plain_critic_iteration_matches_oracle(cuda, plain_critic_oracle, tmp_path, monkeypatch):
+def test_plain_critic_iteration_matches_oracle(cuda, tmp_path, monkeypatch):
     """An eval and a training iteration of the fp32 agent from ft_ppo_diffusion_mlp_plain_critic.yaml (seed 42, the
-    shapes and bounds of tests/test_iteration_gpu.py) against oracle/iteration.py under the fixture."""
+    shapes and bounds of tests/test_iteration_gpu.py) against oracle/iteration.py with the plain critic."""
     from diffusionpolicyoptimization_amd.util import config
     from tests import test_iteration_gpu as IT
     load = config.load_config

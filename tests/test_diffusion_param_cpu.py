@@ -1,5 +1,5 @@
 """denoised_clip_value other than 1.0 (None included) and predict_epsilon=False without a GPU: the model's
-constructor, the x0 table rows, the ABI surface and the cfgs, the x0 restatement of p_losses against finite
+constructor, the x0 table rows, the ABI surface and the cfgs, the x0 target of O.p_losses against finite
 differences, and the proof that each setting is observable on the inputs tests/test_diffusion_param_gpu.py uses:
 
   * moving the clip from 1.0 to 0.5, 2.0 or none, and switching to x0, moves the oracle's actions and chains,
@@ -15,7 +15,7 @@ import pytest
 
 from oracle import dppo_oracle as O
 from oracle import philox as PX
-from tests import param_oracle as PO
+from tests import variants as PO
 from tests import pretrain_cases as C
 from tests.helpers import HOPPER, make_models, to_f64
 
@@ -119,14 +119,15 @@ def test_cfgs_load():
 
 
 # ------------------------------------------------------------------------------------------------
-# the x0 restatement of p_losses
+# the x0 target of p_losses
 # ------------------------------------------------------------------------------------------------
 def test_p_losses_x0_against_finite_differences():
     p, sched = C.model(20)
     inp = C.inputs(5, 20)
     f = lambda x, a, b: np.asarray(x, np.float64).reshape(5, a, b)
     args = (f(inp["x0"], 4, 3), f(inp["cond"], 1, 11), inp["t"], f(inp["noise"], 4, 3))
-    loss, g = PO.p_losses_x0(p, sched, *args)
+    x0_sched = O.with_param(sched, 1.0, False)
+    loss, g = O.p_losses(p, x0_sched, *args)
     loss_eps, g_eps = O.p_losses(p, sched, *args)
     assert abs(loss - loss_eps) > 0.1 * abs(loss_eps)          # another loss than the epsilon target's
     rng = np.random.default_rng(3)
@@ -136,9 +137,9 @@ def test_p_losses_x0_against_finite_differences():
             h = 1e-6
             q = {k: v.copy() for k, v in p.items()}
             q[name][idx] += h
-            up = PO.p_losses_x0(q, sched, *args, with_grad=False)[0]
+            up = O.p_losses(q, x0_sched, *args, with_grad=False)[0]
             q[name][idx] -= 2 * h
-            dn = PO.p_losses_x0(q, sched, *args, with_grad=False)[0]
+            dn = O.p_losses(q, x0_sched, *args, with_grad=False)[0]
             fd = (up - dn) / (2 * h)
             assert abs(fd - g[name][idx]) <= 1e-6 * (1 + abs(fd)), (name, idx, fd, g[name][idx])
 
@@ -159,7 +160,7 @@ def _off_edges(xr, bounds):
 
 @pytest.mark.parametrize("precision,E", [("fp32", 16), ("bf16", 17), ("fp16", 16)])
 @pytest.mark.parametrize("setting", PO.SETTING_IDS)
-def test_setting_moves_the_sampler(setting, precision, E):
+def test_setting_moves_the_sampler(monkeypatch, setting, precision, E):
     """tests/test_diffusion_param_gpu.py test_sampler_matches_param_oracle's inputs: actions and chains move by ten
     bounds; a tenth and more of the chain's x_recon values lie between the old and the new bound."""
     from tests import test_sampler_surface_gpu as SS
@@ -168,22 +169,17 @@ def test_setting_moves_the_sampler(setting, precision, E):
     _, clip, pe = SETTING[setting]
     inp = SS._Inputs(HOPPER, E, seed=11)
     inp.base, inp.ft = PO.sampler_models(inp, clip)        # denoiser-like without the clip, as the GPU case
-    run = lambda: O.sample(to_f64(inp.base), to_f64(inp.ft), inp.sched, inp.state.astype(np.float64), inp.xT, inp.z,
-                           inp.d.ft_denoising_steps, rnd=_rnd(precision), round_h3=False)
-    default = run()
-    seen = []
-    with PO.param_oracle(clip, pe):
-        inner = O.p_mean_var
+    run = lambda sched: O.sample(to_f64(inp.base), to_f64(inp.ft), sched, inp.state.astype(np.float64), inp.xT, inp.z,
+                                 inp.d.ft_denoising_steps, rnd=_rnd(precision), round_h3=False)
+    default = run(inp.sched)
+    seen, inner = [], O.p_mean_var
 
-        def spy(sched, eps, x, t, denoised_clip=1.0):
-            seen.append(PO.x_recon(sched, eps, x, t, pe))
-            return inner(sched, eps, x, t, denoised_clip)
+    def spy(sched, eps, x, t):      # collects every step's x_recon for the band below; selects nothing
+        seen.append(PO.x_recon(sched, eps, x, t, pe))
+        return inner(sched, eps, x, t)
 
-        O.p_mean_var = spy
-        try:
-            moved = run()
-        finally:
-            O.p_mean_var = inner
+    monkeypatch.setattr(O, "p_mean_var", spy)
+    moved = run(O.with_param(inp.sched, clip, pe))
     SS._assert_moved(f"{setting}-{precision}-E{E}", precision, moved, default)
     xr = np.concatenate([s.ravel() for s in seen])
     c = PO.bound_of(clip)
@@ -213,16 +209,15 @@ class _Update:
     def run(self, clip, pe):
         d, N, kf, bi, di = self.d, self.N, self.kf, self.bi, self.di
         sh = (ROWS, d.horizon_steps, d.action_dim)
-        rnd = _rnd(self.precision)
-        with PO.param_oracle(clip, pe):
-            lp = O.get_logprobs(to_f64(self.ft), self.sched, self.obs.reshape(N, 1, -1).astype(np.float64),
-                                self.chains.reshape(N, kf + 1, d.horizon_steps, d.action_dim).astype(np.float64), kf, rnd=rnd)
-            lp_old = np.clip(lp, -5, 2).mean(axis=(1, 2)).reshape(N, kf)
-            _, ga, gc = O.c_loss(to_f64(self.ft), to_f64(self.critic), self.sched,
-                                 self.obs[bi].reshape(ROWS, 1, -1).astype(np.float64),
-                                 self.chains[bi, di].reshape(sh).astype(np.float64),
-                                 self.chains[bi, di + 1].reshape(sh).astype(np.float64), di, self.ret[bi].astype(np.float64),
-                                 None, self.adv[bi].astype(np.float64), lp_old[bi, di], kf, rnd=rnd, denom=ROWS)
+        rnd, sched = _rnd(self.precision), O.with_param(self.sched, clip, pe)
+        lp = O.get_logprobs(to_f64(self.ft), sched, self.obs.reshape(N, 1, -1).astype(np.float64),
+                            self.chains.reshape(N, kf + 1, d.horizon_steps, d.action_dim).astype(np.float64), kf, rnd=rnd)
+        lp_old = np.clip(lp, -5, 2).mean(axis=(1, 2)).reshape(N, kf)
+        _, ga, gc = O.c_loss(to_f64(self.ft), to_f64(self.critic), sched,
+                             self.obs[bi].reshape(ROWS, 1, -1).astype(np.float64),
+                             self.chains[bi, di].reshape(sh).astype(np.float64),
+                             self.chains[bi, di + 1].reshape(sh).astype(np.float64), di, self.ret[bi].astype(np.float64),
+                             None, self.adv[bi].astype(np.float64), lp_old[bi, di], kf, rnd=rnd, denom=ROWS)
         return lp, ga
 
     def x_recon(self, pe):

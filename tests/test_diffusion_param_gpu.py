@@ -1,5 +1,5 @@
 """denoised_clip_value in {0.5, 2.0, None} and predict_epsilon=False on the GPU: every entry that takes a schedule
-table, against the float64 oracle under tests/param_oracle.py (O.p_mean_var replaced for the duration of a case).
+table, against the float64 oracle on a schedule that carries the same setting (O.with_param).
 
 Hopper's geometry throughout (obs 11, action 3, horizon 4, hidden 512, K = 20, K' = 10). Each comparison uses the
 bound of the existing case it mirrors, taken from that case's helper: the sampler's SS._check / SS.TOL
@@ -11,7 +11,7 @@ printed as a JSON line before it is asserted. tests/test_diffusion_param_cpu.py 
 setting moves every compared quantity by ten bounds and more, and that no x_recon sits on a clip edge.
 
 The sampler cases without the clip run the same seeded models reshaped to behave like a denoiser
-(tests/param_oracle.py denoiser_like: eps = alpha x + 2^-10 of the seeded network's own output): the sampler surface's
+(tests/variants.py denoiser_like: eps = alpha x + 2^-10 of the seeded network's own output): the sampler surface's
 bounds are absolute and presuppose chains of order 1, which only the clip gives a seeded, untrained network (its
 unclipped chains reach 4.7e3, where the fp32 bound of 2e-4 is below half an ulp of the compared values). Bounds, cases
 and reference are unchanged. Measured on an MI355X without the clip, error / bound: fp32 max 3.5e-6 / 2e-4; bf16
@@ -28,7 +28,7 @@ import numpy as np
 import pytest
 
 from oracle import dppo_oracle as O
-from tests import param_oracle as PO
+from tests import variants as PO
 from tests import pretrain_cases as C
 from tests import test_kernels_gpu as KG
 from tests import test_pretrain_step_gpu as PT
@@ -36,8 +36,7 @@ from tests import test_sampler_surface_gpu as SS
 from tests import test_update_regimes_gpu as UR
 from tests import test_update_surface_gpu as US
 from tests.helpers import HOPPER, HOPPER_DDIM, to_f64
-from tests.mish_oracle import HOPPER_MISH, mish_oracle  # noqa: F401
-from tests.plain_oracle import HOPPER_PLAIN, plain_oracle  # noqa: F401
+from tests.variants import HOPPER_MISH, HOPPER_PLAIN
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,6 +62,7 @@ def _gpu(cuda, dims, precision, E, clip, pe, seed=11):
     inp = SS._Inputs(dims, E, seed=seed)
     g = SS._Gpu(inp, precision, cuda)
     g.tab = _table(cuda, inp.sched, clip, pe)
+    inp.sched = O.with_param(inp.sched, clip, pe)
     if clip is None:
         inp.base, inp.ft = PO.sampler_models(inp, clip)
         spec = ops.actor_param_spec(inp.d)
@@ -92,13 +92,12 @@ SAMPLER_IDS = [f"{s}-{p}-E{E}-kf{kf}" + "".join(f"-{k}" for k in kw) for s, p, E
 @pytest.mark.parametrize("setting,precision,E,kf,kernel,kw", SAMPLER_CASES, ids=SAMPLER_IDS)
 def test_sampler_matches_param_oracle(cuda, setting, precision, E, kf, kernel, kw):
     """dppo_sample, injected noise, on a table with the setting recorded: actions and every stored chain row
-    against O.sample under the wrapper, at the sampler surface's bounds; two launches bit-identical."""
+    against O.sample on the setting's schedule, at the sampler surface's bounds; two launches bit-identical."""
     _, clip, pe = SETTING[setting]
     inp, g = _gpu(cuda, dict(HOPPER, ft_denoising_steps=kf), precision, E, clip, pe)
     assert g.plan["kernel"] == kernel, g.plan
     act, ch = g.twice(**kw)
-    with PO.param_oracle(clip, pe):
-        ref = inp.oracle(precision, **kw)
+    ref = inp.oracle(precision, **kw)
     SS._check(f"param {setting} E{E} kf{kf}", precision, SS._stats(act, ch, *ref), plan=g.plan)
 
 
@@ -192,10 +191,9 @@ def test_logprob_matches_param_oracle(cuda, setting, precision, n):
     tab = _table(cuda, sched, clip, pe)
     kf = d.ft_denoising_steps
     _, obs, chains, _, _ = PO.update_inputs(d, n)
-    with PO.param_oracle(clip, pe):
-        ref = O.get_logprobs(to_f64(ft), sched, obs.reshape(n, 1, -1).astype(np.float64),
-                             chains.reshape(n, kf + 1, d.horizon_steps, d.action_dim).astype(np.float64), kf,
-                             rnd=KG._rnd(precision))
+    ref = O.get_logprobs(to_f64(ft), O.with_param(sched, clip, pe), obs.reshape(n, 1, -1).astype(np.float64),
+                         chains.reshape(n, kf + 1, d.horizon_steps, d.action_dim).astype(np.float64), kf,
+                         rnd=KG._rnd(precision))
     lpe, lpm = ops.logprob(d, precision, ops.pack_actor(d, pf, precision), tab, torch.tensor(obs, device=cuda),
                            torch.tensor(chains, device=cuda))
     torch.cuda.synchronize()
@@ -212,13 +210,14 @@ def test_logprob_matches_param_oracle(cuda, setting, precision, n):
 # dppo_ppo_minibatch
 # ------------------------------------------------------------------------------------------------
 def _case(monkeypatch, cuda, precision, dims, N, clip, pe, **kw):
-    """A UR._Case on unit-scale chains whose table carries the setting (the case's own constructor already
-    launches dppo_logprob on it). Call under PO.param_oracle."""
+    """A UR._Case on unit-scale chains whose table and oracle schedule carry the setting (the case's own
+    constructor already launches dppo_logprob on it)."""
     setup = UR._setup
 
     def setup_with_record(dims_, cuda_, **skw):
         out = list(setup(dims_, cuda_, **skw))
         out[5] = _table(cuda_, out[4], clip, pe, like=out[5] if pe else None)
+        out[4] = O.with_param(out[4], clip, pe)
         return tuple(out)
 
     monkeypatch.setattr(UR, "_setup", setup_with_record)
@@ -251,23 +250,20 @@ def test_minibatch_grads_match_param_oracle(cuda, monkeypatch, setting, precisio
     """77 rows through a row_index (two whole 32-row tiles and a 13-row tail), ratio 1: the loss metrics and every
     actor and critic gradient tensor."""
     _, clip, pe = SETTING[setting]
-    with PO.param_oracle(clip, pe):
-        case = _case(monkeypatch, cuda, precision, HOPPER, -(-(UR.START + 77) // 10) + 20, clip, pe)
-        _grads_vs_oracle(case, 77, f"param-{setting}-{precision}-r77")
+    case = _case(monkeypatch, cuda, precision, HOPPER, -(-(UR.START + 77) // 10) + 20, clip, pe)
+    _grads_vs_oracle(case, 77, f"param-{setting}-{precision}-r77")
 
 
-def test_minibatch_grads_mish_x0(cuda, monkeypatch, mish_oracle):
+def test_minibatch_grads_mish_x0(cuda, monkeypatch):
     _, clip, pe = SETTING["x0"]
-    with PO.param_oracle(clip, pe):
-        case = _case(monkeypatch, cuda, "bf16", HOPPER_MISH, -(-(UR.START + 77) // 10) + 20, clip, pe)
-        _grads_vs_oracle(case, 77, "param-x0-mish-bf16-r77")
+    case = _case(monkeypatch, cuda, "bf16", HOPPER_MISH, -(-(UR.START + 77) // 10) + 20, clip, pe)
+    _grads_vs_oracle(case, 77, "param-x0-mish-bf16-r77")
 
 
-def test_minibatch_grads_plain_clip(cuda, monkeypatch, plain_oracle):
+def test_minibatch_grads_plain_clip(cuda, monkeypatch):
     _, clip, pe = SETTING["clip0.5"]
-    with PO.param_oracle(clip, pe):
-        case = _case(monkeypatch, cuda, "fp32", HOPPER_PLAIN, -(-(UR.START + 77) // 10) + 20, clip, pe)
-        _grads_vs_oracle(case, 77, "param-clip0.5-plain-fp32-r77")
+    case = _case(monkeypatch, cuda, "fp32", HOPPER_PLAIN, -(-(UR.START + 77) // 10) + 20, clip, pe)
+    _grads_vs_oracle(case, 77, "param-clip0.5-plain-fp32-r77")
 
 
 def test_minibatch_grads_tile64_clip2(cuda, monkeypatch):
@@ -275,20 +271,18 @@ def test_minibatch_grads_tile64_clip2(cuda, monkeypatch):
     from diffusionpolicyoptimization_amd import ops
     _, clip, pe = SETTING["clip2"]
     rows = 64 * UR._cus(cuda)
-    with PO.param_oracle(clip, pe):
-        case = _case(monkeypatch, cuda, "bf16", HOPPER, -(-(UR.START + rows) // 10) + 50, clip, pe)
-        plan = ops.ppo_plan(case.d, "bf16", rows)
-        assert plan["actor_tile_rows"] == 64 and plan["actor_waves"] == 16, plan
-        _grads_vs_oracle(case, rows, "param-clip2-tile64", indexed=False)
+    case = _case(monkeypatch, cuda, "bf16", HOPPER, -(-(UR.START + rows) // 10) + 50, clip, pe)
+    plan = ops.ppo_plan(case.d, "bf16", rows)
+    assert plan["actor_tile_rows"] == 64 and plan["actor_waves"] == 16, plan
+    _grads_vs_oracle(case, rows, "param-clip2-tile64", indexed=False)
 
 
 def test_minibatch_learn_eta_ddim_clip(cuda, monkeypatch):
-    """DPPO_PPO_LEARN_ETA under DDIM (bf16, eta 0.6) at clip 0.5: metrics[8] against the oracle's eta_grad with its
-    np.clip(..., -1, 1) line at the case's bound too, at the 64-row tile test's d_eta bound (3e-2 relative)."""
+    """DPPO_PPO_LEARN_ETA under DDIM (bf16, eta 0.6) at clip 0.5: metrics[8] against the oracle's eta_grad, whose
+    x0 is clipped at the schedule's bound, at the 64-row tile test's d_eta bound (3e-2 relative)."""
     _, clip, pe = SETTING["clip0.5"]
-    with PO.param_oracle(clip, pe, clip_eta=True):
-        case = _case(monkeypatch, cuda, "bf16", HOPPER_DDIM, US.NSAMP, clip, pe, eta=0.6)
-        m, met_ref = _grads_vs_oracle(case, US.ROWS, "param-clip0.5-learn-eta", learn_eta=True, indexed=False)
+    case = _case(monkeypatch, cuda, "bf16", HOPPER_DDIM, US.NSAMP, clip, pe, eta=0.6)
+    m, met_ref = _grads_vs_oracle(case, US.ROWS, "param-clip0.5-learn-eta", learn_eta=True, indexed=False)
     ref = met_ref["d_eta"]
     print(json.dumps({"case": "param-learn-eta", "d_eta": float(m[8]), "ref": ref}))
     assert abs(ref) > 1e-3 and abs(m[8] - ref) <= 3e-2 * abs(ref), (m[8], ref)
@@ -297,23 +291,15 @@ def test_minibatch_learn_eta_ddim_clip(cuda, monkeypatch):
 # ------------------------------------------------------------------------------------------------
 # dppo_pretrain_minibatch
 # ------------------------------------------------------------------------------------------------
-def _reference_x0(p, inp, precision):
-    Ta, Da, To, Do = (HOPPER[k] for k in ("horizon_steps", "action_dim", "cond_steps", "obs_dim"))
-    rows = inp["x0"].shape[0]
-    f = lambda x, a, b: np.asarray(x, np.float64).reshape(rows, a, b)
-    return PO.p_losses_x0(p.ft, p.sched, f(inp["x0"], Ta, Da), f(inp["cond"], To, Do), inp["t"], f(inp["noise"], Ta, Da),
-                          rnd=PT._rnd(precision))
-
-
 @pytest.mark.parametrize("precision", C.PRECISIONS)
 @pytest.mark.parametrize("rows", [1, 33, 65])
 def test_pretrain_x0_target(cuda, rows, precision):
-    """The x0 target at 1, 33 and 65 rows: the loss and every gradient tensor against the restated p_losses."""
+    """The x0 target at 1, 33 and 65 rows: the loss and every gradient tensor against O.p_losses on an x0 schedule."""
     p = PT._Problem(cuda, HOPPER)
     p.tab = _table(cuda, p.sched, 1.0, False)
     inp = C.inputs(rows, 20)
     loss, g, _, _ = PT._run(p, precision, inp)
-    loss_ref, g_ref = _reference_x0(p, inp, precision)
+    loss_ref, g_ref = C.reference(p.ft, O.with_param(p.sched, 1.0, False), inp, rnd=PT._rnd(precision))
     PT._check(f"x0-rows{rows}", precision, loss, g, loss_ref, g_ref)
 
 
@@ -346,8 +332,13 @@ def test_explicit_default_record_is_bit_equal(cuda, precision, E):
 
 
 def test_record_is_erased_with_the_tensor(cuda):
-    """The record goes when the table's tensor is freed: a new table at the same address reads as the default."""
+    """The record goes when the table's tensor is freed: a new table at the same address reads as the default.
+    Unreachable cycles of earlier tests (models, rollout pipes) are collected first: collected by the gc.collect()
+    below instead, their device blocks would join the free list between the table's release and the clones, ahead
+    of the table's block, and whether an automatic collection has run by then depends on how many Python objects
+    the tests before this one happened to allocate."""
     import torch
+    gc.collect()
     inp = SS._Inputs(HOPPER, 16, seed=11)
     g = SS._Gpu(inp, "fp32", cuda)
     a_def, _ = g.sample()
@@ -443,8 +434,7 @@ def test_x0_with_learn_eta_is_refused(cuda, monkeypatch):
     import torch
     from diffusionpolicyoptimization_amd import ops
     _, clip, pe = SETTING["x0"]
-    with PO.param_oracle(clip, pe):
-        case = _case(monkeypatch, cuda, "bf16", HOPPER, 40, clip, pe)
+    case = _case(monkeypatch, cuda, "bf16", HOPPER, 40, clip, pe)
     rows = 77
     grads = torch.full((case.na + case.nc,), SS.SENTINEL, dtype=torch.float32, device=cuda)
     met = torch.full((16,), SS.SENTINEL, dtype=torch.float64, device=cuda)
@@ -496,8 +486,7 @@ def test_x0_with_time_stride_is_refused_by_every_entry(cuda, monkeypatch):
     assert not act_t.array.any() and not done.array.any()
     # the update entries
     _, clip, pe = SETTING["x0"]
-    with PO.param_oracle(clip, pe):
-        case = _case(monkeypatch, cuda, precision, HOPPER, 40, clip, pe)
+    case = _case(monkeypatch, cuda, precision, HOPPER, 40, clip, pe)
     rows = 77
     grads = torch.full((case.na + case.nc,), SS.SENTINEL, dtype=torch.float32, device=cuda)
     met = torch.full((16,), SS.SENTINEL, dtype=torch.float64, device=cuda)
@@ -530,10 +519,10 @@ def test_sampler_noclip_seeded_scale(cuda, precision, E, kf, kernel):
     inp = SS._Inputs(dict(HOPPER, ft_denoising_steps=kf), E, seed=11)
     g = SS._Gpu(inp, precision, cuda)
     g.tab = _table(cuda, inp.sched, None, True)
+    inp.sched = O.with_param(inp.sched, None, True)
     assert g.plan["kernel"] == kernel, g.plan
     act, ch = g.twice()
-    with PO.param_oracle(None, True):
-        ref_a, ref_c = inp.oracle(precision)
+    ref_a, ref_c = inp.oracle(precision)
     s = float(np.abs(ref_c).max())
     assert s > 100.0, s
     SS._check(f"param noclip seeded-scale E{E} kf{kf}", precision, SS._stats(act / s, ch / s, ref_a / s, ref_c / s), plan=g.plan, s=s)
@@ -545,7 +534,7 @@ def test_sampler_noclip_seeded_scale(cuda, precision, E, kf, kernel):
 @pytest.mark.parametrize("setting,suffix", [("x0", "_x0"), ("noclip", "_noclip")])
 def test_finetune_iterations_match_oracle(cuda, tmp_path, monkeypatch, setting, suffix):
     """TrainPPODiffusionAgent from each new fine-tune cfg (fp32, seed 42, the shapes of tests/test_iteration_gpu.py):
-    an eval iteration and two training iterations against oracle/iteration.py under the wrapper, at that file's own
+    an eval iteration and two training iterations against oracle/iteration.py on the model's setting, at that file's own
     bounds (IT._run_and_compare): rollout chains through the model's sched / sched_eval, old log-probs, the update's
     minibatches and the parameter change. The no-clip agent starts from a denoiser-like base policy checkpoint
     (PO.denoiser_like of the seeded weights), for the reason given there."""
@@ -564,8 +553,8 @@ def test_finetune_iterations_match_oracle(cuda, tmp_path, monkeypatch, setting, 
     a, orc = IT._agent_and_oracle(42, tmp_path, extra)
     m = a.model
     assert m.predict_epsilon == pe and m.denoised_clip_value == clip
-    with PO.param_oracle(clip, pe):
-        errs = IT._run_and_compare(a, orc, n_itr=3)
+    assert (orc.sched["denoised_clip"], orc.sched["predict_epsilon"]) == (PO.bound_of(clip), pe)
+    errs = IT._run_and_compare(a, orc, n_itr=3)
     print(json.dumps({"case": f"param-iteration-{setting}", "iterations": errs}))
     assert [e["eval"] for e in errs] == [True, False, False]
 
@@ -574,7 +563,8 @@ def test_finetune_iterations_match_oracle(cuda, tmp_path, monkeypatch, setting, 
 def test_pretrain_x0_steps_follow_the_oracle(cuda, tmp_path, monkeypatch, precision):
     """TrainDiffusionAgent.run() from pre_diffusion_mlp_x0.yaml over three epochs, teacher-forced exactly as
     tests/test_pretrain_step_gpu.py test_pretrain_steps_follow_the_oracle does (that test's body, with the cfg name
-    and the reference loss replaced): every step's loss and gradient against the x0 restatement of p_losses."""
+    replaced; the reference follows the model's predict_epsilon): every step's loss and gradient against O.p_losses
+    with the x0 target."""
     from diffusionpolicyoptimization_amd.util import config
     load = config.load_config
     seen = []
@@ -585,6 +575,5 @@ def test_pretrain_x0_steps_follow_the_oracle(cuda, tmp_path, monkeypatch, precis
         return cfg
 
     monkeypatch.setattr(config, "load_config", load_x0)
-    monkeypatch.setattr(O, "p_losses", PO.p_losses_x0)
     PT.test_pretrain_steps_follow_the_oracle(cuda, tmp_path, precision)
     assert seen == [False]

@@ -52,8 +52,12 @@ def _agent_and_oracle(seed, tmp_path, extra=(), precision="fp32", env_oracle=Non
         env = SyntheticVecEnvOracle(seeds, cfg.obs_dim, cfg.action_dim, cfg.act_steps, cfg.env.max_episode_steps,
                                     cfg.env.get("family_seed", 0))
     assert a.actor_lr_scheduler(1) == a.actor_lr_scheduler(50) == cfg.train.actor_lr   # constant at this cfg
+    # the variant is the agent's model's: its networks, its diffusion parameterisation, its advantage quantiles
+    sched = O.with_param(O.ddpm_schedule(cfg.denoising_steps), m.denoised_clip_value, m.predict_epsilon)
+    quantiles = (m.clip_advantage_lower_quantile, m.clip_advantage_upper_quantile) if m.adv_clip else None
     orc = PPODiffusionLoopOracle(
-        base, ft, critic, m.actor_spec, m.critic_spec, O.ddpm_schedule(cfg.denoising_steps), env,
+        base, ft, critic, m.actor_spec, m.critic_spec, sched, env, model=O.Model.from_dims(m.dims),
+        adv_clip_quantiles=quantiles,
         seed=m.seed, perm_seed=a.perm_seed, n_steps=a.n_steps, ft_steps=m.ft_denoising_steps,
         act_steps=a.act_steps, horizon_steps=a.horizon_steps, action_dim=a.action_dim, val_freq=a.val_freq,
         batch_size=a.batch_size, update_epochs=a.update_epochs, target_kl=a.target_kl, gamma=a.gamma,

@@ -364,7 +364,7 @@ def test_pretrain_steps_follow_the_oracle(cuda, tmp_path, precision):
     n = lambda x: x.detach().cpu().numpy()
     assert [b["x0"].shape[0] for b in batches] == [48, 16] * 3 and len(steps) == len(batches) == 6
     K, bound, rnd = model.denoising_steps, C.BOUND[precision], _rnd(precision)
-    sched = ddpm_buffers(K)
+    sched = O.with_param(ddpm_buffers(K), model.denoised_clip_value, model.predict_epsilon)
     failures = []
     for i, (b, s) in enumerate(zip(batches, steps), start=1):
         B = b["x0"].shape[0]
@@ -374,7 +374,8 @@ def test_pretrain_steps_follow_the_oracle(cuda, tmp_path, precision):
         loss_ref, g_ref = O.p_losses(to_f64(ops.unflatten_params(spec, P)), sched,
                                      n(b["x0"]).astype(np.float64).reshape(B, d.horizon_steps, d.action_dim),
                                      n(b["cond"]).astype(np.float64).reshape(B, d.cond_steps, d.obs_dim), t,
-                                     n(b["noise"]).astype(np.float64).reshape(B, d.horizon_steps, d.action_dim), rnd=rnd)
+                                     n(b["noise"]).astype(np.float64).reshape(B, d.horizon_steps, d.action_dim), rnd=rnd,
+                                     model=O.Model.from_dims(d))
         errs = C.errors(ops.unflatten_params(spec, G), g_ref)
         loss = float(b["loss"])
         loss_err = abs(loss - loss_ref) / loss_ref

@@ -167,6 +167,7 @@ class _Inputs:
         from diffusionpolicyoptimization_amd.model.diffusion.sampling import ddpm_buffers
         self.dims, self.E, self.eta = dims, E, eta
         self.d = d = _dims(dims)
+        self.model = O.Model.from_dims(dims)
         self.base, self.ft, _ = make_models(0, {k: v for k, v in dims.items() if k != "time_stride"})
         self.K = K = d.denoising_steps
         self.sched = O.ddim_schedule(K * d.time_stride, K, eta) if d.time_stride > 1 else ddpm_buffers(K)
@@ -188,7 +189,7 @@ class _Inputs:
         return O.sample(to_f64(self.base), to_f64(self.ft), self.sched,
                         (self.state if state is None else state).astype(np.float64),
                         self.xT if xT is None else xT, self.z if z is None else z, self.d.ft_denoising_steps,
-                        rnd=_rnd(precision), round_h3=not split, **kw)
+                        rnd=_rnd(precision), round_h3=not split, **{"model": self.model, **kw})
 
 
 def _stats(act, ch, ref_a, ref_c):

@@ -58,7 +58,7 @@ def _oracle(case, start, rows, adv_mean_std=None, eta_grad=False):
                     case.chains[bi, di].reshape(sh).astype(np.float64), case.chains[bi, di + 1].reshape(sh).astype(np.float64),
                     di, case.ret[bi].astype(np.float64), None, case.adv[bi].astype(np.float64), case.lp_old_ref[bi, di],
                     case.kf, rnd=_rnd(case.precision), adv_mean_std=adv_mean_std, denom=rows, critic_dedup=_dedup(bi),
-                    eta_grad=eta_grad)
+                    eta_grad=eta_grad, model=case.model)
 
 
 class _Out:

@@ -93,6 +93,7 @@ class _Case:
         self.cuda, self.precision = cuda, precision
         (self.d, _, self.ft, self.critic, self.sched, self.tab, _, self.pf, self.pc) = _setup(dims, cuda, eta=eta)
         d = self.d
+        self.model = O.Model.from_dims(dims)
         self.N, self.kf = N, d.ft_denoising_steps
         self.total = N * self.kf
         self.rng, self.obs, self.chains, self.adv, self.ret = _inputs(d, N, f32_draws)
@@ -107,7 +108,7 @@ class _Case:
         else:
             lp_ref = O.get_logprobs(to_f64(self.ft), self.sched, self.obs.reshape(N, 1, -1).astype(np.float64),
                                     self.chains.reshape(N, self.kf + 1, d.horizon_steps, d.action_dim).astype(np.float64),
-                                    self.kf, rnd=_rnd(precision))
+                                    self.kf, rnd=_rnd(precision), model=self.model)
             lp_ref_mean = np.clip(lp_ref, -5, 2).mean(axis=(1, 2)).reshape(N, self.kf)
             if lp == "perturbed":
                 self.lp_old_gpu = (lp_ref_mean + self.rng.normal(0, 0.02, (N, self.kf))).astype(np.float32)
@@ -122,7 +123,7 @@ class _Case:
 
     def old_values(self):
         """The -clipv case's old values: V(obs) + U(-0.4, 0.4), clip_vloss_coef 0.2."""
-        v_now = O.critic_forward(to_f64(self.critic), self.obs.reshape(self.N, 1, -1).astype(np.float64),
+        v_now = O.critic_forward(to_f64(self.critic), self.obs.reshape(self.N, 1, -1).astype(np.float64), self.model,
                                  rnd=_rnd(self.precision))[0][:, 0]
         self.oldv = (v_now + self.rng.uniform(-0.4, 0.4, self.N)).astype(np.float32)
         self.oldv_dev = self.T(self.oldv)
@@ -140,7 +141,9 @@ class _Case:
         mean = st[1] / st[0]
         return stats, (mean, math.sqrt(max(st[2] / st[0] - mean * mean, 0.0)))
 
-    def oracle(self, rows, adv_mean_std=None, eta_grad=False):
+    def oracle(self, rows, adv_mean_std=None, eta_grad=False, **kw):
+        """O.c_loss on the rows, for the networks the dims describe; kw: further c_loss keywords (adv_clip_quantiles,
+        caches, another model)."""
         d = self.d
         bi, di = self.rows_of(rows)
         sh = (rows, d.horizon_steps, d.action_dim)
@@ -151,7 +154,7 @@ class _Case:
             di, self.ret[bi].astype(np.float64), self.oldv[bi].astype(np.float64) if clipv else None,
             self.adv[bi].astype(np.float64), self.lp_old_ref[bi, di], self.kf, rnd=_rnd(self.precision),
             adv_mean_std=adv_mean_std, denom=rows, critic_dedup=_dedup(bi), clip_vloss_coef=0.2 if clipv else None,
-            eta_grad=eta_grad)
+            eta_grad=eta_grad, **{"model": self.model, **kw})
 
     def launch(self, global_rows, start, rows, stats=None, row_index=None, l2_deferred=False, learn_eta=False):
         """One dppo_ppo_minibatch over permutation rows [start, start + rows): (gradient, metric sums)."""

@@ -74,6 +74,7 @@ class _Problem:
         from diffusionpolicyoptimization_amd.model.diffusion.sampling import ddpm_buffers
         self.dims, self.precision, self.N = dims, precision, n_samples
         self.d = d = ops.ModelDims(**dims)
+        self.model = O.Model.from_dims(dims)
         self.base, self.ft, self.critic = make_models(0, dims)
         self.sched = ddpm_buffers(d.denoising_steps)
         self.kf = kf = d.ft_denoising_steps
@@ -86,7 +87,7 @@ class _Problem:
         self.ret = rng.normal(size=n_samples).astype(np.float32)
         self.lp_hp = dict(dict(min_logprob_std=0.1, reward_horizon=4), **(lp_hp or {}))
         self.lp_ref = O.get_logprobs(to_f64(self.ft), self.sched, self.state(self.obs), self.x(self.chains, kf + 1), kf,
-                                     min_logprob_std=self.lp_hp["min_logprob_std"], rnd=_rnd(precision))
+                                     min_logprob_std=self.lp_hp["min_logprob_std"], rnd=_rnd(precision), model=self.model)
         H = min(self.lp_hp["reward_horizon"], d.horizon_steps)
         self.lp_ref_mean = np.clip(self.lp_ref, -5, 2)[:, :H].mean(axis=(1, 2)).reshape(n_samples, kf)
         self.kind = LP_KIND[precision]
@@ -106,7 +107,7 @@ class _Problem:
             # BLAS blocking, ~1e-16 away, which made clipfrac of the reference alone 0.07)
             bi = self.bi
             lp = O.get_logprobs(to_f64(self.ft), self.sched, self.state(self.obs[bi]), self.x(self.chains[bi], 2), 1,
-                                min_logprob_std=self.lp_hp["min_logprob_std"], rnd=_rnd(precision))
+                                min_logprob_std=self.lp_hp["min_logprob_std"], rnd=_rnd(precision), model=self.model)
             self.lp_old_rows = np.clip(lp, -5, 2)[:, :H].mean(axis=(1, 2))
 
     def state(self, obs):
@@ -118,9 +119,10 @@ class _Problem:
         return a.reshape(sh).astype(np.float64)
 
     def oracle(self, **hp):
-        """O.c_loss on the minibatch's rows; hp: c_loss keywords over DEFAULTS (adv_mean_std, denom too)."""
+        """O.c_loss on the minibatch's rows, for the networks the dims describe; hp: c_loss keywords over DEFAULTS
+        (adv_mean_std, denom, adv_clip_quantiles, caches, another model too)."""
         bi, di = self.bi, self.di
-        kw = dict(DEFAULTS, **hp)
+        kw = {**DEFAULTS, "model": self.model, **hp}
         return O.c_loss(to_f64(self.ft), to_f64(self.critic), self.sched, self.state(self.obs[bi]),
                         self.x(self.chains[bi, di]), self.x(self.chains[bi, di + 1]), di, self.ret[bi].astype(np.float64),
                         None, self.adv[bi].astype(np.float64), self.lp_old_rows, self.kf, rnd=_rnd(self.precision),

@@ -23,6 +23,8 @@ DPPO_STEP_FUSED_PACK = 0x400             # (ABI 11) AdamW + the image in one lau
 DPPO_STEP_CLEAR_GRADS = 0x800            # (ABI 11) the step zeroes the range's gradients after reading
 DPPO_PPO_PRECLEARED = 4                  # (ABI 11) the part's accumulators are already zero
 DPPO_PPO_ADV_CLIP = 8                    # (within ABI 15) adv_stats is fp64[5]: the row tiles clamp to {lo, hi}
+DPPO_BC_ACCUMULATE = 16                  # (within ABI 15) dppo_bc_minibatch adds to grads and its metric slot
+DPPO_METRIC_BC_LOGPROB = 9               # metric slot: dppo_bc_minibatch's sum of clip(lp, -5, 2)
 # the quantile select's count launch: threads per workgroup, workgroups per segment at most (include/dppo.h)
 DPPO_ADV_QUANTILES_BLOCK, DPPO_ADV_QUANTILES_MAX_CHUNKS = 256, 16
 DPPO_NET_ACTOR, DPPO_NET_CRITIC = 1, 2   # dppo_grad_clip_scales / dppo_optimizer_step_clip: OR'd, 3 = [actor | critic]
@@ -124,6 +126,7 @@ _SIGNATURES = {
     "dppo_ppo_minibatch": (_I, [_DIMS, _I, ctypes.POINTER(DppoPpoHparams), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                _I64, _U64, _I, _I64, _I, _P, _P, _P, _P, _P, _P]),
     "dppo_pretrain_minibatch": (_I, [_DIMS, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I64, _F, _P, _P, _P, _P]),
+    "dppo_bc_minibatch": (_I, [_DIMS, _I, _P, _P, _P, _P, _P, _I, _I64, _F, _F, _F, _I, _P, _P, _P, _P]),
     "dppo_ppo_minibatch_part": (_I, [_DIMS, _I, ctypes.POINTER(DppoPpoHparams), _P, _P, _P, _P, _P, _P, _P, _P,
                                     _P, _I64, _U64, _I, _I64, _I, _P, _P, _P, _P, _P, _I, _P]),
     "dppo_feistel_permute": (_I, [_I64, _I64, _I64, _U64, _I, _P, _P]),

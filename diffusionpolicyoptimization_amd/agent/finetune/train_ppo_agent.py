@@ -38,6 +38,8 @@ class TrainPPOAgent(TrainAgent):
         self.gae_lambda = cfg.train.get("gae_lambda", 0.95)
         self.target_kl = cfg.train.target_kl
         self.update_epochs = cfg.train.update_epochs
+        # read and not applied: entropy_loss = -eta is a constant of the parameters unless eta is learnable, and a
+        # learnable eta's loss terms beyond the policy term are not built
         self.ent_coef = cfg.train.get("ent_coef", 0)
         self.vf_coef = cfg.train.get("vf_coef", 0)
         self.model.vf_coef = self.vf_coef

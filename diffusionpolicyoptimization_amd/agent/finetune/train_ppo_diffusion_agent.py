@@ -23,6 +23,7 @@ from ... import ops
 from ...util.dist import allreduce_sum_, explained_variance_from_moments
 from ...util.scheduler import CosineAnnealingWarmupRestarts
 from ...util.timer import Timer
+from ...model.diffusion.diffusion_ppo import M_BC
 from .train_ppo_agent import TrainPPOAgent
 
 log = logging.getLogger(__name__)
@@ -176,6 +177,20 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         super().__init__(cfg)
         self.reward_horizon = cfg.get("reward_horizon", self.act_steps)
         self.learn_eta = self.model.learn_eta
+        # train.bc_loss_coeff: the weight of c_loss's behaviour-cloning term in the loss (the DPPO algorithm's
+        # `+ bc_loss * bc_loss_coeff`, which the reference comments out at :340-342; PARITY UNPINNED). 0, every
+        # shipped cfg but ft_ppo_diffusion_mlp_bc: the term is only reported (use_bc_loss) and the update is
+        # launch for launch what it is without the knob
+        self.bc_loss_coeff = float(self.bc_loss_coeff or 0)
+        if self.bc_loss_coeff < 0:
+            raise ValueError(f"train.bc_loss_coeff = {self.bc_loss_coeff} < 0")
+        if self.bc_loss_coeff > 0 and not self.use_bc_loss:
+            raise ValueError("train.bc_loss_coeff > 0 needs train.use_bc_loss: true")
+        if self.bc_loss_coeff > 0 and self.learn_eta:
+            raise ValueError("train.bc_loss_coeff > 0 with learn_eta: the behaviour-cloning term's derivative with "
+                             "respect to a learnable eta is not built")
+        self.bc_in_loss = bool(self.use_bc_loss) and self.bc_loss_coeff > 0
+        self.model.bc_loss_coeff = self.bc_loss_coeff
         if self.learn_eta:
             # the eta AdamW of agent :28-45 (Keras defaults, its own cosine-warmup schedule evaluated at
             # the eta optimizer's step count), stepped every eta_update_interval minibatches as the
@@ -689,18 +704,41 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
             stream.wait_event(ev_met)
         return enqueue
 
-    def _enqueue_unsplit(self, run_mb, dp):
+    def _enqueue_unsplit(self, run_mb, dp, bc=None):
         """DPPO_SPLIT_UPDATE=0: one launch sequence on the main stream into model.metrics and, under
-        data parallelism, one collective: gradients + metric sums."""
+        data parallelism, one collective: gradients + metric sums.
+        bc = (obs_flat, total_local, kf, rows_local_full) with train.bc_loss_coeff > 0: every minibatch's actor gradient gets
+        bc_loss_coeff * bc_loss of the minibatch's own rows before the collective and the optimizer step
+        (PPODiffusion.bc_grad over obs_flat[idx // K'] of its permutation window: one base chain per row, repeats
+        included, as the reference's obs_b); global_samples is the rows over all ranks, so the term rides in the
+        gradients' all-reduce, and its sum of clipped log-probs (metric slot M_BC) behind the other metric sums.
+        The term runs on this path only: the split / fused update with it is not built."""
         m = self.model
         ng, ext, met, allreduce = m.grads.numel(), m.grads_ext, m.metrics, self._bucket_allreduce
+        if bc is not None:
+            # one chunk size, so one workspace, for the full and the short minibatches of the update: a full
+            # minibatch of the reference's 50,000 rows is 500,000 BC rows, past the entry's 2 GiB workspace limit
+            obs_flat, total_local, kf, rows_full = bc
+            chunk = ops.bc_chunk(m.dims, m.precision, rows_full)
 
         def enqueue(mb, global_rows, stats, pre, slot):
             run_mb(*mb, global_rows=global_rows, adv_stats=stats)
+            if bc is not None:
+                idx = ops.feistel_permute(mb[1], mb[2], total_local, self.perm_seed, mb[0], self.device)
+                # (a window inside total_local never holds a negative index; no mask, so no host wait here)
+                m.bc_grad(obs_flat[idx // kf], self.bc_loss_coeff, accumulate=True, global_samples=global_rows,
+                          chunk=chunk)
             if dp:
                 _pack_metric_sums(ext, ng, met)
+                if bc is not None:
+                    ext[ng + 6:ng + 7].copy_(met[M_BC:M_BC + 1])
                 allreduce("all", ext)
                 _unpack_metric_sums(ext, ng, met)
+                if bc is not None:
+                    met[M_BC:M_BC + 1].copy_(ext[ng + 6:ng + 7])
+            if bc is not None:   # kept for this and the previous minibatch: the last APPLIED one's is the report
+                self._bc_sums[slot:slot + 1].copy_(met[M_BC:M_BC + 1])
+                self._bc_rows[slot] = (mb, global_rows)
         return enqueue
 
     # The optimiser step (agent :346) of one minibatch: step(lr, slot, tag) applies AdamW, sends the
@@ -792,7 +830,9 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         dp = self.world_size > 1
         W = self.world_size if dp else self.emulate_world
         num_batch, rows_local_full = minibatch_geometry(total_local, self.batch_size, W, self.dp_scale_batch)
-        split = os.environ.get("DPPO_SPLIT_UPDATE", "1") != "0"
+        # the behaviour-cloning term in the loss takes the unsplit path (_enqueue_unsplit), as max_grad_norm did
+        # before the device clip
+        split = os.environ.get("DPPO_SPLIT_UPDATE", "1") != "0" and not self.bc_in_loss
         # train.max_grad_norm (agent :349-354: tf.clip_by_norm(grad, 1.0) per variable) keeps the split
         # update (the device clip, _step_split); the unsplit path keeps the torch clip (_step_unsplit)
         clip_c = None
@@ -830,7 +870,11 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
                        self._enqueue_split(run_mb, stream, side, tagged))
             step, mets = self._step_split(bound, stream, side), self._met_dev
         else:
-            enqueue = self._enqueue_unsplit(run_mb, dp)
+            bc = (obs_flat, total_local, kf, rows_local_full) if self.bc_in_loss else None
+            if bc is not None:
+                self._bc_sums = torch.zeros(2, dtype=torch.float64, device=self.device)
+                self._bc_rows = [None, None]
+            enqueue = self._enqueue_unsplit(run_mb, dp, bc)
             step, mets = self._step_unsplit(bound, clip_c), (m.metrics, m.metrics)
         hp_, events, hook, learn_eta = self.host_profile, self.update_events, self.minibatch_hook, self.learn_eta
         adv_base, epoch0, steps0 = adv_tab.data_ptr(), 1000 * self.itr, opt.iterations
@@ -900,7 +944,11 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
         stream.synchronize()
         for g in (self._ipc_groups or {}).values():
             g.check()   # a barrier timeout in any bucket all-reduce of this update
-        if self.use_bc_loss and last_mb is not None:
+        if self.bc_in_loss:
+            # the last applied minibatch's value, from the metric slot its bc_grad left
+            if last_mb is not None:
+                info["bc_loss"] = self._bc_applied(last_mb, kf)
+        elif self.use_bc_loss and last_mb is not None:
             info["bc_loss"] = self._bc_loss_report(last_mb, obs_flat, total_local, kf)
         # explained variance (:373-377) from the moments value_moments stored before the epochs
         info["explained_var"] = explained_variance_from_moments(
@@ -930,6 +978,15 @@ class TrainPPODiffusionAgent(TrainPPOAgent):
             self._allreduce(t)
             s, n_el = float(t[0]), float(t[1])
         return -s / max(n_el, 1.0)
+
+    def _bc_applied(self, mb, kf):
+        """bc_loss of minibatch `mb` (the update's last applied one) from the sum of clipped log-probs its
+        bc_grad left in the metric slot (summed over ranks under data parallelism): one chain per row, so
+        rows x K' x xd elements."""
+        for slot, rec in enumerate(self._bc_rows):
+            if rec is not None and rec[0] == mb:
+                return -float(self._bc_sums[slot]) / (rec[1] * kf * self.model.dims.xd)
+        raise RuntimeError(f"no behaviour-cloning sum was kept for the update's last applied minibatch {mb}")
 
     def _clip_by_norm_per_tensor(self, clip_norm=1.0):
         """Else-branch of agent :349-353: tf.clip_by_norm(grad, 1.0) per variable (clip_norm:

@@ -80,12 +80,17 @@ __host__ __device__ inline uint32_t ws_off(const PpoWorkspace& w, const void* im
 // per-row source of a row-tile launch
 // ROWS_PRETRAIN: the pretraining loss p_losses (diffusion.py:179-202) through the TRAIN row tile:
 // row r is sample r, t and noise come with it, KF holds K (every t is a bucket)
-enum { ROWS_LOGPROB = 0, ROWS_TRAIN = 1, ROWS_VALUE = 2, ROWS_PRETRAIN = 3 };
+// ROWS_BC: the behaviour-cloning term (diffusion_ppo.py:63-71) through the TRAIN row tile: ROWS_LOGPROB's rows
+// (row g is sample g / KF, step g % KF of chains [nsamp][KF+1][XD]; no permutation, advantage or old log-prob);
+// hp.grad_scale is the launch-uniform d loss / d (a row's mean clipped log-prob)
+enum { ROWS_LOGPROB = 0, ROWS_TRAIN = 1, ROWS_VALUE = 2, ROWS_PRETRAIN = 3, ROWS_BC = 4 };
+// the modes that run the TRAIN instantiation of the actor row tile over the 64-padded images
+inline bool rows_train_mode(int mode) { return mode == ROWS_TRAIN || mode == ROWS_PRETRAIN || mode == ROWS_BC; }
 
 struct LossHP {
     float gamma_denoising, clip_coef, clip_coef_base, clip_coef_rate, min_lp_std, vf_coef;
     int norm_adv, reward_horizon;
-    float grad_scale;     // loss_scale / global_rows
+    float grad_scale;     // loss_scale / global_rows (ROWS_BC: -coeff loss_scale / (global_samples K'))
     float eta_unscale;    // learnable DDIM eta (DPPO_PPO_LEARN_ETA): 1 / the fp16 seed scale, else 0
     float clip_vloss;     // > 0: the clipped value loss against old_values (diffusion_ppo.py:110-116)
     const float* old_values;

@@ -53,5 +53,6 @@ struct ZeroArgs { void* p[4]; size_t n[4]; };
 int launch_zero(const ZeroArgs& z, unsigned blocks, hipStream_t s);
 // Per-(device, stream) device scratch that kernels leave zeroed between uses, created zeroed on first
 // use and kept for the process (one process-wide table, update.hip)
-enum { SCRATCH_TICKET = 0, SCRATCH_CRIT_COUNT = 1 };
+// (SCRATCH_BC_GRAD: dppo_bc_minibatch's accumulate form zeroes its own, the call's gradient before it is added)
+enum { SCRATCH_TICKET = 0, SCRATCH_CRIT_COUNT = 1, SCRATCH_BC_GRAD = 2 };
 int stream_scratch(hipStream_t s, int kind, size_t bytes, void** out);

@@ -8,6 +8,9 @@
 //                         (train_ppo_diffusion_agent.py:287-312) -> forward -> fused c_loss policy
 //                         term and its gradient (diffusion_ppo.py:45-106) -> backward dX chain,
 //                         writing feature-major activation/gradient images for the dW kernel
+//   actor, mode BC      : the TRAIN tile over LOGPROB's rows (every step of every sample's base-policy chain):
+//                         the behaviour-cloning term -mean clip(lp, -5, 2) (diffusion_ppo.py:63-71) and its
+//                         gradient in the epilogue, then TRAIN's backward
 //   critic, mode VALUE  : CriticObs forward (model/common/critic.py:40-54)
 //   critic, mode TRAIN  : forward -> v_loss gradient (diffusion_ppo.py:108-118) -> backward chain
 #include <stdlib.h>
@@ -130,6 +133,8 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
     constexpr bool train = TRAIN;
     // pretraining (ROWS_PRETRAIN) runs the TRAIN body with its own prologue rows and epilogue loss
     const bool pre = train && a.mode == ROWS_PRETRAIN;
+    // the behaviour-cloning term (ROWS_BC) runs it with LOGPROB's rows and an epilogue without ratio or advantage
+    const bool bc = train && a.mode == ROWS_BC;
     const int H = a.H;
     AT* tA = (AT*)(smem + S.tA);
     AT* tB = (AT*)(smem + S.tB);
@@ -178,7 +183,7 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
             if (pre) {                         // row = sample; t = KF-1-j below, KF = K
                 n = (int)gr;
                 j = KF - 1 - a.tsteps[gr];
-            } else if (train) {
+            } else if (train && !bc) {
                 const uint64_t idx = minibatch_row(a.row_index, (uint64_t)(a.start + gr), a.fk);
                 if (idx < a.fk.n) {   // tf.unravel_index; sample counts are < 2^32 (host-checked)
                     n = (int)((uint32_t)idx / (uint32_t)KF);
@@ -190,11 +195,11 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
             }
         }
         rn[tid] = n; rj[tid] = j;
-        if (train && !pre) {
+        if (train && !pre && !bc) {
             pre_adv = n >= 0 ? a.adv[n] : 0.f;
             pre_lpo = n >= 0 ? a.lp_old[(size_t)n * KF + j] : 0.f;
         }
-    } else if (train && !pre && tid == ROWS) {   // population mean / std of the minibatch (diffusion_ppo.py:74-75)
+    } else if (train && !pre && !bc && tid == ROWS) {   // population mean / std of the minibatch (diffusion_ppo.py:74-75)
         const double* S3 = a.adv_stats;
         const double mean = S3[1] / S3[0];
         const double var = fmax(S3[2] / S3[0] - mean * mean, 0.0);
@@ -300,7 +305,7 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
     if constexpr (train) store_accT<P, MT, NT>(wsr, ws_off(a.ws, a.ws.u1T), ldm32, ntile0, grow32, lane, acc);
     lds_sync();
     PHASE(1);
-    if (train && !pre) {   // loaded in the prologue, read from the epilogue on (after later barriers)
+    if (train && !pre && !bc) {   // loaded in the prologue, read from the epilogue on (after later barriers)
         if (tid < ROWS) { radv[tid] = pre_adv; rlpo[tid] = pre_lpo; }
         else if (tid == ROWS) {
             nrm[0] = pre_m; nrm[1] = pre_s;
@@ -391,7 +396,8 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
     // of wave 0 -> the row's mean log-prob and loss terms; (C) one (row, q) element per thread ->
     // d loss / d eps into the dy tile (A operand of the backward) and the dyT image.
     const float* bo = bias + 3 * H;            // RT_BOUT
-    const int nh = min(a.hp.reward_horizon, XD / a.Da) * a.Da;                      // [:, :reward_horizon]
+    // [:, :reward_horizon]; the behaviour-cloning term takes every element (diffusion_ppo.py:70)
+    const int nh = bc ? XD : min(a.hp.reward_horizon, XD / a.Da) * a.Da;
     float* e_lp = (float*)tB;                  // [ROWS][XD] (relu(h2) is dead once the out layer has run)
     float* e_mu = e_lp + ROWS * XD;            // [ROWS][XD]
     float* e_uc = e_mu + ROWS * XD;            // [ROWS][XD] 1 = x_recon not clipped
@@ -430,6 +436,9 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
             const float newlp = lpsum / (float)nh;
             if (!train) {
                 if (n >= 0 && a.lp_mean) a.lp_mean[(size_t)n * KF + j] = newlp;
+            } else if (bc) {
+                // -coeff mean clip(lp): the row's clipped sum for the metric, the launch-uniform seed for phase C
+                if (n >= 0) { pg = lpsum; dnewlp = a.hp.grad_scale; }
             } else if (n >= 0) {
                 float A = radv[r];
                 // the minibatch's quantile bounds on the raw advantage (DPPO_PPO_ADV_CLIP); the moments stay
@@ -461,7 +470,10 @@ __device__ __forceinline__ void actor_rowtile_body(const ActorArgs& a) {
             }
             e_dn[r] = dnewlp;
         }
-        if (train) {
+        if (bc) {
+            pg = wave_sum(pg);
+            if (tid == 0) atomic_add_metric(a.metrics, DPPO_METRIC_BC_LOGPROB, pg);
+        } else if (train) {
             pg = wave_sum(pg); kl = wave_sum(kl); cf = wave_sum(cf); ra = wave_sum(ra);
             if (tid == 0) {
                 atomic_add_metric(a.metrics, 0, pg);
@@ -631,11 +643,11 @@ static int launch_actor_t(const ActorArgs& a, hipStream_t s, bool dry) {
     { const int rc_ = dppo_func_lds((const void*)k, (size_t)S.total); if (rc_) return rc_; }
     // TRAIN mode covers every row of the 64-padded feature-major images (padding rows get
     // finite activations and zero gradients), so the dW kernel never reads unwritten memory
-    const int64_t all = (a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN) ? (int64_t)a.ws.ldm : a.nrows;
+    const int64_t all = rows_train_mode(a.mode) ? (int64_t)a.ws.ldm : a.nrows;
     const int64_t rows = (a.row_end > 0 ? a.row_end : all) - a.row0;
     const int64_t grid = (rows + 16 * MT - 1) / (16 * MT);
     if (grid <= 0) return DPPO_OK;
-    DppoKtScope kt(a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN ? KT_ACTOR_TRAIN : KT_ACTOR_LOGPROB, s);
+    DppoKtScope kt(rows_train_mode(a.mode) ? KT_ACTOR_TRAIN : KT_ACTOR_LOGPROB, s);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * WAVES), S.total, s, a);
     DPPO_HIP(hipGetLastError());
     return DPPO_OK;
@@ -643,7 +655,7 @@ static int launch_actor_t(const ActorArgs& a, hipStream_t s, bool dry) {
 
 template <class P, int MT, int NT, int NO, int KSI, int WAVES, bool O4, int ACT>
 static int launch_actor_m(const ActorArgs& a, hipStream_t s, bool dry) {
-    return (a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN) ? launch_actor_t<P, MT, NT, NO, KSI, true, WAVES, O4, ACT>(a, s, dry)
+    return rows_train_mode(a.mode) ? launch_actor_t<P, MT, NT, NO, KSI, true, WAVES, O4, ACT>(a, s, dry)
                                 : launch_actor_t<P, MT, NT, NO, KSI, false, WAVES, O4, ACT>(a, s, dry);
 }
 
@@ -725,7 +737,7 @@ static int launch_actor_2b(const ActorArgs& a, const ActorTilePlan& p, int act, 
 
 int launch_actor_rowtile(const ActorArgs& a, const NetSpec& net, hipStream_t s, bool dry) {
     // TRAIN modes cover the 64-padded images (launch_actor_t), the others the rows given
-    const int64_t rows = (a.mode == ROWS_TRAIN || a.mode == ROWS_PRETRAIN) ? (int64_t)a.ws.ldm : a.nrows;
+    const int64_t rows = rows_train_mode(a.mode) ? (int64_t)a.ws.ldm : a.nrows;
     const int precision = net.precision, act = net.act;   // the image's activation picks the instantiation
     const ActorTilePlan p = actor_tile_plan(precision, a.H, a.XD, rows, act);
     if (precision == DPPO_BF16) return launch_actor_2b<PolicyBF16>(a, p, act, s, dry);

@@ -731,3 +731,98 @@ extern "C" int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const 
     DPPO_HIP(hipGetLastError());
     return launch_time_bwd(D, precision, ws, packed_actor, actor_params, ga, D.K, 1, s, true, plain);
 }
+
+// ---------------------------------------------------------------------------------------------
+// the behaviour-cloning term of the PPO loss (include/dppo.h dppo_bc_minibatch; diffusion_ppo.py:63-71):
+// the TRAIN row tile in mode ROWS_BC over n K' rows, then the actor's dW and time-MLP backward as in
+// part 1 of a minibatch
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void add_into_kernel(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] += src[i];
+}
+
+extern "C" int dppo_bc_minibatch(const dppo_dims* d, int precision, const void* packed_ft, const float* actor_params,
+                                 const float* sched, const float* cond, const float* chains, int n,
+                                 int64_t global_samples, float min_logprob_std, float coeff, float loss_scale, int flags,
+                                 void* workspace, float* grads, double* metrics, void* stream) {
+    Dims D;
+    int rc = dppo_check_dims(d, &D);
+    if (rc) return rc;
+    DPPO_CHECK(dppo_prec_ok(precision), "bad precision %d", precision);
+    DPPO_CHECK(packed_ft && actor_params && sched && cond && chains && workspace && grads && metrics,
+               "dppo_bc_minibatch: null pointer");
+    DPPO_CHECK(n >= 1, "dppo_bc_minibatch: n < 1");
+    DPPO_CHECK(global_samples >= n, "dppo_bc_minibatch: global_samples < n");
+    DPPO_CHECK(coeff >= 0.f, "dppo_bc_minibatch: coeff must be >= 0");   // a NaN fails the comparison too
+    DPPO_CHECK(!(flags & DPPO_PPO_LEARN_ETA),
+               "dppo_bc_minibatch: DPPO_PPO_LEARN_ETA is not supported (the term's derivative with respect to a "
+               "learnable eta is not built)");
+    DPPO_CHECK((flags & ~(DPPO_PPO_L2_DEFERRED | DPPO_BC_ACCUMULATE)) == 0, "dppo_bc_minibatch: unknown flags 0x%x", flags);
+    if (D.KF > PPO_MAX_BUCKETS)
+        return dppo_set_error(DPPO_EUNSUPPORTED, "dppo_bc_minibatch: ft_denoising_steps %d > %d unsupported (bucket sums)",
+                              D.KF, PPO_MAX_BUCKETS);
+    DPPO_CHECK((int64_t)n * D.KF < ((int64_t)1 << 31), "dppo_bc_minibatch: %d samples x steps exceed 2^31", n);
+    const int rows = n * D.KF;
+    hipStream_t s = (hipStream_t)stream;
+    const PpoWorkspace ws = make_ppo_workspace(D, precision, rows, (uint8_t*)workspace);
+    DPPO_CHECK(ws.total < ((size_t)1 << 31), "dppo_bc_minibatch: workspace for %d rows exceeds 2 GiB", rows);
+    const NetSpec anet = actor_net(D, precision, dppo_image_attrs(packed_ft));
+    SchedParams sp;
+    rc = dppo_sched_lookup(D, sched, "dppo_bc_minibatch", &sp);
+    if (rc) return rc;
+    const FlatOffsets FA = make_flat_offsets(anet);
+    const bool plain = anet.plain();   // no l2: nothing to defer
+    const bool l2_def = (flags & DPPO_PPO_L2_DEFERRED) != 0 && !plain;
+    const bool accumulate = (flags & DPPO_BC_ACCUMULATE) != 0;
+    ActorArgs aa = {};
+    aa.packed = (const uint8_t*)packed_ft;
+    aa.L = make_mlp_layout(anet);
+    aa.sched = sched; aa.obs = cond; aa.chains = chains;
+    aa.XD = D.XD; aa.SD = D.SD; aa.TD = D.TD; aa.IN = D.IN; aa.H = D.H; aa.KF = D.KF; aa.Da = D.Da; aa.TS = D.TS;
+    aa.mode = ROWS_BC; aa.nrows = rows; aa.ws = ws; aa.metrics = metrics;
+    aa.x0_clip = sp.clip;
+    aa.hp.min_lp_std = min_logprob_std;
+    aa.hp.reward_horizon = D.XD / D.Da;   // unread: the term takes every element
+    // bc_loss = -sum clip(lp) / (global_samples K' XD): the row tile divides a row's seed by XD itself (phase C), so
+    // the launch-uniform seed is d loss / d (the row's mean clipped log-prob); fp16: times the backward seed scale
+    const int64_t global_rows = global_samples * D.KF;
+    const float gscale = dppo_grad_scale_rows(precision, global_rows);
+    aa.hp.grad_scale = -coeff * loss_scale / ((float)global_samples * (float)D.KF) * gscale;
+    rc = launch_actor_rowtile(aa, anet, s, true);   // rejected geometries leave the outputs untouched
+    if (rc) return rc;
+    rc = time_bwd_check(D, D.KF);
+    if (rc) return rc;
+    // accumulate: the tail's kernels store their tensors (in_b, the time MLP, l2 and W_out through the fold), so
+    // the call's gradient is formed apart, in a scratch buffer kept per stream, and added in one launch
+    float* ga = grads;
+    if (accumulate) {
+        rc = stream_scratch(s, SCRATCH_BC_GRAD, FA.count * sizeof(float), (void**)&ga);
+        if (rc) return rc;
+    }
+    ZeroArgs z = {};
+    z.p[0] = ga; z.n[0] = FA.count * sizeof(float);
+    z.p[1] = ws.pl2;   // pl2 | pa0 | gseg's bucket rows the dW adds into, as a minibatch's actor half zeroes them
+    z.n[1] = (size_t)((const uint8_t*)(ws.gseg + (size_t)dppo_cdiv(D.KF, 16) * 16 * D.H) - (const uint8_t*)ws.pl2);
+    if (!accumulate) { z.p[2] = metrics + DPPO_METRIC_BC_LOGPROB; z.n[2] = sizeof(double); }
+    {
+        DppoKtScope kt(KT_ZERO, s);
+        rc = launch_zero(z, 64, s);
+        if (rc) return rc;
+    }
+    rc = launch_actor_rowtile(aa, anet, s);
+    if (rc) return rc;
+    DWItem items[4];
+    actor_dw_items(D, ws, ga, false, l2_def, items, plain);
+    {
+        DppoKtScope kt(KT_DW_ACTOR, s);
+        rc = launch_dw(DWTile::ACTOR, precision, items, 4, ws, 1.f / gscale, nullptr, PPO_MIN_CHUNK_ROWS, s);
+        if (rc) return rc;
+    }
+    rc = launch_time_bwd(D, precision, ws, packed_ft, actor_params, ga, D.KF, D.TS, s, !l2_def, plain);
+    if (rc || !accumulate) return rc;
+    const size_t cnt = FA.count;
+    const unsigned blocks = (unsigned)(dppo_cdiv((int)((cnt + 255) / 256), 4) < 1024 ? dppo_cdiv((int)((cnt + 255) / 256), 4) : 1024);
+    hipLaunchKernelGGL(add_into_kernel, dim3(blocks), dim3(256), 0, s, grads, (const float*)ga, cnt);
+    DPPO_HIP(hipGetLastError());
+    return DPPO_OK;
+}

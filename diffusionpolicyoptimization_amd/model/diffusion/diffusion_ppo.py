@@ -13,6 +13,7 @@ from .diffusion_vpg import VPGDiffusion, _as_state
 # metrics slots written by the kernels (sums over rows; see update.hip)
 M_PG, M_VLOSS, M_KL, M_CLIPFRAC, M_RATIO = 0, 1, 2, 3, 4
 M_DETA = 8   # learn_eta: d loss / d eta (DPPO_PPO_LEARN_ETA)
+M_BC = _lib.DPPO_METRIC_BC_LOGPROB   # bc_grad: the sum of the clipped log-probs (dppo_bc_minibatch)
 
 
 class PPODiffusion(VPGDiffusion):
@@ -36,6 +37,9 @@ class PPODiffusion(VPGDiffusion):
         self.clip_advantage_upper_quantile = float(clip_advantage_upper_quantile)
         self.norm_adv = norm_adv
         self.vf_coef = vf_coef
+        # the weight of c_loss's behaviour-cloning term in the gradient (the agent sets it from
+        # cfg.train.bc_loss_coeff); 0: the term is reported only, as in the reference (:340-342)
+        self.bc_loss_coeff = 0.0
         self.metrics = torch.zeros(16, dtype=torch.float64, device=self.device)
         self._ws = {}
 
@@ -113,6 +117,14 @@ class PPODiffusion(VPGDiffusion):
         noise does not depend on use_bc_loss; x_T / noise inject the draws (tests)."""
         state = _as_state(obs, self.device, self.dims.sd)
         n = state.shape[0]
+        ch = self._bc_chains(state, x_T, noise)
+        lp = self.get_logprobs(state, ch)
+        return -float(lp.clamp(-5, 2).mean())
+
+    def _bc_chains(self, state, x_T=None, noise=None):
+        """The frozen base policy's chains [n, K'+1, xd] for these observations (bc_loss and bc_grad draw them the
+        same way, one call id of the counter each)."""
+        n = state.shape[0]
         calls = getattr(self, "_bc_calls", 0)
         _, ch = ops.sample(self.dims, self.precision, self.packed_base, self.packed_base, self.sched_for(False), state,
                            x_T=x_T, noise=noise, seed=self.seed, call_id=(1 << 40) + calls,
@@ -120,15 +132,46 @@ class PPODiffusion(VPGDiffusion):
                            min_sampling_std=self.get_min_sampling_denoising_std(), randn_clip=self.randn_clip_value,
                            final_clip=self.final_action_clip_value, want_chains=True)
         self._bc_calls = calls + 1
-        lp = self.get_logprobs(state, ch.view(n, self.ft_denoising_steps + 1, self.dims.xd))
-        return -float(lp.clamp(-5, 2).mean())
+        return ch.view(n, self.ft_denoising_steps + 1, self.dims.xd)
+
+    def bc_grad(self, obs, coeff, *, accumulate=True, global_samples=None, loss_scale=1.0, l2_deferred=False,
+                chunk=None, x_T=None, noise=None):
+        """coeff * bc_loss in the gradient: the base chains drawn exactly as bc_loss draws them (the same
+        ops.sample call, the same (1 << 40) + _bc_calls call ids, so a run's rollout noise does not depend on the
+        knob), then ops.bc_minibatch over them into self.grads[:n_actor] and self.metrics[M_BC] (the sum of the
+        clipped log-probs). accumulate (the default) adds to both, on top of a PPO minibatch's actor gradients
+        (which zeroed the slot); otherwise both are overwritten. chunk: ceil(n / chunk) accumulate calls of at
+        most `chunk` samples on one workspace of chunk * K' rows, whatever n is (a caller that passes one chunk
+        for its full and its short minibatches reuses one workspace); by default ops.bc_chunk(n), which is n where
+        the workspace of n * K' rows stays under ops.BC_WORKSPACE_BYTES and the calls' even share above that (the
+        entry refuses a workspace of 2 GiB: 29,000 samples at K' = 10 in bf16, 14,700 in fp32). global_samples (default n) and loss_scale are a data-parallel
+        rank's: the samples over all ranks and the minibatch's scale. Returns bc_loss of what the slot then holds,
+        a device scalar. The derivative with respect to a learnable eta is not built."""
+        if self.learn_eta:
+            raise ValueError("PPODiffusion.bc_grad: the behaviour-cloning term with learn_eta is not built")
+        state = _as_state(obs, self.device, self.dims.sd)
+        n = state.shape[0]
+        g = n if global_samples is None else int(global_samples)
+        kf = self.ft_denoising_steps
+        ch = self._bc_chains(state, x_T, noise)
+        step = ops.bc_chunk(self.dims, self.precision, n) if chunk is None else max(1, int(chunk))
+        ws = self.workspace(step * kf)
+        for a in range(0, n, step):
+            out = ops.bc_minibatch(self.dims, self.precision, self.packed_ft, self.actor_ft_params, self.sched,
+                                   state[a:a + step], ch[a:a + step], ws, self.grads, self.metrics, coeff,
+                                   min_logprob_std=self.min_logprob_denoising_std, global_samples=g,
+                                   loss_scale=loss_scale, accumulate=accumulate or a > 0, l2_deferred=l2_deferred)
+        return out
 
     def c_loss(self, obs, chains_prev, chains_next, denoising_inds, returns, oldvalues, advantages, oldlogprobs,
                use_bc_loss=False, reward_horizon=4):
         """diffusion_ppo.py:32-132 on an explicit batch. Returns (pg_loss, entropy_loss, v_loss, clipfrac,
         approx_kl, ratio, bc_loss, eta) as floats; gradients are left in self.grads (of pg_loss +
-        vf_coef v_loss: the agent's loss, train_ppo_diffusion_agent.py:340-342; bc_loss is reported only)."""
-        bc = self.bc_loss(obs) if use_bc_loss else 0.0   # :63-71
+        vf_coef v_loss: the agent's loss, train_ppo_diffusion_agent.py:340-342; bc_loss is reported only while
+        self.bc_loss_coeff is 0; above 0, use_bc_loss adds bc_loss_coeff * bc_loss to that loss (bc_grad) and the
+        tuple's bc_loss is read from the metric slot it leaves)."""
+        bc_in_grad = use_bc_loss and self.bc_loss_coeff > 0
+        bc = self.bc_loss(obs) if use_bc_loss and not bc_in_grad else 0.0   # :63-71
         dev = self.device
         state = _as_state(obs, dev, self.dims.sd)
         b = state.shape[0]
@@ -157,6 +200,8 @@ class PPODiffusion(VPGDiffusion):
                                       self.clip_advantage_upper_quantile, stats[3:].view(1, 2))
         self.minibatch(state, ch, lp_old, adv, ret, 0, 0, 0, b, reward_horizon=reward_horizon, row_index=row_index,
                        old_values=oldv, adv_stats=stats)
+        if bc_in_grad:   # on top of the minibatch's actor gradients; the minibatch zeroed the slot
+            bc = float(self.bc_grad(state, self.bc_loss_coeff, accumulate=True))
         m = (self.metrics[:5] / b).cpu().numpy()
         eta = self.current_eta()
         # entropy_loss = -mean(eta), the last element mean(eta) (diffusion_ppo.py:49, 131); with

@@ -1312,6 +1312,66 @@ def pretrain_minibatch(d: ModelDims, precision, packed_actor, actor_params, sche
     return metrics[0] * (float(loss_scale) / (g * d.xd))
 
 
+# bc_chunk's default workspace budget: a dppo_bc_minibatch over n samples takes a PPO workspace of n * K' rows
+# (about 7.3 KB a row in the 2-byte precisions at hopper's widths, 14.6 KB in fp32), and the entry refuses one of
+# 2 GiB or more
+BC_WORKSPACE_BYTES = 1 << 29
+
+
+def bc_chunk(d: ModelDims, precision, n, budget=BC_WORKSPACE_BYTES):
+    """Samples per dppo_bc_minibatch call when n samples are walked in accumulate calls over one workspace of at
+    most `budget` bytes (dppo_ppo_workspace_bytes(chunk * K') <= budget < 2 GiB): n itself where that fits, else
+    the calls' even share, ceil(n / calls) with the fewest calls that fit. Host arithmetic only."""
+    n, kf, prec = int(n), d.ft_denoising_steps, _prec(precision)
+    if n < 1 or not 0 < budget < (1 << 31):
+        raise ValueError(f"bc_chunk: need n >= 1 and 0 < budget < 2 GiB, got n = {n}, budget = {budget}")
+    fits = lambda s: _workspace_bytes(d, prec, s * kf) <= budget
+    if fits(n):
+        return n
+    if not fits(1):
+        raise ValueError(f"bc_chunk: one sample's workspace ({_workspace_bytes(d, prec, kf)} B) exceeds the budget {budget}")
+    lo, hi = 1, n          # fits(lo), not fits(hi): the workspace grows with the rows
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+    calls = -(-n // lo)
+    return -(-n // calls)
+
+
+def bc_minibatch(d: ModelDims, precision, packed_ft, actor_params, sched, cond, chains, workspace, grads, metrics,
+                 coeff, min_logprob_std=0.1, global_samples=None, loss_scale=1.0, accumulate=False, l2_deferred=False):
+    """The behaviour-cloning term coeff * bc_loss (diffusion_ppo.py:63-71) and its actor gradient for n
+    observations cond [n, SD] and their base-policy chains [n, K'+1, XD]; see include/dppo.h. The sum of the
+    clipped log-probs lands in metrics[DPPO_METRIC_BC_LOGPROB]; accumulate adds to it and to grads[:actor count]
+    instead of overwriting them. grads beyond the actor's count and every other metric slot are not touched.
+    Returns bc_loss of what the slot holds so far as a device scalar (-slot / (global_samples * K' * xd))."""
+    n = cond.shape[0]
+    g = n if global_samples is None else int(global_samples)
+    kf = d.ft_denoising_steps
+    _check(cond, (n, d.sd), torch.float32, "cond")
+    _check(chains, (n, kf + 1, d.xd), torch.float32, "chains")
+    na = _n_params(d)[0]
+    _check(actor_params, (na,), torch.float32, "actor_params")
+    for t, nm in ((packed_ft, "packed_ft"), (sched, "sched"), (workspace, "workspace"), (grads, "grads")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{nm}: expected a device tensor")
+    if grads.dtype != torch.float32 or not grads.is_contiguous() or grads.numel() < na:
+        raise ValueError("grads: needs contiguous fp32 of at least the actor parameter count")
+    _check(metrics, (16,), torch.float64, "metrics")
+    for t, nm in ((chains, "chains"), (actor_params, "actor_params"), (grads, "grads"), (metrics, "metrics"),
+                  (workspace, "workspace"), (packed_ft, "packed_ft"), (sched, "sched")):
+        if t.device != cond.device:
+            raise ValueError(f"{nm}: on {t.device}, cond on {cond.device}")
+    need = _workspace_bytes(d, _prec(precision), int(n * kf))
+    if workspace.numel() < need:
+        raise ValueError(f"workspace too small: {workspace.numel()} < {need}")
+    flags = (_lib.DPPO_BC_ACCUMULATE if accumulate else 0) | (_lib.DPPO_PPO_L2_DEFERRED if l2_deferred else 0)
+    _lib.call("dppo_bc_minibatch", ctypes.byref(_dims_c(d)), _prec(precision), ptr(packed_ft), ptr(actor_params),
+              ptr(sched), ptr(cond), ptr(chains), int(n), int(g), float(min_logprob_std), float(coeff),
+              float(loss_scale), int(flags), ptr(workspace), ptr(grads), ptr(metrics), stream_handle(cond.device))
+    return metrics[_lib.DPPO_METRIC_BC_LOGPROB] * (-1.0 / (g * kf * d.xd))
+
+
 def adamw(params, grads, m, v, step, lr, weight_decay=0.004, beta1=0.9, beta2=0.999, eps=1e-7, mode="keras"):
     n = params.numel()
     for t, nm in ((grads, "grads"), (m, "m"), (v, "v")):

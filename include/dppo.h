@@ -688,6 +688,52 @@ DPPO_API int dppo_pretrain_minibatch(const dppo_dims* d, int precision, const vo
                             const int32_t* t, const float* noise, int rows, int64_t global_rows, float loss_scale,
                             void* workspace, float* grads, double* metrics, void* stream);
 
+/* ---- the behaviour-cloning term of the PPO loss and its actor gradient (an addition within ABI 15):
+ * loss = pg_loss + vf_coef v_loss + bc_loss_coeff bc_loss (the DPPO algorithm; the reference computes bc_loss at
+ * model/diffusion/diffusion_ppo.py:63-71 and comments the term out of the loss at
+ * agent/finetune/train_ppo_diffusion_agent.py:340-342, so parity is unpinned).
+ * For n observations cond [n][cond_steps*obs_dim] and the chains [n][K'+1][horizon*action_dim] the caller sampled
+ * from the frozen BASE policy (every denoising step on the base actor; dppo_sample with packed_ft = packed_base),
+ * row g = (sample g / K', step j = g % K') as in dppo_logprob:
+ *   lp[g][q] = Normal(mu_ft(chains[i][j], t = K'-1-j), clip(sigma_t, min_logprob_std, 1e6)).log_prob(chains[i][j+1])
+ *   bc_loss  = -sum_{g,q} clip(lp, -5, 2) / (global_samples K' horizon*action_dim)     over EVERY element q
+ * metrics[DPPO_METRIC_BC_LOGPROB] (fp64, device) receives this call's sum of clip(lp, -5, 2); grads[0 : actor_count]
+ * receive coeff * loss_scale * d bc_loss / d actor_ft: d / d lp = -coeff loss_scale / (global_samples K' XD) where
+ * -5 <= lp <= 2 (the bounds pass the gradient, as tf.clip_by_value does) and 0 elsewhere, then the PPO update's own
+ * chain (mu, clip(x_recon) under the schedule table's record as in dppo_logprob, the row tile's backward, the
+ * actor's weight-gradient launch and time-MLP backward). The chains are data and carry no gradient. It runs the
+ * TRAIN instantiations of the actor row tile over rows = n K' rows: dppo_ppo_plan{,_act}(DPPO_PLAN_TRAIN, rows)
+ * reports the tile. Workspace: dppo_ppo_workspace_bytes(d, precision, n * K'), any contents.
+ * flags: DPPO_PPO_L2_DEFERRED (the factored l2 form of dppo_ppo_minibatch) and DPPO_BC_ACCUMULATE.
+ *   without DPPO_BC_ACCUMULATE: grads[0 : actor_count] and the metric slot are OVERWRITTEN;
+ *   with it: nothing is zeroed and both are ADDED to, so a caller puts the term on top of a PPO minibatch's actor
+ *     gradients (both factored, or both materialised) or walks a large batch in chunks of samples over one
+ *     workspace. The call forms its gradient in a per-stream scratch buffer the library keeps (actor_count floats,
+ *     allocated on the stream's first such call) and adds it in one launch.
+ *   grads beyond the actor's count and every other metric slot are untouched in both forms.
+ *   accepted: every precision, both row tiles (32 and 64 rows), every activation, both heads, DDPM and DDIM tables,
+ *     a table record with any bound or x0-prediction (as dppo_logprob), global_samples >= n (a data-parallel
+ *     rank's share: global_samples over all ranks, loss_scale the minibatch's), coeff >= 0 (0: zero gradients).
+ *   refused with DPPO_EINVAL and a message of its own, nothing enqueued, outputs untouched:
+ *     a null pointer                          "dppo_bc_minibatch: null pointer"
+ *     n < 1                                   "dppo_bc_minibatch: n < 1"
+ *     global_samples < n                      "dppo_bc_minibatch: global_samples < n"
+ *     a NaN or negative coeff                 "dppo_bc_minibatch: coeff must be >= 0"
+ *     DPPO_PPO_LEARN_ETA                      "dppo_bc_minibatch: DPPO_PPO_LEARN_ETA is not supported ..." (the
+ *                                             term's derivative with respect to a learnable eta is out of scope)
+ *     any other flag bit                      "dppo_bc_minibatch: unknown flags 0x%x"
+ *   refused with DPPO_EUNSUPPORTED on the lines of the geometry table above that dppo_ppo_minibatch's actor half is
+ *   refused on: ft_denoising_steps > 64 ("dppo_bc_minibatch: ft_denoising_steps %d > 64 unsupported (bucket
+ *   sums)"), a geometry without a TRAIN instantiation and the 64-row tile's LDS line ("actor row tile needs %zu B
+ *   LDS"), the dispatch's own messages.
+ * tests/test_bc_grad_gpu.py pins this. ---- */
+enum { DPPO_METRIC_BC_LOGPROB = 9 };   /* metric slot: sum of clip(lp, -5, 2) over the call's (or calls') elements */
+enum { DPPO_BC_ACCUMULATE = 16 };      /* dppo_bc_minibatch's flags; shares the bit space of DPPO_PPO_* */
+DPPO_API int dppo_bc_minibatch(const dppo_dims* d, int precision, const void* packed_ft, const float* actor_params,
+                               const float* sched, const float* cond, const float* chains, int n,
+                               int64_t global_samples, float min_logprob_std, float coeff, float loss_scale, int flags,
+                               void* workspace, float* grads, double* metrics, void* stream);
+
 /* One half of dppo_ppo_minibatch on the caller's stream, so a caller can overlap the critic's half
  * of minibatch i+1 with the actor's tail of minibatch i: part 1 = the actor (zeroes the actor
  * gradients and metrics 0, 2..15; row tiles, dW, time-MLP backward; needs adv_stats), part 2 =
